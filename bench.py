@@ -16,14 +16,19 @@ Infinity Cache).  Every GPU processes its own replica batch (frame k -> GPU k mo
 collective (weak scaling); value = frames all ranks processed / max-over-ranks time.  Each rank first
 binds itself to the CPUs of its GPU's NUMA node (mi_thread_bind_near_device; --no-numa-bind to skip).
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the JSON line; beside the headline it carries
   roofline     -- the dominant kernel's algorithmic bytes per launch (for the fused single-read kernel: the whole
                   path's 3.5 W H per frame) / its average launch duration (HIP events stamped by the dispatches
                   themselves on the launch stream inside the timed region; for N > 1 averaged over the ranks,
-                  with the slowest and fastest rank beside it) against the 8 TB/s HBM peak;
+                  with the slowest and fastest rank beside it) against the 8 TB/s HBM peak.
+--full adds everything else, after the timed region:
+  parity_spot_check -- first, middle and last frame of the last step against the CPU oracle;
+  nv12_1080p   -- the same protocol on 1920x1080 frames;
+  stream_4k60_512_all_gpus (N > 1 or --force-dist), opencv_cross_check (where cv2 exists), extras (N = 1) -- secondary figures;
   cpu_baseline -- the CPU oracle (a port of OpenCV 4.4's arithmetic, see oracle/) timed on this
                   host's cores on a bounded sample of the same workload (rank 0, after the other ranks have left).
-The oracle is used here only for that leg and for a one-frame parity spot check.
+The oracle is used here only for that leg and for the parity spot check.
+--dump-outputs DIR writes what the last timed step computed (rank 0's batch) as .npy files: see dump_outputs().
 """
 from __future__ import annotations
 
@@ -42,6 +47,8 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
 HBM_MEASURED_COPY_GBS = 6290.0  # same guide: float4 copy ceiling
 DEADLINE_DEFAULT_S = 480.0      # launcher deadline; a torchrun rank's own watchdog fires RANK_WATCHDOG_SLACK_S later: 510 s < the driver's 600 s
 RANK_WATCHDOG_SLACK_S = 30.0
+DUMP_SAMPLE = 1 << 23           # output bytes --dump-outputs writes as float32: 32 MiB of the 64 MB a dump may take
+DUMP_SEED = 0x5EED0D
 
 
 def parse_args(argv=None):
@@ -49,6 +56,11 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the parity spot check, the 1920x1080 leg, the stream / OpenCV / extras "
+                         "figures and the CPU baseline (a plain run does only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float, at most 64 MB; see dump_outputs)")
     ap.add_argument("--batch", type=int, default=64, help="frames per GPU per step")
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
@@ -73,7 +85,10 @@ def parse_args(argv=None):
                     help="whole-job deadline: the launcher ends its children by PID, says which phase each rank was in and exits 124; "
                          "a rank started by torchrun ends itself 30 s later (0 = none).  The default keeps both inside the 600 s the "
                          "driver gives a bench run, so a stuck job names its ranks' phases before it is killed from outside")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---- heartbeats ------------------------------------------------------------------------------------------------------
@@ -339,6 +354,38 @@ def device_for_collectives(torch, backend, local_rank):
     return torch.device("cuda", local_rank) if backend == "nccl" else torch.device("cpu")
 
 
+def dump_outputs(d_out, out_dir):
+    """What a caller of the timed path receives -- the output batch of the last step, n_frames x NV12 frame bytes -- written to
+    `out_dir` so that two builds can be compared output for output (the bench's inputs are seeded: the same arguments give the same
+    frames).  The batch is larger than a dump may be (64 x 4K frames = 796 MB), so:
+      frames_out_sample.npy  float32 [min(DUMP_SAMPLE, bytes)]  the output bytes at fixed positions, one in each of DUMP_SAMPLE equal
+                             strata of the flattened batch, drawn by a generator seeded with DUMP_SEED (the whole batch when smaller);
+      frames_out_hist.npy    float64 [n_frames, 256]            every output frame's byte histogram, so that every pixel is counted.
+    Returns the paths written."""
+    import numpy as np
+    import torch
+    from mi_lumaeq import xfer
+    flat = d_out.reshape(-1)
+    n = flat.numel()
+    if n <= DUMP_SAMPLE:
+        idx = torch.arange(n, device=flat.device)
+    else:
+        stride = n // DUMP_SAMPLE
+        g = torch.Generator(device=flat.device)
+        g.manual_seed(DUMP_SEED)
+        idx = (torch.arange(DUMP_SAMPLE, device=flat.device) * stride +
+               torch.randint(0, stride, (DUMP_SAMPLE,), device=flat.device, generator=g))
+    sample = xfer.to_host(flat[idx]).astype(np.float32)
+    hist = torch.stack([torch.bincount(d_out[k].reshape(-1).to(torch.int32), minlength=256) for k in range(d_out.shape[0])])
+    hist = xfer.to_host(hist).astype(np.float64)
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    paths = [out_dir / "frames_out_sample.npy", out_dir / "frames_out_hist.npy"]
+    np.save(paths[0], sample)
+    np.save(paths[1], hist)
+    return paths
+
+
 def opencv_cross_check(ctx, w, h, dist_name):
     """the oracle is a restatement (parity unpinned).  Wherever a real OpenCV is importable, compare the GPU path with cv2
     itself and say so in the JSON line; None when there is no cv2 (this image has none).  The bench's own resolution AND 1920x1080
@@ -506,7 +553,7 @@ def main():
 
     # parity spot check of the measured configuration (rank 0; first, middle and last frame of the last step) -- checker only
     parity = None
-    if rank == 0 and run_ok:
+    if rank == 0 and run_ok and args.full:
         import numpy as np
         import oracle
         parity = True
@@ -523,11 +570,14 @@ def main():
             dist.destroy_process_group()
         raise SystemExit("REFUSING TO REPORT: " + (run_err or ("PARITY FAILURE: GPU output differs from the oracle" if parity is False
                                                                  else "another rank failed its run or parity check")))
+    if rank == 0 and args.dump_outputs:
+        hb("dump_outputs")
+        dump_outputs(d_out, args.dump_outputs)
 
     # The north star asks for 1920x1080 next to 3840x2160 at every GPU count: the same protocol (barriers on both sides, max over
     # ranks) on 4x as many frames of a quarter of the size, so that it is reported by the 1/2/4/8 runs as well.  Not the headline.
     second = None
-    if (w, h) == (3840, 2160) and not args.no_second_resolution:
+    if args.full and (w, h) == (3840, 2160) and not args.no_second_resolution:
         hw, hh, hb2 = 1920, 1080, 4 * B
         hb("second_resolution")
         del d_in, d_out
@@ -559,7 +609,7 @@ def main():
     # nv12_stream child per rank, which doubles the processes on the GPUs (four ranks rehearsed on one GPU = 8 GPU processes, more than
     # a gpurun box allows -- docs/experiments.md R4.1).  Every rank takes part in the reductions whatever happened to its own leg.
     stream_all = None
-    if use_dist and not args.no_extras and (w, h) == (3840, 2160):
+    if args.full and use_dist and not args.no_extras and (w, h) == (3840, 2160):
         barrier()
         hb("stream_all_ranks")
         try:
@@ -701,12 +751,12 @@ def main():
             return {"error": repr(e)}
     if stream_all is not None:
         out["stream_4k60_512_all_gpus"] = stream_all
-    if world == 1:
+    if args.full and world == 1:
         out["opencv_cross_check"] = guarded(opencv_cross_check, ctx, w, h, args.dist)
-    if world == 1 and not use_dist and not args.no_extras:       # (--force-dist behaves like a rank of an N>1 job: no N=1 extras)
+    if args.full and world == 1 and not use_dist and not args.no_extras:     # (--force-dist behaves like a rank of an N>1 job: no N=1 extras)
         hb("extras")
         out["extras"] = guarded(extras, ctx, args, torch, mi_lumaeq, synth)
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         hb("cpu_baseline")                                   # N > 1 as well: rank 0 alone by now, the other ranks have exited
         out["cpu_baseline"] = guarded(cpu_baseline, args, w, h)
     line = (json.dumps(out) + "\n").encode()

@@ -218,7 +218,7 @@ def test_bench_two_ranks_contract_on_gpu():
     import json
     env = {k: v for k, v in __import__("os").environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--all-ranks-on-device", "0",
-                        "--steps", "5", "--warmup", "2", "--no-extras", "--cpu-seconds", "1.5", "--batch", "32"],
+                        "--steps", "5", "--warmup", "2", "--full", "--no-extras", "--cpu-seconds", "1.5", "--batch", "32"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -252,7 +252,7 @@ def test_bench_two_ranks_under_torchrun_as_the_driver_launches_it():
     env = {k: v for k, v in __import__("os").environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--all-ranks-on-device", "0",
-                        "--steps", "5", "--warmup", "2", "--cpu-seconds", "1.5", "--batch", "16"],
+                        "--steps", "5", "--warmup", "2", "--full", "--cpu-seconds", "1.5", "--batch", "16"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
     out_lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -273,7 +273,7 @@ def test_bench_four_ranks_contract_on_gpu():
     import json
     env = {k: v for k, v in __import__("os").environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "4", "--dist-backend", "gloo", "--all-ranks-on-device", "0",
-                        "--steps", "5", "--warmup", "2", "--cpu-seconds", "1.5", "--batch", "16", "--deadline-s", "600"],
+                        "--steps", "5", "--warmup", "2", "--full", "--cpu-seconds", "1.5", "--batch", "16", "--deadline-s", "600"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -302,6 +302,81 @@ def test_deadlines_fit_inside_the_drivers_limit():
     assert bench.launch_children.__defaults__[-1] == bench.DEADLINE_DEFAULT_S
 
 
+def test_plain_run_options():
+    """A plain run does the headline only: --full (off by default) adds the other legs; --steps is the number of timed steps and must
+    be at least one; --dump-outputs takes a directory."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "some/dir"])
+    assert a.full is True and a.dump_outputs == "some/dir"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dump_outputs_sample_and_histograms(tmp_path, monkeypatch):
+    """bench.dump_outputs on a CPU tensor: float files only, the whole batch when it fits the sample, otherwise one value from each
+    stratum at seeded positions (the same on every call), and every frame's byte histogram; 64 x 4K NV12 frames stay under 64 MB."""
+    import numpy as np
+    import torch
+    import bench
+    fb = 3840 * 2160 * 3 // 2
+    assert 4 * bench.DUMP_SAMPLE + 8 * 256 * 64 < 64e6 and bench.DUMP_SAMPLE < 64 * fb
+    g = torch.Generator().manual_seed(1)
+    out = torch.randint(0, 256, (3, 6000), dtype=torch.uint8, generator=g)
+    flat = out.reshape(-1).numpy()
+    p1 = bench.dump_outputs(out, tmp_path / "a")
+    sample, hist = (np.load(p) for p in p1)
+    assert sample.dtype == np.float32 and hist.dtype == np.float64
+    assert np.array_equal(sample, flat.astype(np.float32))
+    assert hist.shape == (3, 256) and np.array_equal(hist, np.stack([np.bincount(r, minlength=256) for r in out.numpy()]))
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    pa = bench.dump_outputs(out, tmp_path / "b")
+    pb = bench.dump_outputs(out, tmp_path / "c")
+    sa, sb = np.load(pa[0]), np.load(pb[0])
+    assert sa.shape == (1000,) and np.array_equal(sa, sb)
+    stride = flat.size // 1000
+    for k in (0, 499, 999):                                   # value k comes from stratum k
+        assert sa[k] in flat[k * stride:(k + 1) * stride].astype(np.float32)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """`python bench.py --steps K --warmup W` without --full: the headline line with exactly K timed steps and nothing from the other
+    legs; --dump-outputs writes the last step's output as float .npy files under 64 MB, the same in two runs with the same arguments."""
+    import json
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1 and r.stdout.strip() == lines[0].strip(), r.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["metric"] == "frames/sec, 3840x2160 NV12 Y equalizeHist" and line["unit"] == "frames/s" and line["dtype"] == "u8"
+        assert line["higher_is_better"] is True and line["steps"] == 3 and line["warmup"] == 1
+        assert abs(line["value"] - 8 * 3 / (line["ms_per_step"] * 3e-3)) / line["value"] < 0.01
+        assert line["parity_spot_check"] is None and line["nv12_1080p"] is None and line["fused_fallbacks_in_run"] == 0
+        for key in ("cpu_baseline", "extras", "opencv_cross_check", "stream_4k60_512_all_gpus"):
+            assert key not in line, key
+        for phase in ("second_resolution", "extras", "cpu_baseline"):
+            assert f"phase={phase}" not in r.stderr, phase
+        files = sorted(d.iterdir())
+        assert [f.name for f in files] == ["frames_out_hist.npy", "frames_out_sample.npy"]
+        assert sum(f.stat().st_size for f in files) <= 64e6
+        arrs = {f.name: np.load(f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        hist = arrs["frames_out_hist.npy"]
+        assert hist.shape == (8, 256) and (hist.sum(axis=1) == 3840 * 2160 * 3 // 2).all()
+        assert (hist[:, 128] >= 3840 * 2160 // 2).all()                   # UV = 128 (the default --uv fill128)
+        dumps.append(arrs)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+
+
 @pytest.mark.gpu
 def test_bench_nccl_world1_contract_on_gpu():
     """The RCCL branch on ONE GPU: `--force-dist` brings up a one-rank process group on the real backend, so init_process_group("nccl",
@@ -311,7 +386,7 @@ def test_bench_nccl_world1_contract_on_gpu():
     import json
     env = {k: v for k, v in __import__("os").environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     common = ["--steps", "20", "--warmup", "5", "--cpu-seconds", "1.5"]
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--force-dist"] + common, capture_output=True, text=True, timeout=900, env=env)
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--force-dist", "--full"] + common, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -336,7 +411,7 @@ def test_bench_line_contract_on_gpu():
     """`python bench.py` prints ONE JSON line with the fields the driver reads, the roofline and cpu_baseline objects, and the
     truthfulness fields of round 2 (traffic source, moved-bytes fraction, backend, fallbacks)."""
     import json
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "5", "--warmup", "2", "--no-extras", "--cpu-seconds", "1.5"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "5", "--warmup", "2", "--full", "--no-extras", "--cpu-seconds", "1.5"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

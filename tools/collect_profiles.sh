@@ -19,7 +19,7 @@ if [ "$OP" = clahe16 ]; then
     rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT/pmc_$c" -- "${PROG[@]}" > /dev/null 2> "$OUT/pmc_$c.err"
   done
 else
-  python3 bench.py --op "$OP" > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
+  python3 bench.py --op "$OP" --full > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 bench.py --op "$OP" --steps 50 --warmup 5 --no-cpu-baseline --no-extras --no-second-resolution > "$OUT/bench_stats.json" 2> "$OUT/stats.err"
   for c in FETCH_SIZE WRITE_SIZE; do
     rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT/pmc_$c" -- python3 bench.py --op "$OP" --steps 5 --warmup 2 --no-cpu-baseline --no-extras --no-second-resolution > /dev/null 2> "$OUT/pmc_$c.err"
