@@ -38,7 +38,7 @@ extern "C" {
 #endif
 
 #define MI_LUMAEQ_VERSION_MAJOR 0
-#define MI_LUMAEQ_VERSION_MINOR 2
+#define MI_LUMAEQ_VERSION_MINOR 3
 
 typedef enum mi_status {
     MI_OK = 0,
@@ -54,7 +54,10 @@ typedef enum mi_status {
 /* UV handling of whole-NV12-frame entry points:
  *   MI_UV_FILL128 : memset(out + W*H, 128, W*H/2)      OpenCVequalHist.cpp:160-162, clahevideo.cpp:200-201
  *   MI_UV_COPY    : memcpy(out + W*H, in + W*H, W*H/2) ColoropenCVCwqualHist.cpp:165, improvement.cpp:163,
- *                                                      nextimprovement.cpp:160 */
+ *                                                      nextimprovement.cpp:160
+ * On P010 / P012 / P016 frames (MI_FMT_P010, mi_clahe_p010*) the same two modes act on 16-bit samples: MI_UV_FILL128 sets every
+ * chroma sample to 0x8000 -- 128 in the high byte, the neutral value of all three formats -- and MI_UV_COPY copies the chroma half
+ * (W*H bytes) byte for byte. */
 typedef enum mi_uv_mode { MI_UV_FILL128 = 0, MI_UV_COPY = 1 } mi_uv_mode;
 
 typedef struct mi_ctx mi_ctx;    /* opaque: device id, streams, pinned staging, device scratch */
@@ -208,6 +211,26 @@ mi_status mi_clahe_u16_batch_dev(mi_ctx* ctx, const void* d_src, size_t src_step
                                  int width, int height, int n_frames,
                                  double clip_limit, int tiles_x, int tiles_y, void* stream);
 
+/* ---- CLAHE on 16-bit 4:2:0 video frames: P010, P012, P016 (what an HEVC Main10 / HDR decoder hands over) -------------------
+ * A frame is W x H little-endian uint16 luma samples followed by H/2 rows of W interleaved uint16 U, V samples: 3*W*H bytes,
+ * tightly packed, W and H even.  The layout is the same for P010, P012 and P016 and the operation never looks at the bit depth.
+ *   luma   : cv::createCLAHE(clip, Size(tiles_x, tiles_y))->apply(y, y) on the CV_16UC1 view of the Y plane (row pitch 2*W),
+ *            i.e. exactly what mi_clahe_u16* computes on that plane.  Output samples are NOT re-quantised to multiples of 64
+ *            (or 16): OpenCV returns full 16-bit values for that view, and so does this.
+ *   chroma : MI_UV_FILL128 = every sample 0x8000; MI_UV_COPY = copied byte for byte (in place: nothing moves).
+ * equalizeHist has no 16-bit form in OpenCV (it asserts CV_8UC1): P010 offers CLAHE only.
+ * Errors: odd W or H, a null pointer, a pointer that is not 2-byte aligned, tiles <= 0: MI_ERR_BAD_ARG; width, height or n_frames
+ * of 0: MI_OK, nothing done; W*H beyond what mi_clahe_u16 accepts: MI_ERR_UNSUPPORTED.
+ * mi_clahe_p010: host frames, synchronous, in == out allowed.  Only the Y plane crosses PCIe (directly when the frame is pinned,
+ *   see mi_host_register); the chroma half is written on the host while the GPU works on Y.
+ * mi_clahe_p010_batch_dev: n_frames frames at a frame pitch of 3*W*H bytes, stream-ordered like the other batched device forms;
+ *   d_in == d_out allowed; capturable into a hipGraph after one eager call of the same shape. */
+enum { MI_FMT_NV12 = 0, MI_FMT_P010 = 1 };   /* P010 = any 16-bit LE 4:2:0 semi-planar frame: P010 / P012 / P016 */
+mi_status mi_clahe_p010(mi_ctx* ctx, const uint16_t* in, uint16_t* out, int width, int height,
+                        mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
+mi_status mi_clahe_p010_batch_dev(mi_ctx* ctx, const void* d_in, void* d_out, int width, int height, int n_frames,
+                                  mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y, void* stream);
+
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at
  * OpenCVequalHist.cpp:115/:158).  Registering a pool's memory once lets the host-pointer forms DMA straight
@@ -264,7 +287,11 @@ mi_status mi_host_unregister(void* ptr);
  * (its result sits in staging that is freed).  Ownership follows the reference's rule for a buffer that was pushed and then dropped
  * (OpenCVequalHist.cpp:183-187: ownership passes on push, a failed push is unref'd, never read): discard such outputs.  A caller
  * that wants every frame calls mi_pipe_wait until mi_pipe_pending() is 0 before destroying the pipe; micv::FramePool::finish()
- * and nv12_stream do exactly that and never rely on destroy to complete a frame. */
+ * and nv12_stream do exactly that and never rely on destroy to complete a frame.
+ *   format     MI_FMT_NV12 (0, the default of a zeroed config) or MI_FMT_P010 (16-bit frames of 3*W*H bytes, see mi_clahe_p010;
+ *              in / out are then those frames' bytes).  P010 takes MI_OP_CLAHE only -- the other ops answer MI_ERR_UNSUPPORTED at
+ *              mi_pipe_create -- and runs it through the 16-bit path; under MI_PIPE_UV_HOST only Y crosses and the waiting thread
+ *              writes the chroma, under MI_PIPE_UV_DEVICE whole frames cross and a kernel writes it.  Default depth by frame bytes. */
 typedef struct mi_pipe mi_pipe;
 enum { MI_OP_EQUALIZE = 0, MI_OP_CLAHE = 1, MI_OP_CHANNELS = 2 };
 enum { MI_PIPE_UV_AUTO = 0, MI_PIPE_UV_HOST = 1, MI_PIPE_UV_DEVICE = 2 };
@@ -276,6 +303,7 @@ typedef struct mi_pipe_config {
     int tiles_x, tiles_y;        /* MI_OP_CLAHE */
     int depth;
     int uv_policy;
+    int format;                  /* MI_FMT_NV12 | MI_FMT_P010 (appended in 0.3: keep it the last member) */
 } mi_pipe_config;
 mi_status mi_pipe_create(mi_ctx* ctx, const mi_pipe_config* cfg, mi_pipe** out);
 void      mi_pipe_destroy(mi_pipe* pipe);

@@ -7,9 +7,9 @@
 extern "C" {
 
 #ifdef MI_TEST_HOOKS
-const char* mi_version(void) { return "mi_lumaeq 0.2 (gfx950) +test-hooks"; }
+const char* mi_version(void) { return "mi_lumaeq 0.3 (gfx950) +test-hooks"; }
 #else
-const char* mi_version(void) { return "mi_lumaeq 0.2 (gfx950)"; }
+const char* mi_version(void) { return "mi_lumaeq 0.3 (gfx950)"; }
 #endif
 
 const char* mi_status_str(mi_status s)

@@ -28,6 +28,8 @@
 // a 4K plane's transfer time; with the next frame's copy already running on the other stream the link never waits for it.
 // UV handling: "host" (default for Y-only ops) moves only the Y plane over the bus and fills / copies the UV half on the
 // host inside mi_pipe_wait while the engines are busy; "device" ships whole NV12 frames and lets the kernels do it.
+// Format: NV12 (8-bit) or P010 (16-bit samples, any of P010 / P012 / P016: the same layout with every size doubled; CLAHE only,
+// through the 16-bit path, and the chroma half is 0x8000-filled / copied by mi_host::p010_chroma or p010_uv_kernel).
 
 struct PipeSlot {
     int lane = 0;                                                 // which of the two copy streams per direction carries this frame
@@ -86,6 +88,12 @@ mi_status pipe_run_op(mi_pipe* p, PipeSlot& sl)
     const mi_pipe_config& g = p->cfg;
     const size_t fstride = p->ybytes + p->uvbytes;
     if (g.op == MI_OP_CHANNELS) return nv12_bgr_equalize_dev(c, p->s_k, sl.d_in, fstride, sl.d_out, fstride, g.width, g.height, 1);
+    if (g.format == MI_FMT_P010) {                                // 16-bit frames: CLAHE on the 2W-pitch Y plane, the chroma kernel when asked
+        mi_status st = clahe16_dev(c, p->s_k, sl.d_in, (size_t)g.width * 2, fstride, sl.d_out, (size_t)g.width * 2, fstride, g.width, g.height, 1,
+                                   g.clip_limit, g.tiles_x, g.tiles_y);
+        if (st || !p->uv_dev) return st;
+        return p010_uv_dev(c, p->s_k, sl.d_in, sl.d_out, g.width, g.height, 1, g.uv_mode);
+    }
     PlaneArgs a{sl.d_in, (size_t)g.width, fstride, sl.d_out, (size_t)g.width, fstride, g.width, g.height, 1};
     UVJob uv{};
     const UVJob* puv = nullptr;
@@ -155,9 +163,12 @@ mi_status mi_pipe_create(mi_ctx* c, const mi_pipe_config* cfg, mi_pipe** out)
     if (!cfg || !out) return fail(c, MI_ERR_BAD_ARG, "null config / out");
     *out = nullptr;
     if (cfg->width <= 0 || cfg->height <= 0) return fail(c, MI_ERR_BAD_ARG, "pipe needs a positive frame size");
-    if ((cfg->width & 1) || (cfg->height & 1)) return fail(c, MI_ERR_BAD_ARG, "NV12 frames have even width and height");
+    if ((cfg->width & 1) || (cfg->height & 1)) return fail(c, MI_ERR_BAD_ARG, "NV12 / P010 frames have even width and height");
+    if (cfg->format != MI_FMT_NV12 && cfg->format != MI_FMT_P010) return fail(c, MI_ERR_BAD_ARG, "bad format");
     if ((long long)cfg->width * cfg->height > 0x7fffffffLL / 3) return fail(c, MI_ERR_UNSUPPORTED, "frame too large");
     if (cfg->op != MI_OP_EQUALIZE && cfg->op != MI_OP_CLAHE && cfg->op != MI_OP_CHANNELS) return fail(c, MI_ERR_BAD_ARG, "bad op");
+    // equalizeHist has no 16-bit form in OpenCV (it asserts CV_8UC1): P010 frames take CLAHE only
+    if (cfg->format == MI_FMT_P010 && cfg->op != MI_OP_CLAHE) return fail(c, MI_ERR_UNSUPPORTED, "P010 frames: MI_OP_CLAHE only");
     if (cfg->uv_mode != MI_UV_FILL128 && cfg->uv_mode != MI_UV_COPY) return fail(c, MI_ERR_BAD_ARG, "bad uv_mode");
     if (cfg->op == MI_OP_CLAHE && (cfg->tiles_x <= 0 || cfg->tiles_y <= 0)) return fail(c, MI_ERR_BAD_ARG, "tile grid must be >= 1x1");
     if (cfg->uv_policy < MI_PIPE_UV_AUTO || cfg->uv_policy > MI_PIPE_UV_DEVICE) return fail(c, MI_ERR_BAD_ARG, "bad uv_policy");
@@ -165,7 +176,8 @@ mi_status mi_pipe_create(mi_ctx* c, const mi_pipe_config* cfg, mi_pipe** out)
     mi_pipe* p = new (std::nothrow) mi_pipe();
     if (!p) return fail(c, MI_ERR_OOM, "pipe allocation failed");
     p->c = c; p->cfg = *cfg;
-    p->ybytes = (size_t)cfg->width * cfg->height; p->uvbytes = p->ybytes / 2;
+    // NV12: W*H luma bytes + W*H/2 chroma bytes; P010: twice both (16-bit samples)
+    p->ybytes = (size_t)cfg->width * cfg->height * (cfg->format == MI_FMT_P010 ? 2 : 1); p->uvbytes = p->ybytes / 2;
     // Default depth by frame size (profiles/r04_t_*, r04_u_*): one thread that submits and waits on 4K frames is fastest with THREE in
     // flight (5.44-5.59 k frames/s; four: 4.74-4.81 k, two: 3.8-4.3 k -- a fourth frame only deepens the copy lanes' queues), while
     // 1080p frames, bound by their per-frame launch sequence, want more (six: 17.2 k, four: 15.8 k, three: 13.0 k through the pool)
@@ -370,7 +382,9 @@ mi_status mi_pipe_wait(mi_pipe* p, uint64_t* tag, uint8_t** out_frame)
     if (tag) *tag = sl.tag;
     if (out_frame) *out_frame = sl.out;
     // the host's share of the frame first: it overlaps whatever the copy engines are still doing
-    if (!p->uv_dev) {
+    if (!p->uv_dev && p->cfg.format == MI_FMT_P010) {
+        mi_host::p010_chroma(sl.out + p->ybytes, sl.in + p->ybytes, p->uvbytes, p->cfg.uv_mode == MI_UV_COPY ? 1 : 0);
+    } else if (!p->uv_dev) {
         if (p->cfg.uv_mode == MI_UV_FILL128) memset(sl.out + p->ybytes, 128, p->uvbytes);
         else if (sl.out != sl.in) memmove(sl.out + p->ybytes, sl.in + p->ybytes, p->uvbytes);
     }

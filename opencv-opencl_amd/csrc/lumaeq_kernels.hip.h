@@ -29,6 +29,7 @@
 //   kernels/color.hip.h           cvtColor BGR2YUV / YUV2BGR + fused split/merge, 4:2:0 codes, NV12 per-channel equalize (N3)
 //   kernels/color_clahe.hip.h     CLAHE on the luma of interleaved BGR in two passes (N3)
 //   kernels/diff.hip.h            absdiff + analyzeDiff: the reference's own device-vs-CPU check (1frameMeasure.cpp:91-100)
+//   kernels/p010.hip.h            chroma half of 16-bit 4:2:0 frames (P010 / P012 / P016): copy or fill 0x8000
 #pragma once
 #include "kernels/common.hip.h"
 #include "kernels/equalize.hip.h"
@@ -38,3 +39,4 @@
 #include "kernels/color.hip.h"
 #include "kernels/color_clahe.hip.h"
 #include "kernels/diff.hip.h"
+#include "kernels/p010.hip.h"

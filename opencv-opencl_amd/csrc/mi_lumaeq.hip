@@ -27,6 +27,7 @@
 #include "host/pin_registry.hpp"
 #include "host/numa_affinity.hpp"
 #include "host/wide_hint.hpp"
+#include "host/p010_chroma.hpp"
 
 using namespace mi;
 
@@ -39,5 +40,6 @@ using namespace mi;
 #include "host/capi.inc.hpp"
 #include "host/color.inc.hpp"
 #include "host/clahe16.inc.hpp"
+#include "host/p010.inc.hpp"            // 16-bit 4:2:0 frames: CLAHE on Y (clahe16) + the chroma kernel
 #include "host/pipe.inc.hpp"
 #include "host/diff.inc.hpp"

@@ -14,7 +14,9 @@
 // once, the way a GstBufferPool's memory would be), --loop (rewind --input at its end: clahevideo.cpp:294-302), --dump-every K
 // (write only every K-th delivered frame to --output), --no-numa-bind (do not bind each worker to the CPUs of its GPU's NUMA node;
 // the binding is printed in the banner), --max-workers-per-gpu K (default 2; 0 = no cap).  --workers may exceed the GPU count
-// (worker w -> GPU w mod N), up to 64; at most K of them are started per GPU.
+// (worker w -> GPU w mod N), up to 64; at most K of them are started per GPU.  --format nv12|p010: p010 streams 16-bit 4:2:0 frames
+// (P010 / P012 / P016 layout, 3*W*H bytes each; --input / --output are raw P010 files) through CLAHE on the 16-bit path -- only
+// --op clahe (equalizeHist has no 16-bit form in OpenCV); the synthetic source then makes 10-bit samples << 6.
 #include <sched.h>
 #include <sys/resource.h>
 
@@ -44,7 +46,7 @@ int main(int argc, char** argv)
     double clip = 2.0;
     bool paced = false, pin = true, loop = false, numa_bind = true;
     int dump_every = 1;
-    std::string op = "equalize", uv = "fill128", uv_policy = "host", input, output, v;
+    std::string op = "equalize", uv = "fill128", uv_policy = "host", format = "nv12", input, output, v;
     for (int i = 1; i < argc; ++i) {
         if (kv(argv[i], "workers", v, i, argc, argv)) workers = std::max(1, std::min(64, atoi(v.c_str())));    // reference: 1..8 (OpenCVequalHist.cpp:274)
         else if (kv(argv[i], "width", v, i, argc, argv)) width = atoi(v.c_str());
@@ -60,6 +62,7 @@ int main(int argc, char** argv)
         else if (strcmp(argv[i], "--paced") == 0) paced = true;
         else if (kv(argv[i], "depth", v, i, argc, argv)) depth = atoi(v.c_str());
         else if (kv(argv[i], "uv-policy", v, i, argc, argv)) uv_policy = v;
+        else if (kv(argv[i], "format", v, i, argc, argv)) format = v;
         else if (strcmp(argv[i], "--pin") == 0) pin = true;          // (default) register the frame ring like a pinned GstBufferPool
         else if (strcmp(argv[i], "--no-pin") == 0) pin = false;
         else if (strcmp(argv[i], "--loop") == 0) loop = true;
@@ -69,7 +72,10 @@ int main(int argc, char** argv)
         else fprintf(stderr, "Warning: ignoring unknown arg: %s\n", argv[i]);
     }
     if (width <= 0 || height <= 0 || frames <= 0) { fprintf(stderr, "bad size\n"); return 1; }
-    const size_t fb = (size_t)width * height + (size_t)width * height / 2;
+    if (format != "nv12" && format != "p010") { fprintf(stderr, "--format must be nv12 or p010\n"); return 1; }
+    const bool p010 = format == "p010";
+    if (p010 && op != "clahe") { fprintf(stderr, "--format p010 supports --op clahe only (equalizeHist has no 16-bit form)\n"); return 1; }
+    const size_t fb = FramePool::frame_bytes(width, height, p010 ? MI_FMT_P010 : MI_FMT_NV12);
     if (depth <= 0) depth = fb >= ((size_t)8 << 20) ? 4 : 6;      // a pool worker (fed by the submitting thread): four 4K frames in flight, six of 1080p or less (profiles/r04_t_*)
     const int ring = 32;                                            // frames in flight (input + output ring)
     // every worker on one GPU (one worker, or a one-GPU process -- how bench.py runs one streamer per GPU): the submitting thread
@@ -108,7 +114,15 @@ int main(int argc, char** argv)
         for (size_t i = 0; i < fb; i += 8) {
             s += 0x9E3779B97F4A7C15ull; uint64_t z = s;
             z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; z ^= z >> 31;
-            for (int b = 0; b < 8 && i + b < fb; ++b) f[i + b] = (unsigned char)(64 + ((z >> (8 * b)) & 0x7f));
+            if (p010) {                                                               // four 10-bit samples << 6 per hash
+                for (int b = 0; b < 8 && i + b < fb; b += 2) {
+                    const uint16_t q = (uint16_t)(((z >> (8 * b)) & 0x3ff) << 6);
+                    f[i + b] = (unsigned char)(q & 0xff);
+                    if (i + b + 1 < fb) f[i + b + 1] = (unsigned char)(q >> 8);
+                }
+            } else {
+                for (int b = 0; b < 8 && i + b < fb; ++b) f[i + b] = (unsigned char)(64 + ((z >> (8 * b)) & 0x7f));
+            }
         }
     };
     std::vector<std::chrono::steady_clock::time_point> t_submit((size_t)frames);
@@ -126,9 +140,9 @@ int main(int argc, char** argv)
                            delivered.fetch_add(1);
                        },
                        clip, Size(tile, tile), ring / (size_t)workers > 2 ? ring / (size_t)workers - 1 : 1, depth,
-                       uv_policy == "device" ? MI_PIPE_UV_DEVICE : MI_PIPE_UV_HOST, numa_bind, per_gpu);
-        printf("nv12_stream: %dx%d %s uv=%s (uv-policy %s) workers=%d depth=%d gpus=%d frames=%d%s%s\n", width, height, op.c_str(), uv.c_str(),
-               uv_policy.c_str(), pool.workers(), depth, getDeviceCount(), frames, paced ? " paced" : "", pin ? " pinned-ring" : " pageable-ring");
+                       uv_policy == "device" ? MI_PIPE_UV_DEVICE : MI_PIPE_UV_HOST, numa_bind, per_gpu, p010 ? MI_FMT_P010 : MI_FMT_NV12);
+        printf("nv12_stream: %dx%d %s uv=%s (uv-policy %s) workers=%d depth=%d gpus=%d frames=%d%s%s%s\n", width, height, op.c_str(), uv.c_str(),
+               uv_policy.c_str(), pool.workers(), depth, getDeviceCount(), frames, paced ? " paced" : "", pin ? " pinned-ring" : " pageable-ring", p010 ? " format=p010" : "");
         if (pool.workers() != pool.requested())
             printf("workers: %d requested, %d started (at most %d per GPU: one keeps the link busy, more never help)\n", pool.requested(), pool.workers(), per_gpu);
         printf("placement: %s\n", main_placement.c_str());
@@ -173,8 +187,8 @@ int main(int argc, char** argv)
         pool.finish();
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         const auto cpu1 = cpu_seconds();
-        printf("done: %llu frames in %.3f s = %.1f frames/s (host NV12 in -> host NV12 out, PCIe inclusive), errors=%llu\n",
-               (unsigned long long)pool.stats().frames_out.load(), el, pool.stats().frames_out.load() / el,
+        printf("done: %llu frames in %.3f s = %.1f frames/s (host %s in -> host %s out, PCIe inclusive), errors=%llu\n",
+               (unsigned long long)pool.stats().frames_out.load(), el, pool.stats().frames_out.load() / el, p010 ? "P010" : "NV12", p010 ? "P010" : "NV12",
                (unsigned long long)pool.stats().processing_errors.load());
         {
             const double n = (double)std::max<uint64_t>(1, pool.stats().frames_out.load());

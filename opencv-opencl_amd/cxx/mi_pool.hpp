@@ -43,7 +43,7 @@ struct PoolStats {                       // the counters of OpenCVequalHist.cpp:
 
 struct FrameJob {
     uint64_t index = 0;                  // assigned by submit(), strictly increasing
-    const unsigned char* in = nullptr;   // tightly packed NV12, W*H*3/2 bytes, caller-owned until delivered
+    const unsigned char* in = nullptr;   // tightly packed NV12 (W*H*3/2 bytes) or P010 (3*W*H bytes), caller-owned until delivered
     unsigned char* out = nullptr;        // caller-owned output frame (may equal `in`)
     bool ok = false;
     std::string error;
@@ -54,15 +54,15 @@ public:
     enum Op { EQUALIZE, CLAHE_OP, CHANNELS_EQ };   // CHANNELS_EQ: NV12 -> BGR -> equalizeHist on B, G, R -> NV12 (BASELINE config 5 read literally; ignores uv)
     using Sink = std::function<void(const FrameJob&)>;   // called in frame order, from a pool thread
 
-    // depth: frames a worker keeps in flight on its GPU (2..16; 0 = by frame size: 4 at 4K, 6 at 1080p and below);
-    // uv_policy: MI_PIPE_UV_AUTO / _HOST / _DEVICE (mi_lumaeq.h)
+    // depth: frames a worker keeps in flight on its GPU (2..16; 0 = by frame bytes: 4 for 8 MiB and more (4K NV12, 1080p P010 and up), 6 below);
+    // uv_policy: MI_PIPE_UV_AUTO / _HOST / _DEVICE (mi_lumaeq.h); format: MI_FMT_NV12 or MI_FMT_P010 (16-bit frames, CLAHE_OP only)
     FramePool(int workers, int width, int height, Op op, UVMode uv, Sink sink,
               double clip = 2.0, Size tiles = Size(8, 8), size_t max_queue = 16, int depth = 0, int uv_policy = MI_PIPE_UV_AUTO,
-              bool numa_bind = true, int max_workers_per_gpu = 2)
+              bool numa_bind = true, int max_workers_per_gpu = 2, int format = MI_FMT_NV12)
         : width_(width), height_(height), op_(op), uv_(uv), clip_(clip), tiles_(tiles), sink_(std::move(sink)), max_queue_(max_queue),
-          depth_(depth <= 0 ? ((size_t)width * height * 3 / 2 >= ((size_t)8 << 20) ? 4 : 6)      // a worker fed by the submitting thread: four 4K
+          depth_(depth <= 0 ? (frame_bytes(width, height, format) >= ((size_t)8 << 20) ? 4 : 6)   // a worker fed by the submitting thread: four 4K
                             : (depth < 2 ? 2 : (depth > 16 ? 16 : depth))),                      // frames, six of 1080p and below (docs/experiments.md R4.9)
-          uv_policy_(uv_policy), numa_bind_(numa_bind)
+          uv_policy_(uv_policy), format_(format), numa_bind_(numa_bind)
     {
         if (workers < 1) workers = 1;
         if (workers > 64) workers = 64;
@@ -93,6 +93,11 @@ public:
         return (max_workers_per_gpu >= 1 && requested > ndev * max_workers_per_gpu) ? ndev * max_workers_per_gpu : requested;
     }
     static int device_of_worker(int worker, int ndev) { return worker % ndev; }
+    // bytes of one frame: NV12 W*H*3/2, P010 (16-bit samples) 3*W*H
+    static size_t frame_bytes(int width, int height, int format)
+    {
+        return (size_t)width * height * 3 / 2 * (format == MI_FMT_P010 ? 2 : 1);
+    }
     static int device_of_frame(uint64_t frame, int workers, int ndev) { return device_of_worker((int)(frame % (uint64_t)workers), ndev); }
 
     int workers() const { return (int)threads_.size(); }        // workers actually started (<= max_workers_per_gpu per GPU)
@@ -159,7 +164,7 @@ private:
             cfg.width = width_; cfg.height = height_;
             cfg.op = op_ == EQUALIZE ? MI_OP_EQUALIZE : (op_ == CLAHE_OP ? MI_OP_CLAHE : MI_OP_CHANNELS);
             cfg.uv_mode = (mi_uv_mode)uv_; cfg.clip_limit = clip_; cfg.tiles_x = tiles_.width; cfg.tiles_y = tiles_.height;
-            cfg.depth = depth_; cfg.uv_policy = uv_policy_;
+            cfg.depth = depth_; cfg.uv_policy = uv_policy_; cfg.format = format_;
             detail::check(c, mi_pipe_create(c, &cfg, &pipe), "mi_pipe_create");
         } catch (const std::exception& e) {
             pipe_error = e.what();                              // reported per frame; the pool still comes up so submit()/finish() do not hang
@@ -247,7 +252,7 @@ private:
     Size tiles_;
     Sink sink_;
     size_t max_queue_;
-    int depth_, uv_policy_;
+    int depth_, uv_policy_, format_;
     bool numa_bind_;
     int requested_ = 0;
     std::vector<std::string> placement_;

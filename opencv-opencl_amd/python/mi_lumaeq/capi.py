@@ -23,6 +23,7 @@ COLOR_BGR2YUV, COLOR_YUV2BGR = 82, 84
 COLOR_YUV2BGR_NV12, COLOR_BGR2YUV_I420 = 93, 128
 OP_EQUALIZE, OP_CLAHE, OP_CHANNELS = 0, 1, 2
 PIPE_UV_AUTO, PIPE_UV_HOST, PIPE_UV_DEVICE = 0, 1, 2
+FMT_NV12, FMT_P010 = 0, 1              # MI_FMT_*: P010 = any 16-bit LE 4:2:0 semi-planar frame (P010 / P012 / P016)
 ERR_BUSY = 6
 
 # every extern "C" symbol include/mi_lumaeq.h declares (tests check the .so exports them all)
@@ -42,6 +43,7 @@ DECLARED_SYMBOLS = [
     "mi_nv12_bgr_equalize", "mi_nv12_bgr_equalize_batch_dev", "mi_cvt_color_420_u8", "mi_cvt_color_420_u8_batch_dev",
     "mi_analyze_diff_u8", "mi_analyze_diff_u8_batch_dev",
     "mi_device_pci_bus_id", "mi_thread_bind_near_device",
+    "mi_clahe_p010", "mi_clahe_p010_batch_dev",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -58,7 +60,7 @@ class _NumaBinding(C.Structure):
 
 class _PipeConfig(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("op", C.c_int), ("uv_mode", C.c_int), ("clip_limit", C.c_double),
-                ("tiles_x", C.c_int), ("tiles_y", C.c_int), ("depth", C.c_int), ("uv_policy", C.c_int)]
+                ("tiles_x", C.c_int), ("tiles_y", C.c_int), ("depth", C.c_int), ("uv_policy", C.c_int), ("format", C.c_int)]
 
 
 class MiError(RuntimeError):
@@ -137,6 +139,8 @@ def _load(p: Path) -> C.CDLL:
     L.mi_nv12_bgr_equalize_batch_dev.argtypes = [vp, vp, sz, vp, sz, i, i, i, vp]
     L.mi_clahe_u16.argtypes = [vp, vp, sz, vp, sz, i, i, d, i, i]
     L.mi_clahe_u16_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, d, i, i, vp]
+    L.mi_clahe_p010.argtypes = [vp, vp, vp, i, i, i, d, i, i]
+    L.mi_clahe_p010_batch_dev.argtypes = [vp, vp, vp, i, i, i, i, d, i, i, vp]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -429,6 +433,30 @@ class Context:
                                                width * 2 * height, width, height, n_frames, float(clip_limit), tiles_x, tiles_y, stream),
                   "mi_clahe_u16_batch_dev")
 
+    # ---- 16-bit 4:2:0 frames: P010 / P012 / P016 ----
+    def clahe_p010(self, frame: np.ndarray, width: int, height: int, uv_mode: int = UV_FILL128, clip_limit: float = 2.0,
+                   tiles_x: int = 8, tiles_y: int = 8, out: np.ndarray | None = None) -> np.ndarray:
+        """mi_clahe_p010 on a host frame: a contiguous uint16 array of 3*W*H/2 samples (e.g. shape (3H/2, W)).  `out` may be
+        `frame` (in place); otherwise a new array of the frame's shape is returned."""
+        if not isinstance(frame, np.ndarray) or frame.dtype != np.uint16 or not frame.flags.c_contiguous:
+            raise MiError(2, "clahe_p010", "expected a contiguous uint16 ndarray (P010 frame)")
+        if width >= 0 and height >= 0 and frame.size < width * height * 3 // 2:
+            raise MiError(1, "clahe_p010", "frame smaller than W*H*3/2 samples")
+        if out is None:
+            out = np.empty_like(frame)
+        elif out.dtype != np.uint16 or not out.flags.c_contiguous or out.size < frame.size:
+            raise MiError(1, "clahe_p010", "out must be a contiguous uint16 array as large as the frame")
+        self._chk(self._L.mi_clahe_p010(self._h, frame.ctypes.data, out.ctypes.data, int(width), int(height), int(uv_mode),
+                                      float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_p010")
+        return out
+
+    def clahe_p010_batch_dev(self, d_in, d_out, width, height, n_frames, uv_mode=UV_FILL128, clip_limit=2.0, tiles_x=8, tiles_y=8,
+                             stream=0):
+        """mi_clahe_p010_batch_dev: n_frames P010 frames at a pitch of 3*W*H bytes (device memory; d_in may be d_out)."""
+        self._chk(self._L.mi_clahe_p010_batch_dev(self._h, _dptr(d_in), _dptr(d_out), int(width), int(height), int(n_frames),
+                                                int(uv_mode), float(clip_limit), int(tiles_x), int(tiles_y), stream),
+                  "mi_clahe_p010_batch_dev")
+
     # ---- colour-domain neighbours (N3) ----
     @staticmethod
     def _host3(a, name):
@@ -538,17 +566,22 @@ class Context:
 
 
 class Pipe:
-    """mi_pipe wrapper: asynchronous in-order NV12 frame pipeline on one context (frames are numpy uint8 arrays of W*H*3/2 bytes).
+    """mi_pipe wrapper: asynchronous in-order frame pipeline on one context.  NV12 (format=FMT_NV12): numpy uint8 arrays of W*H*3/2
+    bytes; P010 (format=FMT_P010, op=OP_CLAHE): contiguous uint16 arrays of W*H*3/2 samples, e.g. shape (3H/2, W).
     The arrays handed to submit() are kept alive until wait() returns them."""
 
     def __init__(self, ctx: Context, width: int, height: int, op: int = OP_EQUALIZE, uv_mode: int = UV_FILL128,
-                 clip_limit: float = 2.0, tiles_x: int = 8, tiles_y: int = 8, depth: int = 0, uv_policy: int = PIPE_UV_AUTO):
+                 clip_limit: float = 2.0, tiles_x: int = 8, tiles_y: int = 8, depth: int = 0, uv_policy: int = PIPE_UV_AUTO,
+                 format: int = FMT_NV12):
         self._ctx = ctx
         self._h = C.c_void_p()
         self._held = {}
-        cfg = _PipeConfig(int(width), int(height), int(op), int(uv_mode), float(clip_limit), int(tiles_x), int(tiles_y), int(depth), int(uv_policy))
+        cfg = _PipeConfig(int(width), int(height), int(op), int(uv_mode), float(clip_limit), int(tiles_x), int(tiles_y), int(depth), int(uv_policy),
+                          int(format))
         ctx._chk(self._ctx._L.mi_pipe_create(ctx._h, C.byref(cfg), C.byref(self._h)), "mi_pipe_create")
-        self.frame_bytes = width * height * 3 // 2
+        self.format = int(format)
+        self._dtype = np.uint16 if self.format == FMT_P010 else np.uint8
+        self.frame_bytes = width * height * 3 // 2 * np.dtype(self._dtype).itemsize
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -573,8 +606,8 @@ class Pipe:
     def submit(self, frame_in: np.ndarray, frame_out: np.ndarray, tag: int) -> bool:
         """False when the pipe is full (MI_ERR_BUSY: call wait() first)."""
         for a in (frame_in, frame_out):
-            if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or not a.flags.c_contiguous or a.size < self.frame_bytes:
-                raise MiError(1, "mi_pipe_submit", "frames must be contiguous uint8 arrays of W*H*3/2 bytes")
+            if not isinstance(a, np.ndarray) or a.dtype != self._dtype or not a.flags.c_contiguous or a.nbytes < self.frame_bytes:
+                raise MiError(1, "mi_pipe_submit", "frames must be contiguous uint8 (NV12) / uint16 (P010) arrays of W*H*3/2 samples")
         rc = self._ctx._L.mi_pipe_submit(self._h, frame_in.ctypes.data, frame_out.ctypes.data, int(tag))
         if rc == ERR_BUSY:
             return False

@@ -3,7 +3,7 @@
 Y distributions:  D1 uniform bytes | D2 "natural low-contrast" (gradient + triangular noise,
 clamped to [16,200], ~60 populated bins) | D3 constant 128 | D4 two-valued 16/235 checkerboard |
 D5 full horizontal ramp.  UV plane: uniform bytes from seed ^ 0xA5A5 (so passthrough vs 128-fill
-is checkable).  seed = 0x5EED0000 + frame_index.
+is checkable).  seed = 0x5EED0000 + frame_index.  p010_frame(): the 16-bit 4:2:0 counterpart (P010 / P012 / P016 content).
 """
 from __future__ import annotations
 
@@ -110,6 +110,27 @@ def uv_plane(width: int, height: int, frame_index: int = 0) -> np.ndarray:
 
 def nv12_frame(width: int, height: int, dist: str = "D1", frame_index: int = 0) -> np.ndarray:
     return np.concatenate([y_plane(width, height, dist, frame_index).reshape(-1), uv_plane(width, height, frame_index)])
+
+
+P010_CONTENT = {"p010": (10, 6), "p012": (12, 4), "p016": (16, 0)}      # luma bits, shift into the high bits of the word
+
+
+def random_u16(n: int, seed: int) -> np.ndarray:
+    words = splitmix64(np.arange((n + 3) // 4, dtype=np.uint64), seed)
+    return words.view(np.uint16)[:n].copy()
+
+
+def p010_frame(width: int, height: int, content: str = "p010", frame_index: int = 0) -> np.ndarray:
+    """A seeded 16-bit 4:2:0 semi-planar frame (P010 layout: W x H uint16 luma, then H/2 rows of W interleaved uint16 U, V), shape
+    (3H/2, W).  Luma: uniform samples of the content's bit depth in the HIGH bits of the word, as P010 / P012 store them
+    ("p010": 10 bits << 6, "p012": 12 bits << 4, "p016": full 16-bit).  Chroma: random 10-bit samples << 6.  Same SplitMix64
+    scheme as the NV12 frames (seed = frame_seed(frame_index); chroma from seed ^ 0xA5A5)."""
+    bits, shift = P010_CONTENT[content]
+    seed = frame_seed(frame_index)
+    n = width * height
+    y = random_u16(n, seed ^ 0x0100) >> np.uint16(16 - bits) << np.uint16(shift)
+    uv = random_u16(n // 2, seed ^ 0xA5A5) >> np.uint16(6) << np.uint16(6)
+    return np.concatenate([y, uv]).reshape(height * 3 // 2, width)
 
 
 def nv12_batch(width: int, height: int, n_frames: int, dist: str = "D1", first_index: int = 0) -> np.ndarray:
