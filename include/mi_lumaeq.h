@@ -153,6 +153,37 @@ mi_status mi_clahe_nv12_batch_dev(mi_ctx* ctx, const void* d_in, void* d_out,
                                   int width, int height, int n_frames, mi_uv_mode uv_mode,
                                   double clip_limit, int tiles_x, int tiles_y, void* stream);
 
+/* A LIST of NV12 frames in device memory, each with its own Y and UV plane addresses: decoder surfaces from a pool (each its own
+ * allocation, rows padded to a pitch, the UV plane at pitch * aligned_height), or a list of frame tensors.  `frames` is a host array
+ * of n_frames entries, read only during the call; the pointers in it are device pointers on the context's device.  Every frame of
+ * one call has the same width and height and the same four pitches (bytes between rows; each >= width):
+ *   y_in  : H rows of W bytes at y_in_pitch        y_out  : H rows at y_out_pitch
+ *   uv_in : H/2 rows of W bytes at uv_in_pitch     uv_out : H/2 rows at uv_out_pitch
+ *           (read with MI_UV_COPY only; may be NULL with MI_UV_FILL128)
+ * Plane addresses may have any alignment.  The Y output is byte for byte what the _nv12_batch_dev forms (cv::equalizeHist /
+ * CLAHE::apply) return on the same pixels, the UV output is filled with 128 or copied; nothing outside the W bytes of each output
+ * row is written (not the pitch padding, nor rows between the planes).  A frame may be processed in place (y_out == y_in and
+ * uv_out == uv_in, with equal pitches); in place with MI_UV_COPY leaves the chroma as it is.  Outputs of DIFFERENT frames that
+ * overlap each other give undefined results (not checked).  Stream rules as above; the call returns after enqueueing, and can be
+ * captured into a hipGraph after one eager call of the same shape.  The options clahe_fp_contract and two_kernel_max_frames apply;
+ * these frames never take the fused equalizeHist kernel.
+ * Errors, MI_ERR_BAD_ARG: a null ctx, a null `frames` with n_frames > 0, n_frames < 0, odd W or H, a pitch < W, a null Y plane or
+ * uv_out, a null uv_in with MI_UV_COPY, an output plane that overlaps an input plane of the same frame other than exactly (same
+ * address, same pitch), tiles <= 0, a bad uv_mode.  n_frames, width or height of 0: MI_OK, nothing written.  Nothing is enqueued
+ * unless every frame passes the checks. */
+typedef struct mi_nv12_frame_dev {
+    const void* y_in;
+    const void* uv_in;
+    void*       y_out;
+    void*       uv_out;
+} mi_nv12_frame_dev;
+mi_status mi_equalize_hist_nv12_frames_dev(mi_ctx* ctx, const mi_nv12_frame_dev* frames, int n_frames, int width, int height,
+                                           size_t y_in_pitch, size_t uv_in_pitch, size_t y_out_pitch, size_t uv_out_pitch,
+                                           mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_nv12_frames_dev(mi_ctx* ctx, const mi_nv12_frame_dev* frames, int n_frames, int width, int height,
+                                   size_t y_in_pitch, size_t uv_in_pitch, size_t y_out_pitch, size_t uv_out_pitch,
+                                   mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y, void* stream);
+
 /* ---- stage-level device entry points ---------------------------
  * The same kernels the fused forms launch, exposed one stage at a time so each can be checked
  * against the oracle and timed against its own roofline. */

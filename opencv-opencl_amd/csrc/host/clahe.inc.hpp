@@ -37,7 +37,8 @@ int clahe_auto_tiles_per_wg(const ClaheGeom& g)
     return (long long)g.tile_w * g.tile_h < 3LL * 16 * 512 ? 2 : 1;
 }
 
-mi_status launch_tile_luts(mi_ctx* c, hipStream_t s, const PlaneArgs& a, const ClaheGeom& g, int f0, int nf, uint8_t* d_luts_out)
+mi_status launch_tile_luts(mi_ctx* c, hipStream_t s, const PlaneArgs& a, const ClaheGeom& g, int f0, int nf, uint8_t* d_luts_out,
+                           const FrameList* fl = nullptr)
 {
     const int tiles = g.tiles_x * g.tiles_y;
     // Splits per tile.  Splitting costs a third launch (partials -> tile_lut_kernel) and pays only for LARGE tiles on few frames, and then
@@ -68,12 +69,23 @@ mi_status launch_tile_luts(mi_ctx* c, hipStream_t s, const PlaneArgs& a, const C
         while (K > 1 && (long long)tiles / K * nf < (long long)c->cu_count * 8) K >>= 1;
         if (K > 1 && run % K != 0) K = 1;
     }
+    if (K > 1 && fl) {
+        LAUNCH(c, s, MI_K_TILE_HIST, tile_hist_multi_frames_kernel, dim3(1, tiles / K, nf), dim3(kTileMultiThreads), 0,
+               *fl, (long long)a.src_step, g, direct, tiles, K, xcd_map);
+        return MI_OK;
+    }
     if (K > 1) {
         LAUNCH(c, s, MI_K_TILE_HIST, tile_hist_multi_kernel, dim3(1, tiles / K, nf), dim3(kTileMultiThreads), 0,
                src, (long long)a.src_step, (long long)a.src_frame, g, direct, tiles, K, xcd_map);
         return MI_OK;
     }
-    if (c->clahe_hist_threads == 512)
+    if (fl && c->clahe_hist_threads == 512)
+        LAUNCH(c, s, MI_K_TILE_HIST, tile_hist_frames_kernel<512>, dim3(S, tiles, nf), dim3(512), 0,
+               *fl, (long long)a.src_step, g, c->d_partial, direct, xcd_map);
+    else if (fl)
+        LAUNCH(c, s, MI_K_TILE_HIST, tile_hist_frames_kernel<kThreads>, dim3(S, tiles, nf), dim3(kThreads), 0,
+               *fl, (long long)a.src_step, g, c->d_partial, direct, xcd_map);
+    else if (c->clahe_hist_threads == 512)
         LAUNCH(c, s, MI_K_TILE_HIST, tile_hist_kernel<512>, dim3(S, tiles, nf), dim3(512), 0,
                src, (long long)a.src_step, (long long)a.src_frame, g, c->d_partial, direct, xcd_map);
     else
@@ -86,7 +98,7 @@ mi_status launch_tile_luts(mi_ctx* c, hipStream_t s, const PlaneArgs& a, const C
 }
 
 mi_status launch_interp(mi_ctx* c, hipStream_t s, const PlaneArgs& a, const ClaheGeom& g, int f0, int nf,
-                        const uint8_t* d_luts, const UVJob* uv_all)
+                        const uint8_t* d_luts, const UVJob* uv_all, const FrameList* fl = nullptr)
 {
     PlaneBatch p;
     p.src = a.src + (size_t)f0 * a.src_frame; p.dst = a.dst + (size_t)f0 * a.dst_frame;
@@ -129,15 +141,28 @@ mi_status launch_interp(mi_ctx* c, hipStream_t s, const PlaneArgs& a, const Clah
         if ((npairs <= kMaxPairsLdsF32 || seg_tables) && c->clahe_float_tables) {
             const int cap = seg_tables ? seg_cap : kMaxPairsLdsF32;
             const size_t lds = (size_t)std::min(npairs, cap) * 256 * 4 * sizeof(float);
-            if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp_kernel<true, true>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, uv, cap);
+            if (fl && g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp_frames_kernel<true, true>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
+            else if (fl)          LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp_frames_kernel<true, false>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
+            else if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp_kernel<true, true>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, uv, cap);
             else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp_kernel<true, false>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, uv, cap);
         } else {
             const size_t lds = (size_t)npairs * 256 * sizeof(uint32_t);
-            if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp_kernel<false, true>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, uv, kMaxPairsLds + 1);
+            if (fl && g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp_frames_kernel<false, true>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, kMaxPairsLds + 1);
+            else if (fl)          LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp_frames_kernel<false, false>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, kMaxPairsLds + 1);
+            else if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp_kernel<false, true>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, uv, kMaxPairsLds + 1);
             else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp_kernel<false, false>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, uv, kMaxPairsLds + 1);
         }
     } else {
         if (a.height > kMaxGridY) return fail(c, MI_ERR_UNSUPPORTED, "height > 65535 with tiles_x > 62");
+        if (fl) {
+            LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp_global_frames_kernel,
+                   dim3((a.width + kThreads - 1) / kThreads, a.height, nf), dim3(kThreads), 0, *fl, p, g, d_luts);
+            if (fl->uv.rows > 0) {
+                const int B = blocks_per_frame(c, fl->uv.row_bytes * fl->uv.rows, fl->uv.rows, nf, 2048);
+                LAUNCH(c, s, MI_K_LUT_APPLY, uv_frames_kernel, dim3(B, nf), dim3(kThreads), 0, *fl);
+            }
+            return MI_OK;
+        }
         LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp_global_kernel,
                dim3((a.width + kThreads - 1) / kThreads, a.height, nf), dim3(kThreads), 0, p, g, d_luts);
         if (uv.bytes > 0) {
@@ -148,7 +173,8 @@ mi_status launch_interp(mi_ctx* c, hipStream_t s, const PlaneArgs& a, const Clah
     return MI_OK;
 }
 
-mi_status clahe_dev(mi_ctx* c, hipStream_t s, const PlaneArgs& a, double clip_limit, int tiles_x, int tiles_y, const UVJob* uv)
+mi_status clahe_dev(mi_ctx* c, hipStream_t s, const PlaneArgs& a, double clip_limit, int tiles_x, int tiles_y, const UVJob* uv,
+                    const FrameList* fl = nullptr)
 {
     ClaheGeom g;
     mi_status st = clahe_geometry(c, a.width, a.height, clip_limit, tiles_x, tiles_y, &g);
@@ -159,9 +185,9 @@ mi_status clahe_dev(mi_ctx* c, hipStream_t s, const PlaneArgs& a, double clip_li
         const int nf = std::min(chunk, a.n_frames - f0);
         st = grow_dev(c, &c->d_luts, &c->luts_bytes, (size_t)nf * tiles * 256);
         if (st) return st;
-        st = launch_tile_luts(c, s, a, g, f0, nf, c->d_luts);
+        st = launch_tile_luts(c, s, a, g, f0, nf, c->d_luts, fl);
         if (st) return st;
-        st = launch_interp(c, s, a, g, f0, nf, c->d_luts, uv);
+        st = launch_interp(c, s, a, g, f0, nf, c->d_luts, uv, fl);
         if (st) return st;
     }
     return MI_OK;

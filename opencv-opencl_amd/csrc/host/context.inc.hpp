@@ -314,7 +314,10 @@ PlaneBatch make_plane(const PlaneArgs& a)
 constexpr int kMaxGridY = 65535;
 
 // ---- stage launchers (all assume ctx lock held, device set) -------------------------------------
-mi_status launch_hist_partials(mi_ctx* c, hipStream_t s, const PlaneArgs& a, int f0, int nf, int* nparts_out)
+// The stage launchers below take an optional frame list (kernels/common.hip.h FrameList, mi_*_nv12_frames_dev): with one, the
+// launch goes to the *_frames_kernel entry on the same body, and `a` describes the shape only (a.src / a.dst: the list's first
+// frame, frame strides 0).
+mi_status launch_hist_partials(mi_ctx* c, hipStream_t s, const PlaneArgs& a, int f0, int nf, int* nparts_out, const FrameList* fl = nullptr)
 {
     PlaneArgs b = a;
     b.src = a.src + (size_t)f0 * a.src_frame; b.dst = nullptr; b.n_frames = nf;
@@ -322,12 +325,14 @@ mi_status launch_hist_partials(mi_ctx* c, hipStream_t s, const PlaneArgs& a, int
     const int B = blocks_per_frame(c, (long long)a.width * a.height, p.rows, nf, 256);
     mi_status st = grow_dev(c, &c->d_partial, &c->partial_bytes, (size_t)nf * B * 256 * sizeof(uint32_t));
     if (st) return st;
-    LAUNCH(c, s, MI_K_HIST, hist_partial_kernel, dim3(B, nf), dim3(kHistThreads), 0, p, c->d_partial);
+    if (fl) LAUNCH(c, s, MI_K_HIST, hist_partial_frames_kernel, dim3(B, nf), dim3(kHistThreads), 0, *fl, p, c->d_partial);
+    else    LAUNCH(c, s, MI_K_HIST, hist_partial_kernel, dim3(B, nf), dim3(kHistThreads), 0, p, c->d_partial);
     *nparts_out = B;
     return MI_OK;
 }
 
-mi_status launch_apply(mi_ctx* c, hipStream_t s, const PlaneArgs& a, int f0, int nf, const uint8_t* d_luts, const UVJob* uv_all)
+mi_status launch_apply(mi_ctx* c, hipStream_t s, const PlaneArgs& a, int f0, int nf, const uint8_t* d_luts, const UVJob* uv_all,
+                       const FrameList* fl = nullptr)
 {
     PlaneArgs b = a;
     b.src = a.src + (size_t)f0 * a.src_frame; b.dst = a.dst + (size_t)f0 * a.dst_frame; b.n_frames = nf;
@@ -340,7 +345,9 @@ mi_status launch_apply(mi_ctx* c, hipStream_t s, const PlaneArgs& a, int f0, int
         uv.dst = uv_all->dst + (long long)f0 * uv_all->dst_frame;
         bytes += uv.bytes * (uv.mode ? 2 : 1);
     }
+    if (fl) bytes += fl->uv.row_bytes * fl->uv.rows * (fl->uv.mode ? 2 : 1);
     const int B = blocks_per_frame(c, bytes / 2, p.rows, nf, 2048);
-    LAUNCH(c, s, MI_K_LUT_APPLY, lut_apply_kernel, dim3(B, nf), dim3(kThreads), 0, p, d_luts, uv);
+    if (fl) LAUNCH(c, s, MI_K_LUT_APPLY, lut_apply_frames_kernel, dim3(B, nf), dim3(kThreads), 0, *fl, p, d_luts);
+    else    LAUNCH(c, s, MI_K_LUT_APPLY, lut_apply_kernel, dim3(B, nf), dim3(kThreads), 0, p, d_luts, uv);
     return MI_OK;
 }

@@ -202,7 +202,7 @@ mi_status equalize_fused_dev(mi_ctx* c, hipStream_t s, const PlaneArgs& a, const
 // Up to eight frames (a stream's frame, a cv::Mat call; up to sixteen of 1080p or less): histogram + LUT in one launch whose last
 // workgroup writes the LUT, then the apply kernel.  No inter-workgroup waits, so no finish kernel and nothing to repair: 17 us per
 // 4K frame against 22.5 us for the fused pair, whose single read cannot pay for its hand-off latency on so little data.
-mi_status equalize_two_kernel_dev(mi_ctx* c, hipStream_t s, const PlaneArgs& a, const UVJob* uv)
+mi_status equalize_two_kernel_dev(mi_ctx* c, hipStream_t s, const PlaneArgs& a, const UVJob* uv, const FrameList* fl = nullptr)
 {
     const size_t need = (size_t)a.n_frames * (256 + 1) * sizeof(uint32_t);
     if (need > c->ghist_bytes) {
@@ -223,30 +223,33 @@ mi_status equalize_two_kernel_dev(mi_ctx* c, hipStream_t s, const PlaneArgs& a, 
     if (p.rows > 1) Bq = std::min<long long>(Bq, p.rows);
     const int B = (int)std::max<long long>(1, Bq);
     uint32_t* cnt = c->d_ghist + (size_t)a.n_frames * 256;
-    LAUNCH(c, s, MI_K_HIST, hist_lut_kernel, dim3(B, a.n_frames), dim3(kHistThreads), 0, p, c->d_ghist, cnt,
-           (int)((long long)a.width * a.height), c->d_luts);
-    return launch_apply(c, s, a, 0, a.n_frames, c->d_luts, uv);
+    if (fl) LAUNCH(c, s, MI_K_HIST, hist_lut_frames_kernel, dim3(B, a.n_frames), dim3(kHistThreads), 0, *fl, p, c->d_ghist, cnt,
+                   (int)((long long)a.width * a.height), c->d_luts);
+    else    LAUNCH(c, s, MI_K_HIST, hist_lut_kernel, dim3(B, a.n_frames), dim3(kHistThreads), 0, p, c->d_ghist, cnt,
+                   (int)((long long)a.width * a.height), c->d_luts);
+    return launch_apply(c, s, a, 0, a.n_frames, c->d_luts, uv, fl);
 }
 
-mi_status equalize_dev(mi_ctx* c, hipStream_t s, const PlaneArgs& a, const UVJob* uv)
+// `fl`: a chunk of a frame list (at most kFramesPerLaunch frames): the same stages on the table policy, never the fused kernel
+mi_status equalize_dev(mi_ctx* c, hipStream_t s, const PlaneArgs& a, const UVJob* uv, const FrameList* fl = nullptr)
 {
     // measured (profiles/r03_l_single_frame.txt, us per call, two-kernel / fused pair / three-kernel): 4K 1 frame 17.0 / 22.5 / 24.5,
     // 2 frames 20.6 / 28.2 / 29.5, 4 frames 29.3 / 38.9 / 37.1, 8 frames 45.5 / 52.2 / 53.2, 16 frames 87.2 / 87.0 / 90.5;
     // 1080p 4 frames 15.3 / 22.5 / 19.7, 8 frames 21.6 / 28.2 / 25.1, 16 frames 29.5 / 39.3 / 35.7
     const long long px = (long long)a.width * a.height;
     const int k2 = c->two_kernel_max_frames;
-    if (k2 > 0 && (a.n_frames <= k2 || (a.n_frames <= 2 * k2 && px <= 1920LL * 1088))) return equalize_two_kernel_dev(c, s, a, uv);
-    if (fused_applicable(c, a, uv) && fused_admit(c)) return equalize_fused_dev(c, s, a, uv);
+    if (k2 > 0 && (a.n_frames <= k2 || (a.n_frames <= 2 * k2 && px <= 1920LL * 1088))) return equalize_two_kernel_dev(c, s, a, uv, fl);
+    if (!fl && fused_applicable(c, a, uv) && fused_admit(c)) return equalize_fused_dev(c, s, a, uv);
     for (int f0 = 0; f0 < a.n_frames; f0 += kMaxGridY) {
         const int nf = std::min(kMaxGridY, a.n_frames - f0);
         int nparts = 0;
-        mi_status st = launch_hist_partials(c, s, a, f0, nf, &nparts);
+        mi_status st = launch_hist_partials(c, s, a, f0, nf, &nparts, fl);
         if (st) return st;
         st = grow_dev(c, &c->d_luts, &c->luts_bytes, (size_t)nf * 256);
         if (st) return st;
         LAUNCH(c, s, MI_K_EQ_LUT, equalize_lut_kernel, dim3(nf), dim3(kThreads), 0,
                (const uint32_t*)c->d_partial, nparts, (int)((long long)a.width * a.height), c->d_luts, (int32_t*)nullptr);
-        st = launch_apply(c, s, a, f0, nf, c->d_luts, uv);
+        st = launch_apply(c, s, a, f0, nf, c->d_luts, uv, fl);
         if (st) return st;
     }
     return MI_OK;

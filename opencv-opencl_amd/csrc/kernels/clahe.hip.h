@@ -105,9 +105,9 @@ __device__ __forceinline__ void tile_hist_edges(uint32_t* h, const uint8_t* src,
 
 // NT = 256 or 512 threads: the histogram is shared by the whole workgroup either way (32 KiB), so 512 threads put 32 waves on a CU
 // (4 workgroups) instead of 20 (5 workgroups of 4 waves); waves 4..7 leave before the 256-thread fold / LUT stage.
-template <int NT>
-__global__ __launch_bounds__(NT) void tile_hist_kernel(const uint8_t* __restrict__ src_base, long long step, long long frame_stride,
-                                                      ClaheGeom g, uint32_t* __restrict__ partial, uint8_t* __restrict__ luts, int xcd_map)
+template <int NT, class Frames>
+__device__ __forceinline__ void tile_hist_body(const Frames& fr, const long long& step, const ClaheGeom& g, uint32_t* __restrict__ partial,
+                                               uint8_t* __restrict__ luts, int xcd_map)
 {
     __shared__ uint32_t h[256 * kCopies];                       // exactly 32 KiB: five workgroups per CU (a 16-byte scan scratch
     uint32_t* const s_wave = h;                                 // next to it made it four); the scans reuse h[0..3] once h is folded
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(NT) void tile_hist_kernel(const uint8_t* __restrict
     const int ntiles = gridDim.y;
     const int tile = xcd_map ? ((int)(blockIdx.y & 7) * (ntiles >> 3) + (int)(blockIdx.y >> 3)) : (int)blockIdx.y;
     const int ty = tile / g.tiles_x, tx = tile - ty * g.tiles_x;
-    const uint8_t* src = src_base + (long long)f * frame_stride;
+    const uint8_t* src = fr.src_of(f);
     const int r0 = (int)((long long)g.tile_h * s / S), r1 = (int)((long long)g.tile_h * (s + 1) / S);
     const int x0 = tx * g.tile_w;
     const int in_w = max(0, min(g.tile_w, g.width - x0));     // columns of this tile that lie inside the frame
@@ -156,6 +156,18 @@ __global__ __launch_bounds__(NT) void tile_hist_kernel(const uint8_t* __restrict
     if (luts) luts[((size_t)f * gridDim.y + tile) * 256 + t] = tile_lut_value(bin, g, s_wave);     // host passes luts only when S == 1
     else partial[(((size_t)f * gridDim.y + tile) * S + s) * 256 + t] = bin;
 }
+template <int NT>
+__global__ __launch_bounds__(NT) void tile_hist_kernel(const uint8_t* __restrict__ src_base, long long step, long long frame_stride,
+                                                      ClaheGeom g, uint32_t* __restrict__ partial, uint8_t* __restrict__ luts, int xcd_map)
+{
+    tile_hist_body<NT>(StridedSource{src_base, frame_stride}, step, g, partial, luts, xcd_map);
+}
+template <int NT>
+__global__ __launch_bounds__(NT) void tile_hist_frames_kernel(FrameList l, long long step, ClaheGeom g, uint32_t* __restrict__ partial,
+                                                             uint8_t* __restrict__ luts, int xcd_map)
+{
+    tile_hist_body<NT>(TableFrames{l}, step, g, partial, luts, xcd_map);
+}
 
 // ---------------------------------------------------------------------------------------------
 // K4m  K4 for batches of SMALL tiles: one workgroup walks K consecutive tiles of its XCD's run, LUT included.
@@ -169,9 +181,9 @@ __global__ __launch_bounds__(NT) void tile_hist_kernel(const uint8_t* __restrict
 // (tiles / 8) % K == 0; without the XCD map: g * K + k.
 // ---------------------------------------------------------------------------------------------
 constexpr int kTileMultiThreads = 512;
-__global__ __launch_bounds__(kTileMultiThreads) void tile_hist_multi_kernel(const uint8_t* __restrict__ src_base, long long step,
-                                                                            long long frame_stride, ClaheGeom g,
-                                                                            uint8_t* __restrict__ luts, int ntiles, int K, int xcd_map)
+template <class Frames>
+__device__ __forceinline__ void tile_hist_multi_body(const Frames& fr, const long long& step, const ClaheGeom& g, uint8_t* __restrict__ luts, int ntiles,
+                                                     int K, int xcd_map)
 {
     constexpr int NT = kTileMultiThreads;
     __shared__ uint32_t h[256 * kCopies];
@@ -182,7 +194,7 @@ __global__ __launch_bounds__(kTileMultiThreads) void tile_hist_multi_kernel(cons
     const u32x4 zero = {0u, 0u, 0u, 0u};
     for (int i = t; i < 256 * kCopies / 4; i += NT) reinterpret_cast<u32x4*>(h)[i] = zero;
     const int f = blockIdx.z, grp = blockIdx.y;
-    const uint8_t* src = src_base + (long long)f * frame_stride;
+    const uint8_t* src = fr.src_of(f);
     const int first = xcd_map ? ((grp & 7) * (ntiles >> 3) + (grp >> 3) * K) : grp * K;
     for (int k = 0; k < K; ++k) {
         __syncthreads();                                        // histogram zeroed (and the previous tile's scans done with s_wave)
@@ -230,6 +242,17 @@ __global__ __launch_bounds__(kTileMultiThreads) void tile_hist_multi_kernel(cons
             __syncthreads(); __syncthreads();
         }
     }
+}
+__global__ __launch_bounds__(kTileMultiThreads) void tile_hist_multi_kernel(const uint8_t* __restrict__ src_base, long long step,
+                                                                            long long frame_stride, ClaheGeom g,
+                                                                            uint8_t* __restrict__ luts, int ntiles, int K, int xcd_map)
+{
+    tile_hist_multi_body(StridedSource{src_base, frame_stride}, step, g, luts, ntiles, K, xcd_map);
+}
+__global__ __launch_bounds__(kTileMultiThreads) void tile_hist_multi_frames_kernel(FrameList l, long long step, ClaheGeom g,
+                                                                                   uint8_t* __restrict__ luts, int ntiles, int K, int xcd_map)
+{
+    tile_hist_multi_body(TableFrames{l}, step, g, luts, ntiles, K, xcd_map);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -377,9 +400,9 @@ __device__ __forceinline__ u32x4 clahe_vec16_f32(const f32x4* quadf, u32x4 q, co
 // segment (blockIdx.z, `groups` 16-pixel groups wide -- the host sizes it so that a segment touches at most pair_cap pairs) stages only
 // the pairs ITS columns use, first pair = p0 below, and the float tables serve grids of up to 63 tiles across (16 x 16 on 4K: the
 // interpolation 322 -> see DESIGN.md).
-template <bool FT, bool FMA>
-__global__ __launch_bounds__(kThreads) void clahe_interp_kernel(PlaneBatch p, ClaheGeom g, const uint8_t* __restrict__ luts,
-                                                               int subs, int groups, UVJob uv, int pair_cap)
+template <bool FT, bool FMA, class Frames>
+__device__ __forceinline__ void clahe_interp_body(const PlaneBatch& p, const Frames& fr, const ClaheGeom& g, const uint8_t* __restrict__ luts,
+                                                  int subs, int groups, int pair_cap)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t quad[];   // [(tiles_x + 1)][256] u32 quads, or f32x4 when FT
     f32x4* quadf = reinterpret_cast<f32x4*>(quad);
@@ -441,8 +464,8 @@ __global__ __launch_bounds__(kThreads) void clahe_interp_kernel(PlaneBatch p, Cl
             pr = pr < 0 ? 0 : (pr >= npairs ? npairs - 1 : pr);
             poff[j] = pr << 8;
         }
-        const uint8_t* src = p.src + (long long)f * p.src_frame;
-        uint8_t* dst = p.dst + (long long)f * p.dst_frame;
+        const uint8_t* src = fr.src_of(f);
+        uint8_t* dst = fr.dst_of(f);
         const bool full = x0 + kInterpPx <= g.width;
         // ty1 is monotone in y: trim the widened range to the rows that really belong to this band, using the
         // reference's own float expression (at most kBandMargin+1 steps per end)
@@ -497,12 +520,27 @@ __global__ __launch_bounds__(kThreads) void clahe_interp_kernel(PlaneBatch p, Cl
             }
         }
     }
+}
+template <bool FT, bool FMA>
+__global__ __launch_bounds__(kThreads) void clahe_interp_kernel(PlaneBatch p, ClaheGeom g, const uint8_t* __restrict__ luts,
+                                                               int subs, int groups, UVJob uv, int pair_cap)
+{
+    clahe_interp_body<FT, FMA>(p, StridedFrames{p}, g, luts, subs, groups, pair_cap);
+    const int f = (int)gridDim.y - 1 - (int)blockIdx.y;
     if (uv.bytes > 0 && blockIdx.z == 0)
         uv_flat(uv.src + (long long)f * uv.src_frame, uv.dst + (long long)f * uv.dst_frame, uv.bytes, uv.mode, blockIdx.x, gridDim.x);
 }
+template <bool FT, bool FMA>
+__global__ __launch_bounds__(kThreads) void clahe_interp_frames_kernel(FrameList l, PlaneBatch p, ClaheGeom g, const uint8_t* __restrict__ luts,
+                                                                      int subs, int groups, int pair_cap)
+{
+    clahe_interp_body<FT, FMA>(p, TableFrames{l}, g, luts, subs, groups, pair_cap);
+    if (blockIdx.z == 0) uv_frame(l, (int)gridDim.y - 1 - (int)blockIdx.y, blockIdx.x, gridDim.x);
+}
 
 // Fallback for tile grids too wide for the LDS pair table: LUTs gathered from global memory (L2).
-__global__ __launch_bounds__(kThreads) void clahe_interp_global_kernel(PlaneBatch p, ClaheGeom g, const uint8_t* __restrict__ luts)
+template <class Frames>
+__device__ __forceinline__ void clahe_interp_global_body(const PlaneBatch& p, const Frames& fr, const ClaheGeom& g, const uint8_t* __restrict__ luts)
 {
     const int f = blockIdx.z;
     const int y = blockIdx.y;
@@ -517,13 +555,21 @@ __global__ __launch_bounds__(kThreads) void clahe_interp_global_kernel(PlaneBatc
     int ty1 = floor_f32_to_int(tyf);
     const float ya = __fsub_rn(tyf, (float)ty1), ya1 = __fsub_rn(1.0f, ya);
     int ty2 = ty1 + 1; ty1 = max(ty1, 0); ty2 = min(ty2, g.tiles_y - 1);
-    const uint32_t v = p.src[(long long)f * p.src_frame + (long long)y * p.src_step + x];
+    const uint32_t v = fr.src_of(f)[(long long)y * p.src_step + x];
     const uint32_t q = (uint32_t)lf[((size_t)ty1 * g.tiles_x + tx1) * 256 + v] |
                        ((uint32_t)lf[((size_t)ty1 * g.tiles_x + tx2) * 256 + v] << 8) |
                        ((uint32_t)lf[((size_t)ty2 * g.tiles_x + tx1) * 256 + v] << 16) |
                        ((uint32_t)lf[((size_t)ty2 * g.tiles_x + tx2) * 256 + v] << 24);
-    p.dst[(long long)f * p.dst_frame + (long long)y * p.dst_step + x] =
+    fr.dst_of(f)[(long long)y * p.dst_step + x] =
         (uint8_t)(g.contract ? clahe_px<true>(q, xa, xa1, ya, ya1) : clahe_px<false>(q, xa, xa1, ya, ya1));
+}
+__global__ __launch_bounds__(kThreads) void clahe_interp_global_kernel(PlaneBatch p, ClaheGeom g, const uint8_t* __restrict__ luts)
+{
+    clahe_interp_global_body(p, StridedFrames{p}, g, luts);
+}
+__global__ __launch_bounds__(kThreads) void clahe_interp_global_frames_kernel(FrameList l, PlaneBatch p, ClaheGeom g, const uint8_t* __restrict__ luts)
+{
+    clahe_interp_global_body(p, TableFrames{l}, g, luts);
 }
 
 // UV-only launch (used when the Y kernel cannot carry the UV job).
@@ -531,6 +577,10 @@ __global__ __launch_bounds__(kThreads) void uv_kernel(UVJob uv)
 {
     const int f = blockIdx.y;
     uv_flat(uv.src + (long long)f * uv.src_frame, uv.dst + (long long)f * uv.dst_frame, uv.bytes, uv.mode, blockIdx.x, gridDim.x);
+}
+__global__ __launch_bounds__(kThreads) void uv_frames_kernel(FrameList l)
+{
+    uv_frame(l, blockIdx.y, blockIdx.x, gridDim.x);
 }
 
 

@@ -43,6 +43,39 @@ struct UVJob {
     int mode;                         // 0 = fill 128, 1 = copy
 };
 
+// A list of NV12 frames, each with its own Y and UV plane addresses (mi_*_nv12_frames_dev): the table travels BY VALUE in the kernel
+// arguments -- 64 x 32 B = 2 KiB, read with scalar kernarg loads indexed by the frame's grid coordinate (no scratch, no extra copy).
+// The planes share one shape: the Y pitches live in the launch's PlaneBatch, the UV pitches in `uv`.
+constexpr int kFramesPerLaunch = 64;
+struct FramePlanes { const uint8_t* y_in; const uint8_t* uv_in; uint8_t* y_out; uint8_t* uv_out; };
+struct UVRows {
+    long long src_step, dst_step;     // bytes between UV rows
+    long long row_bytes;              // W
+    int rows;                         // H / 2; 0 = no UV work
+    int mode;                         // 0 = fill 128, 1 = copy
+};
+struct FrameList { FramePlanes f[kFramesPerLaunch]; UVRows uv; };
+
+// Where frame f of a launch lives.  Kernel bodies are templates on one of these two policies: the existing kernels wrap them with
+// the strided one (exactly the arithmetic they always had), the *_frames_kernel entries with the table.
+// (The strided policies refer to the kernel's own arguments instead of copying them, so that a wrapped kernel reads them where it
+// always did; DESIGN.md §9 records how close its ISA stays to the kernel's before the split.)
+struct StridedFrames {                // frame f at base + f * frame_stride, over a PlaneBatch
+    const PlaneBatch& p;
+    __device__ __forceinline__ const uint8_t* src_of(long long f) const { return p.src + f * p.src_frame; }
+    __device__ __forceinline__ uint8_t* dst_of(long long f) const { return p.dst + f * p.dst_frame; }
+};
+struct StridedSource {                // the same for kernels that only read: base pointer and frame stride as separate arguments
+    const uint8_t* __restrict__ const& base;
+    const long long& frame_stride;
+    __device__ __forceinline__ const uint8_t* src_of(long long f) const { return base + f * frame_stride; }
+};
+struct TableFrames {                  // frame f at the addresses the table holds
+    const FrameList& l;
+    __device__ __forceinline__ const uint8_t* src_of(long long f) const { return l.f[f].y_in; }
+    __device__ __forceinline__ uint8_t* dst_of(long long f) const { return l.f[f].y_out; }
+};
+
 struct Split16 { long long head, nvec, tail; };
 
 __device__ __forceinline__ Split16 split16(const void* p, long long n)

@@ -65,12 +65,13 @@ __device__ __forceinline__ void hist_rows(uint32_t* h, const uint8_t* row0, long
 }
 
 // this workgroup's share (blockIdx.x of gridDim.x) of frame blockIdx.y, counted into the LDS histogram h (zeroed here)
-__device__ __forceinline__ void hist_block(uint32_t* h, const PlaneBatch& p)
+template <class Frames>
+__device__ __forceinline__ void hist_block(uint32_t* h, const PlaneBatch& p, const Frames& fr)
 {
     const int t = threadIdx.x;
     for (int i = t; i < 256 * kCopies; i += kHistThreads) h[i] = 0;
     __syncthreads();
-    const uint8_t* base = p.src + (long long)blockIdx.y * p.src_frame;
+    const uint8_t* base = fr.src_of(blockIdx.y);
     if (p.rows == 1) {
         hist_flat<kHistThreads>(h, base, p.row_bytes, blockIdx.x, gridDim.x);
     } else if ((p.src_step & 15) == 0) {
@@ -82,12 +83,21 @@ __device__ __forceinline__ void hist_block(uint32_t* h, const PlaneBatch& p)
     __syncthreads();
 }
 
-__global__ __launch_bounds__(kHistThreads) void hist_partial_kernel(PlaneBatch p, uint32_t* __restrict__ partial)
+template <class Frames>
+__device__ __forceinline__ void hist_partial_body(const PlaneBatch& p, const Frames& fr, uint32_t* __restrict__ partial)
 {
     __shared__ uint32_t h[256 * kCopies];
-    hist_block(h, p);
+    hist_block(h, p, fr);
     const int t = threadIdx.x;
     if (t < 256) partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + t] = lds_hist_bin(h, t);
+}
+__global__ __launch_bounds__(kHistThreads) void hist_partial_kernel(PlaneBatch p, uint32_t* __restrict__ partial)
+{
+    hist_partial_body(p, StridedFrames{p}, partial);
+}
+__global__ __launch_bounds__(kHistThreads) void hist_partial_frames_kernel(FrameList l, PlaneBatch p, uint32_t* __restrict__ partial)
+{
+    hist_partial_body(p, TableFrames{l}, partial);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -145,13 +155,14 @@ __global__ __launch_bounds__(kThreads) void equalize_lut_kernel(const uint32_t* 
 // launch (plus its gap) is gone against K1 -> K2.  With lut_apply_kernel behind it a single 4K frame costs two launches.
 // grid = (B, n_frames), 256 threads.  ghist[f][256] and cnt[f] must be zero on entry (they are zero again on exit).
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kHistThreads) void hist_lut_kernel(PlaneBatch p, uint32_t* __restrict__ ghist, uint32_t* __restrict__ cnt,
-                                                                int total, uint8_t* __restrict__ lut_out)
+template <class Frames>
+__device__ __forceinline__ void hist_lut_body(const PlaneBatch& p, const Frames& fr, uint32_t* __restrict__ ghist, uint32_t* __restrict__ cnt,
+                                              int total, uint8_t* __restrict__ lut_out)
 {
     __shared__ uint32_t h[256 * kCopies];
     __shared__ EqLutShared sh;
     __shared__ int s_last;
-    hist_block(h, p);
+    hist_block(h, p, fr);
     const int t = threadIdx.x, f = blockIdx.y;
     uint32_t* gh = ghist + (size_t)f * 256;
     const uint32_t mine = lds_hist_bin(h, t);
@@ -167,6 +178,16 @@ __global__ __launch_bounds__(kHistThreads) void hist_lut_kernel(PlaneBatch p, ui
     const uint32_t c = __hip_atomic_exchange(gh + t, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // RMW at the L2: coherent by construction
     if (t == 0) __hip_atomic_store(cnt + f, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     lut_out[(size_t)f * 256 + t] = equalize_lut_value(c, total, &sh);
+}
+__global__ __launch_bounds__(kHistThreads) void hist_lut_kernel(PlaneBatch p, uint32_t* __restrict__ ghist, uint32_t* __restrict__ cnt,
+                                                                int total, uint8_t* __restrict__ lut_out)
+{
+    hist_lut_body(p, StridedFrames{p}, ghist, cnt, total, lut_out);
+}
+__global__ __launch_bounds__(kHistThreads) void hist_lut_frames_kernel(FrameList l, PlaneBatch p, uint32_t* __restrict__ ghist,
+                                                                       uint32_t* __restrict__ cnt, int total, uint8_t* __restrict__ lut_out)
+{
+    hist_lut_body(p, TableFrames{l}, ghist, cnt, total, lut_out);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -280,7 +301,60 @@ __device__ __forceinline__ void uv_flat(const uint8_t* src, uint8_t* dst, long l
     }
 }
 
-__global__ __launch_bounds__(kThreads) void lut_apply_kernel(PlaneBatch p, const uint8_t* __restrict__ luts, UVJob uv)
+// UV plane of pitched rows (a frame of a list): fill with 128 or copy.  This workgroup (`part` of `nparts`) takes a band of rows and
+// walks it as (row, 16-byte slot) items, four in flight per lane, stores aligned on each destination row; the unaligned bytes at both
+// ends of a row (at most 15 + 15) are byte stores.  Nothing outside the row_bytes of each row is touched.
+__device__ __forceinline__ void uv_rows(const uint8_t* src, long long src_step, uint8_t* dst, long long dst_step, long long row_bytes,
+                                        int rows, int mode, int part, int nparts)
+{
+    const int t = threadIdx.x;
+    const int r0 = (int)((long long)rows * part / nparts), r1 = (int)((long long)rows * (part + 1) / nparts);
+    const int slots = (int)(row_bytes >> 4);                   // a row holds at most this many aligned vectors
+    if (slots > 0) {
+        const u32x4 g = {0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};
+        const int items = (r1 - r0) * slots;
+        int row = r0 + t / slots, slot = t % slots;
+        const int drow = kThreads / slots, dslot = kThreads - drow * slots;
+        for (int it = t; it < items; it += 4 * kThreads) {
+            u32x4 q[4]; bool qv[4]; uint8_t* dp[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                uint8_t* d = dst + (long long)row * dst_step;
+                const long long o = (long long)((16 - (int)((uintptr_t)d & 15)) & 15) + ((long long)slot << 4);
+                qv[k] = it + k * kThreads < items && o + 16 <= row_bytes;
+                dp[k] = d + o;
+                q[k] = g;
+                if (mode && qv[k]) q[k] = *reinterpret_cast<const u32x4_u*>(src + (long long)row * src_step + o);
+                row += drow; slot += dslot;
+                if (slot >= slots) { slot -= slots; ++row; }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) if (qv[k]) *reinterpret_cast<u32x4*>(dp[k]) = q[k];
+        }
+    }
+    const int items = (r1 - r0) * 30;                           // byte items per row: c < 15 its head, c >= 15 its tail
+    for (int it = t; it < items; it += kThreads) {
+        const int row = r0 + it / 30, c = it % 30;
+        uint8_t* d = dst + (long long)row * dst_step;
+        const Split16 s = split16(d, row_bytes);
+        long long o = -1;
+        if (c < 15) { if (c < s.head) o = c; }
+        else if (c - 15 < s.tail) o = s.head + (s.nvec << 4) + (c - 15);
+        if (o >= 0) d[o] = mode ? src[(long long)row * src_step + o] : (uint8_t)128;
+    }
+}
+
+// the chroma of frame f of a list (rows == 1: one flat plane, split across the workgroups as uv_flat does); an in-place copy moves nothing
+__device__ __forceinline__ void uv_frame(const FrameList& l, int f, int part, int nparts)
+{
+    const UVRows& uv = l.uv;
+    if (uv.rows <= 0 || (uv.mode && l.f[f].uv_in == l.f[f].uv_out)) return;
+    if (uv.rows == 1) uv_flat(l.f[f].uv_in, l.f[f].uv_out, uv.row_bytes, uv.mode, part, nparts);
+    else uv_rows(l.f[f].uv_in, uv.src_step, l.f[f].uv_out, uv.dst_step, uv.row_bytes, uv.rows, uv.mode, part, nparts);
+}
+
+template <class Frames>
+__device__ __forceinline__ void lut_apply_body(const PlaneBatch& p, const Frames& fr, const uint8_t* __restrict__ luts)
 {
     __shared__ uint32_t lut[256 * kCopies];
     // frames last-to-first: the histogram pass streamed the batch first-to-last, its tail is still in the Infinity Cache
@@ -291,8 +365,8 @@ __global__ __launch_bounds__(kThreads) void lut_apply_kernel(PlaneBatch p, const
         for (int k = 0; k < kCopies; ++k) lut[(t << kCopyShift) + ((k + t) & (kCopies - 1))] = v;
     }
     __syncthreads();
-    const uint8_t* src = p.src + (long long)f * p.src_frame;
-    uint8_t* dst = p.dst + (long long)f * p.dst_frame;
+    const uint8_t* src = fr.src_of(f);
+    uint8_t* dst = fr.dst_of(f);
     if (p.rows == 1) {
         lut_flat(lut, src, dst, p.row_bytes, blockIdx.x, gridDim.x);
     } else if ((p.dst_step & 15) == 0) {
@@ -302,8 +376,18 @@ __global__ __launch_bounds__(kThreads) void lut_apply_kernel(PlaneBatch p, const
         for (int r = blockIdx.x; r < p.rows; r += gridDim.x)
             lut_flat(lut, src + (long long)r * p.src_step, dst + (long long)r * p.dst_step, p.row_bytes, 0, 1);
     }
+}
+__global__ __launch_bounds__(kThreads) void lut_apply_kernel(PlaneBatch p, const uint8_t* __restrict__ luts, UVJob uv)
+{
+    lut_apply_body(p, StridedFrames{p}, luts);
+    const int f = (int)gridDim.y - 1 - (int)blockIdx.y;
     if (uv.bytes > 0)
         uv_flat(uv.src + (long long)f * uv.src_frame, uv.dst + (long long)f * uv.dst_frame, uv.bytes, uv.mode, blockIdx.x, gridDim.x);
+}
+__global__ __launch_bounds__(kThreads) void lut_apply_frames_kernel(FrameList l, PlaneBatch p, const uint8_t* __restrict__ luts)
+{
+    lut_apply_body(p, TableFrames{l}, luts);
+    uv_frame(l, (int)gridDim.y - 1 - (int)blockIdx.y, blockIdx.x, gridDim.x);
 }
 
 

@@ -44,6 +44,7 @@ DECLARED_SYMBOLS = [
     "mi_analyze_diff_u8", "mi_analyze_diff_u8_batch_dev",
     "mi_device_pci_bus_id", "mi_thread_bind_near_device",
     "mi_clahe_p010", "mi_clahe_p010_batch_dev",
+    "mi_equalize_hist_nv12_frames_dev", "mi_clahe_nv12_frames_dev",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -61,6 +62,11 @@ class _NumaBinding(C.Structure):
 class _PipeConfig(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("op", C.c_int), ("uv_mode", C.c_int), ("clip_limit", C.c_double),
                 ("tiles_x", C.c_int), ("tiles_y", C.c_int), ("depth", C.c_int), ("uv_policy", C.c_int), ("format", C.c_int)]
+
+
+class Nv12FrameDev(C.Structure):
+    """mi_nv12_frame_dev: one NV12 frame of a list, its four plane addresses (device pointers)."""
+    _fields_ = [("y_in", C.c_void_p), ("uv_in", C.c_void_p), ("y_out", C.c_void_p), ("uv_out", C.c_void_p)]
 
 
 class MiError(RuntimeError):
@@ -141,6 +147,8 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_u16_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, d, i, i, vp]
     L.mi_clahe_p010.argtypes = [vp, vp, vp, i, i, i, d, i, i]
     L.mi_clahe_p010_batch_dev.argtypes = [vp, vp, vp, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_nv12_frames_dev.argtypes = [vp, C.POINTER(Nv12FrameDev), i, i, i, sz, sz, sz, sz, i, vp]
+    L.mi_clahe_nv12_frames_dev.argtypes = [vp, C.POINTER(Nv12FrameDev), i, i, i, sz, sz, sz, sz, i, d, i, i, vp]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -226,6 +234,33 @@ def _dptr(t) -> int:
     if not t.is_cuda:
         raise MiError(1, "device pointer", "tensor is not on a HIP device")
     return int(t.data_ptr())
+
+
+def _plane_pitch(planes, given, width: int, what: str) -> int:
+    """Row pitch in bytes of a list of planes: `given`, else the row stride shared by the 2-D tensors among them, else `width`."""
+    if given is not None:
+        return int(given)
+    strides = {int(p.stride(-2)) * p.element_size() for p in planes if not isinstance(p, int) and p is not None and p.dim() >= 2}
+    if len(strides) > 1:
+        raise MiError(1, what, f"the planes have different row pitches {sorted(strides)}: one call takes one pitch")
+    return strides.pop() if strides else int(width)
+
+
+def _frame_list(inputs, outputs, width, pitches, what):
+    """inputs / outputs: sequences of (y, uv) pairs (torch CUDA tensors, raw device addresses, uv may be None); outputs None =
+    in place.  Returns the mi_nv12_frame_dev array and the four pitches (y_in, uv_in, y_out, uv_out)."""
+    inputs = list(inputs)
+    outputs = inputs if outputs is None else list(outputs)
+    if len(outputs) != len(inputs):
+        raise MiError(1, what, f"{len(inputs)} inputs but {len(outputs)} outputs")
+    y_in, uv_in = [f[0] for f in inputs], [f[1] for f in inputs]
+    y_out, uv_out = [f[0] for f in outputs], [f[1] for f in outputs]
+    p = [_plane_pitch(pl, g, width, what) for pl, g in zip((y_in, uv_in, y_out, uv_out), pitches)]
+    arr = (Nv12FrameDev * max(1, len(inputs)))()
+    for k in range(len(inputs)):
+        arr[k] = Nv12FrameDev(_dptr(y_in[k]), None if uv_in[k] is None else _dptr(uv_in[k]), _dptr(y_out[k]),
+                               None if uv_out[k] is None else _dptr(uv_out[k]))
+    return arr, len(inputs), p
 
 
 _live_contexts: "weakref.WeakSet[Context]" = weakref.WeakSet()
@@ -352,6 +387,23 @@ class Context:
         self._chk(self._L.mi_clahe_nv12_batch_dev(self._h, _dptr(d_in), _dptr(d_out), width, height, n_frames,
                                                 uv_mode, float(clip_limit), tiles_x, tiles_y, stream),
                   "mi_clahe_nv12_batch_dev")
+
+    # ---- NV12 frames as a list of pitched planes (decoder surfaces, tensor lists) ----
+    def equalize_hist_nv12_frames(self, inputs, outputs, width, height, uv_mode=UV_FILL128, y_in_pitch=None, uv_in_pitch=None,
+                                  y_out_pitch=None, uv_out_pitch=None, stream=0):
+        """mi_equalize_hist_nv12_frames_dev.  inputs / outputs: lists of (y, uv) planes -- torch CUDA tensors or raw device
+        addresses; uv of an input may be None with UV_FILL128; outputs=None processes every frame in place.  A pitch left at None
+        is the row stride of the 2-D uint8 tensors given for that plane (all frames must agree), or the width."""
+        arr, n, p = _frame_list(inputs, outputs, width, (y_in_pitch, uv_in_pitch, y_out_pitch, uv_out_pitch), "equalize_hist_nv12_frames")
+        self._chk(self._L.mi_equalize_hist_nv12_frames_dev(self._h, arr, n, int(width), int(height), p[0], p[1], p[2], p[3],
+                                                         int(uv_mode), stream), "mi_equalize_hist_nv12_frames_dev")
+
+    def clahe_nv12_frames(self, inputs, outputs, width, height, uv_mode=UV_FILL128, clip_limit=2.0, tiles_x=8, tiles_y=8,
+                          y_in_pitch=None, uv_in_pitch=None, y_out_pitch=None, uv_out_pitch=None, stream=0):
+        """mi_clahe_nv12_frames_dev; arguments as equalize_hist_nv12_frames, plus the CLAHE parameters."""
+        arr, n, p = _frame_list(inputs, outputs, width, (y_in_pitch, uv_in_pitch, y_out_pitch, uv_out_pitch), "clahe_nv12_frames")
+        self._chk(self._L.mi_clahe_nv12_frames_dev(self._h, arr, n, int(width), int(height), p[0], p[1], p[2], p[3], int(uv_mode),
+                                                 float(clip_limit), int(tiles_x), int(tiles_y), stream), "mi_clahe_nv12_frames_dev")
 
     # ---- the reference's own check: cv::absdiff + xf::cv::analyzeDiff (1frameMeasure.cpp:91-100) ----
     def analyze_diff(self, a: np.ndarray, b: np.ndarray | None = None, threshold: int = 1, want_diff: bool = False):
