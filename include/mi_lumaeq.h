@@ -261,6 +261,26 @@ mi_status mi_clahe_p010(mi_ctx* ctx, const uint16_t* in, uint16_t* out, int widt
                         mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
 mi_status mi_clahe_p010_batch_dev(mi_ctx* ctx, const void* d_in, void* d_out, int width, int height, int n_frames,
                                   mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y, void* stream);
+/* mi_clahe_p010_frames_dev: a LIST of P010 frames in device memory, each with its own pitched Y and UV plane (a Main10 decoder's
+ * surface pool), as mi_clahe_nv12_frames_dev takes NV12 frames.  mi_p010_frame_dev is mi_nv12_frame_dev: four plane addresses.
+ * Pitches are in BYTES, shared by every frame of the call, even and each >= 2*W:
+ *   y_in  : H rows of W uint16 at y_in_pitch                       y_out  : H rows at y_out_pitch
+ *   uv_in : H/2 rows of W interleaved uint16 U, V at uv_in_pitch   uv_out : H/2 rows at uv_out_pitch
+ *           (read with MI_UV_COPY only; may be NULL with MI_UV_FILL128)
+ * Plane addresses are 2-byte aligned (16-byte aligned Y inputs with a pitch that is a multiple of 16 take the faster tile
+ * histograms; anything else is slower, never different).  The luma is byte for byte what mi_clahe_p010_batch_dev / mi_clahe_u16*
+ * return on the same pixels, the chroma is set to 0x8000 or copied; nothing outside the 2*W bytes of an output row is written.
+ * In place is decided PER FRAME: a frame is in place when y_out == y_in (the pitches must then be equal), and one list may mix
+ * in-place and out-of-place frames; in place with MI_UV_COPY leaves the chroma as it is.  Outputs of DIFFERENT frames that overlap
+ * each other give undefined results (not checked).  Stream rules, hipGraph capture and the options as mi_clahe_nv12_frames_dev and
+ * mi_clahe_u16_batch_dev (clahe16_*).  No equalizeHist form (OpenCV's is 8-bit only) and no host form.
+ * Errors, MI_ERR_BAD_ARG: those of mi_clahe_nv12_frames_dev, plus an odd pitch, a pitch < 2*W and a plane address that is not
+ * 2-byte aligned.  MI_ERR_UNSUPPORTED: sizes beyond what mi_clahe_u16 accepts.  n_frames, width or height of 0: MI_OK, nothing
+ * written.  Nothing is enqueued unless every frame passes the checks. */
+typedef mi_nv12_frame_dev mi_p010_frame_dev;
+mi_status mi_clahe_p010_frames_dev(mi_ctx* ctx, const mi_p010_frame_dev* frames, int n_frames, int width, int height,
+                                   size_t y_in_pitch, size_t uv_in_pitch, size_t y_out_pitch, size_t uv_out_pitch,
+                                   mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y, void* stream);
 
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at

@@ -7,8 +7,12 @@ namespace {
 constexpr int kWideHintWord = 32;          // h_mirror[32]: sequence number of the last call that met a 14-bit rectangle; [33]: of the last call executed
 constexpr int32_t kWideHintCalls = 8;      // ... and for how many executed calls after it clahe_interp16_mid_kernel is still launched
 
+// fl: a frame list (kernels/common.hip.h FrameList, at most kFramesPerLaunch frames: mi_clahe_p010_frames_dev).  With one, every launch
+// goes to the *_frames_kernel entry on the same body, with the same grid; src / dst are then the list's first frame, the frame strides 0,
+// and the steps the shared pitches.  Inside each scratch-bounded chunk below the kernels see the chunk's frames from index 0.
 mi_status clahe16_dev(mi_ctx* c, hipStream_t s, const uint8_t* src, size_t src_step, size_t src_frame, uint8_t* dst, size_t dst_step,
-                      size_t dst_frame, int width, int height, int n_frames, double clip_limit, int tiles_x, int tiles_y)
+                      size_t dst_frame, int width, int height, int n_frames, double clip_limit, int tiles_x, int tiles_y,
+                      const FrameList* fl = nullptr)
 {
     ClaheGeom g;
     mi_status st = clahe_geometry(c, width, height, clip_limit, tiles_x, tiles_y, &g);
@@ -33,9 +37,11 @@ mi_status clahe16_dev(mi_ctx* c, hipStream_t s, const uint8_t* src, size_t src_s
         if (st) return st;
         HIPCHK(c, hipMemsetAsync(c->d_sync16, 0, c->sync16_bytes, s));
     }
-    // vector path of the tile histogram: no REFLECT_101 padding, 8-pixel groups inside one tile, 16-B aligned rows
-    const int vec = width % tiles_x == 0 && height % tiles_y == 0 && g.tile_w % 8 == 0 &&
-                    (((uintptr_t)src | src_step | src_frame) & 15) == 0;
+    // vector path of the tile histogram: no REFLECT_101 padding, 8-pixel groups inside one tile, 16-B aligned rows (a frame list: every
+    // frame's Y input; otherwise the careful path runs, same bytes)
+    uintptr_t in_bits = (uintptr_t)src | src_step | src_frame;
+    if (fl) for (int k = 0; k < n_frames; ++k) in_bits |= (uintptr_t)fl->f[k].y_in;
+    const int vec = width % tiles_x == 0 && height % tiles_y == 0 && g.tile_w % 8 == 0 && (in_bits & 15) == 0;
     const int npairs = tiles_x + 1, bands = tiles_y + 1;
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
         const int nf = std::min(chunk, n_frames - f0);
@@ -44,6 +50,12 @@ mi_status clahe16_dev(mi_ctx* c, hipStream_t s, const uint8_t* src, size_t src_s
         Range16* ranges = reinterpret_cast<Range16*>(c->d_c16 + (size_t)nf * tiles * kHist16 * (sizeof(uint32_t) + sizeof(uint16_t)));
         Range16* franges = ranges + (size_t)nf * tiles;
         uint32_t* fdone = reinterpret_cast<uint32_t*>(franges + nf);
+        FrameList l;                                                 // this chunk's frames of the list, from index 0
+        bool any_in_place = false;
+        if (fl) {
+            l.uv = fl->uv;
+            for (int k = 0; k < nf; ++k) { l.f[k] = fl->f[f0 + k]; any_in_place = any_in_place || l.f[k].y_in == l.f[k].y_out; }
+        }
         const bool bet12 = vec && c->clahe16_fast12;
         // Rectangles whose range needs 8193..16384 table entries (14-bit content) have a kernel of their own since round 6
         // (clahe_interp16_mid_kernel: one window of a 128-KiB table).  Its launch costs ~8 us whether or not it finds work, so with the
@@ -58,10 +70,16 @@ mi_status clahe16_dev(mi_ctx* c, hipStream_t s, const uint8_t* src, size_t src_s
         // the context's shift hint: two words at the end of the arrival scratch (read / collect, rolled over by the interpolation kernel)
         uint32_t* hint = bet12 ? c->d_sync16 + c->sync16_bytes / sizeof(uint32_t) - 4 : nullptr;
         // 12-bit bet (kernels/clahe16.hip.h): vector geometry only; a tile that loses it is redone the careful way in the same workgroup
-        if (bet12)
+        if (bet12 && fl)
+            LAUNCH(c, s, MI_K_TILE_HIST, (tile_hist12_frames_kernel<kHist12Threads, kCopies12>), dim3(tiles, nf), dim3(kHist12Threads), kHist12Words * sizeof(uint32_t),
+                   l, (long long)src_step, g, hist, ranges, lut_scale16, clip16, luts, c->d_sync16, franges, fdone, hint);
+        else if (bet12)
             LAUNCH(c, s, MI_K_TILE_HIST, (tile_hist12_kernel<kHist12Threads, kCopies12>), dim3(tiles, nf), dim3(kHist12Threads), kHist12Words * sizeof(uint32_t),
                    src + (size_t)f0 * src_frame, (long long)src_step, (long long)src_frame, g, hist, ranges, lut_scale16, clip16, luts,
                    c->d_sync16, franges, fdone, hint);
+        else if (fl)
+            LAUNCH(c, s, MI_K_TILE_HIST, tile_hist16_frames_kernel, dim3(tiles, nf), dim3(1024), kHalf16 * sizeof(uint32_t),
+                   l, (long long)src_step, g, hist, ranges, vec);
         else
             LAUNCH(c, s, MI_K_TILE_HIST, tile_hist16_kernel, dim3(tiles, nf), dim3(1024), kHalf16 * sizeof(uint32_t),
                    src + (size_t)f0 * src_frame, (long long)src_step, (long long)src_frame, g, hist, ranges, vec);
@@ -72,9 +90,13 @@ mi_status clahe16_dev(mi_ctx* c, hipStream_t s, const uint8_t* src, size_t src_s
             uint16_t* lutT = reinterpret_cast<uint16_t*>(hist);
             LAUNCH(c, s, MI_K_TILE_LUT, transpose_lut16_kernel, dim3(kHist16 / 256, nf), dim3(kThreads), (size_t)tiles * 256 * sizeof(uint16_t),
                    (const uint16_t*)luts, lutT, tiles);
-            LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp16T_kernel, dim3((width + kThreads - 1) / kThreads, height, nf), dim3(kThreads), 0,
-                   src + (size_t)f0 * src_frame, (long long)src_step, (long long)src_frame,
-                   dst + (size_t)f0 * dst_frame, (long long)dst_step, (long long)dst_frame, g, (const uint16_t*)lutT, (const Range16*)franges, hint);
+            if (fl)
+                LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp16T_frames_kernel, dim3((width + kThreads - 1) / kThreads, height, nf), dim3(kThreads), 0,
+                       l, (long long)src_step, (long long)dst_step, g, (const uint16_t*)lutT, (const Range16*)franges, hint);
+            else
+                LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp16T_kernel, dim3((width + kThreads - 1) / kThreads, height, nf), dim3(kThreads), 0,
+                       src + (size_t)f0 * src_frame, (long long)src_step, (long long)src_frame,
+                       dst + (size_t)f0 * dst_frame, (long long)dst_step, (long long)dst_frame, g, (const uint16_t*)lutT, (const Range16*)franges, hint);
         } else {
             // one workgroup per (tile pair, band, sub-band).  Few frames: enough sub-bands to fill the chip (four workgroups per CU), never
             // less than ~16 rows each.  Many frames: still TWO sub-bands per band while they keep 64 rows -- 2 workgroups are resident per
@@ -90,7 +112,15 @@ mi_status clahe16_dev(mi_ctx* c, hipStream_t s, const uint8_t* src, size_t src_s
             if (grid > 0x7fffffffLL) return fail(c, MI_ERR_UNSUPPORTED, "16-bit CLAHE: tile grid too large");
             const uint8_t* sp = src + (size_t)f0 * src_frame;
             uint8_t* dp = dst + (size_t)f0 * dst_frame;
-            if (g.contract)
+            if (fl && g.contract)
+                LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp16_frames_kernel<true>, dim3((unsigned)grid), dim3(kInterp16Threads),
+                       (size_t)kInterp16Entries * sizeof(uint2), l, (long long)src_step, (long long)dst_step, g, (const uint16_t*)luts,
+                       (const Range16*)franges, subs, nf, (const Range16*)ranges, hint, mid_runs ? 1 : 0, wh);
+            else if (fl)
+                LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp16_frames_kernel<false>, dim3((unsigned)grid), dim3(kInterp16Threads),
+                       (size_t)kInterp16Entries * sizeof(uint2), l, (long long)src_step, (long long)dst_step, g, (const uint16_t*)luts,
+                       (const Range16*)franges, subs, nf, (const Range16*)ranges, hint, mid_runs ? 1 : 0, wh);
+            else if (g.contract)
                 LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp16_kernel<true>, dim3((unsigned)grid), dim3(kInterp16Threads),
                        (size_t)kInterp16Entries * sizeof(uint2), sp, (long long)src_step, (long long)src_frame,
                        dp, (long long)dst_step, (long long)dst_frame, g, (const uint16_t*)luts, (const Range16*)franges, subs, nf, (const Range16*)ranges, hint,
@@ -104,7 +134,15 @@ mi_status clahe16_dev(mi_ctx* c, hipStream_t s, const uint8_t* src, size_t src_s
                 ++c->c16_mid_launches;
                 // the same work items, walked by one persistent workgroup per CU (a multiple of 8 workgroups: each stays on its XCD)
                 const long long grid_p = std::min<long long>(grid, (long long)(std::max(c->cu_count, 8) + 7) / 8 * 8);
-                if (g.contract)
+                if (fl && g.contract)
+                    LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp16_mid_frames_kernel<true>, dim3((unsigned)grid_p), dim3(kInterp16MidThreads),
+                           (size_t)kInterp16MidEntries * sizeof(uint2), l, (long long)src_step, (long long)dst_step, g, (const uint16_t*)luts,
+                           (const Range16*)franges, subs, nf, (const Range16*)ranges);
+                else if (fl)
+                    LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp16_mid_frames_kernel<false>, dim3((unsigned)grid_p), dim3(kInterp16MidThreads),
+                           (size_t)kInterp16MidEntries * sizeof(uint2), l, (long long)src_step, (long long)dst_step, g, (const uint16_t*)luts,
+                           (const Range16*)franges, subs, nf, (const Range16*)ranges);
+                else if (g.contract)
                     LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp16_mid_kernel<true>, dim3((unsigned)grid_p), dim3(kInterp16MidThreads),
                            (size_t)kInterp16MidEntries * sizeof(uint2), sp, (long long)src_step, (long long)src_frame,
                            dp, (long long)dst_step, (long long)dst_frame, g, (const uint16_t*)luts, (const Range16*)franges, subs, nf, (const Range16*)ranges);
@@ -114,12 +152,15 @@ mi_status clahe16_dev(mi_ctx* c, hipStream_t s, const uint8_t* src, size_t src_s
                            dp, (long long)dst_step, (long long)dst_frame, g, (const uint16_t*)luts, (const Range16*)franges, subs, nf, (const Range16*)ranges);
             }
             // IN-PLACE rectangles whose range does not fit one window of a table (their workgroups above returned at once); the launch is a
-            // no-op for frames without any, and is left out altogether when the call is not in place (it cost 8 us per call)
-            if (sp == dp) {
-                const long long wide_items = (long long)((width + kThreads - 1) / kThreads) * height;
-                LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp16_wide_kernel, dim3((unsigned)std::min<long long>(wide_items, std::max(512, 2048 / nf)), 1, nf), dim3(kThreads), 0,
+            // no-op for frames without any, and is left out altogether when no frame of the launch is in place (it cost 8 us per call)
+            const long long wide_items = (long long)((width + kThreads - 1) / kThreads) * height;
+            const dim3 wide_grid((unsigned)std::min<long long>(wide_items, std::max(512, 2048 / nf)), 1, nf);
+            if (fl && any_in_place)
+                LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp16_wide_frames_kernel, wide_grid, dim3(kThreads), 0,
+                       l, (long long)src_step, (long long)dst_step, g, (const uint16_t*)luts, (const Range16*)franges, mid_runs ? 1 : 0, (const Range16*)ranges);
+            else if (!fl && sp == dp)
+                LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp16_wide_kernel, wide_grid, dim3(kThreads), 0,
                        sp, (long long)src_step, (long long)src_frame, dp, (long long)dst_step, (long long)dst_frame, g, (const uint16_t*)luts, (const Range16*)franges, mid_runs ? 1 : 0, (const Range16*)ranges);
-            }
         }
     }
     return MI_OK;

@@ -12,6 +12,7 @@ struct FramesShape {
     int width, height;
     size_t y_in_pitch, uv_in_pitch, y_out_pitch, uv_out_pitch;
     mi_uv_mode uv_mode;
+    int sample_bytes = 1;             // 2: P010 frames (mi_clahe_p010_frames_dev, host/p010_frames.inc.hpp): rows of 2 * W bytes
 };
 
 // The bytes a plane's rows span: [p, p + (rows - 1) * pitch + row_bytes).  Planes are compared as such address ranges.
@@ -22,25 +23,32 @@ struct Span {
 };
 
 // Everything is checked before anything is enqueued: a refused call writes nothing.  *work = false: MI_OK with nothing to do.
+// Rows are W * sample_bytes bytes; 16-bit frames also need even pitches and 2-byte aligned planes, and keep to mi_clahe_u16's sizes.
 mi_status check_frames(mi_ctx* c, const mi_nv12_frame_dev* frames, int n_frames, const FramesShape& s, bool* work)
 {
     *work = false;
     if (n_frames < 0 || s.width < 0 || s.height < 0) return fail(c, MI_ERR_BAD_ARG, "negative size");
     if (n_frames > 0 && !frames) return fail(c, MI_ERR_BAD_ARG, "null frame list");
     if (s.uv_mode != MI_UV_FILL128 && s.uv_mode != MI_UV_COPY) return fail(c, MI_ERR_BAD_ARG, "bad uv_mode");
-    if ((s.width & 1) || (s.height & 1)) return fail(c, MI_ERR_BAD_ARG, "NV12 frames have even width and height");
-    const size_t w = (size_t)s.width;
-    if (s.y_in_pitch < w || s.y_out_pitch < w || s.uv_out_pitch < w || (s.uv_mode == MI_UV_COPY && s.uv_in_pitch < w))
+    if ((s.width & 1) || (s.height & 1)) return fail(c, MI_ERR_BAD_ARG, "4:2:0 frames have even width and height");
+    const size_t w = (size_t)s.width * (size_t)s.sample_bytes;        // bytes per row
+    const bool copy = s.uv_mode == MI_UV_COPY;
+    if (s.y_in_pitch < w || s.y_out_pitch < w || s.uv_out_pitch < w || (copy && s.uv_in_pitch < w))
         return fail(c, MI_ERR_BAD_ARG, "pitch < width");
+    const size_t odd = s.sample_bytes - 1;                             // address bits a 16-bit sample may not have
+    if ((s.y_in_pitch | s.y_out_pitch | s.uv_out_pitch | (copy ? s.uv_in_pitch : 0)) & odd)
+        return fail(c, MI_ERR_BAD_ARG, "16-bit planes need even pitches");
     if (n_frames == 0 || s.width == 0 || s.height == 0) return MI_OK;
+    if (s.sample_bytes == 2 && (long long)s.width * s.height > 0x3fffffffLL) return fail(c, MI_ERR_UNSUPPORTED, "image too large");
     if ((long long)s.width * s.height > 0x7fffffffLL) return fail(c, MI_ERR_UNSUPPORTED, "width*height must be < 2^31 (OpenCV: int total)");
     if (s.width > (1 << 24) || s.height > (1 << 24)) return fail(c, MI_ERR_UNSUPPORTED, "width/height must be <= 2^24");
     const size_t yrows = (size_t)s.height, uvrows = yrows / 2;
-    const bool copy = s.uv_mode == MI_UV_COPY;
     for (int k = 0; k < n_frames; ++k) {
         const mi_nv12_frame_dev& f = frames[k];
         if (!f.y_in || !f.y_out || !f.uv_out) return fail(c, MI_ERR_BAD_ARG, "null plane pointer");
         if (copy && !f.uv_in) return fail(c, MI_ERR_BAD_ARG, "null uv_in with MI_UV_COPY");
+        if (((uintptr_t)f.y_in | (uintptr_t)f.y_out | (uintptr_t)f.uv_out | (copy ? (uintptr_t)f.uv_in : 0)) & odd)
+            return fail(c, MI_ERR_BAD_ARG, "16-bit planes must be 2-byte aligned");
         // each output plane against each plane the call reads (Y in; UV in when copying): disjoint, or the very same plane (in place)
         const Span yi(f.y_in, s.y_in_pitch, w, yrows), yo(f.y_out, s.y_out_pitch, w, yrows), uo(f.uv_out, s.uv_out_pitch, w, uvrows);
         const bool y_in_place = f.y_out == f.y_in && s.y_out_pitch == s.y_in_pitch;
@@ -64,7 +72,7 @@ FrameList frame_chunk(const mi_nv12_frame_dev* frames, int nf, const FramesShape
     for (int k = 0; k < nf; ++k)
         l.f[k] = FramePlanes{(const uint8_t*)frames[k].y_in, s.uv_mode == MI_UV_COPY ? (const uint8_t*)frames[k].uv_in : nullptr,
                              (uint8_t*)frames[k].y_out, (uint8_t*)frames[k].uv_out};
-    const long long w = s.width, uvrows = s.height / 2;
+    const long long w = (long long)s.width * s.sample_bytes, uvrows = s.height / 2;
     l.uv.mode = s.uv_mode == MI_UV_COPY ? 1 : 0;
     l.uv.src_step = (long long)s.uv_in_pitch; l.uv.dst_step = (long long)s.uv_out_pitch;
     const bool tight = s.uv_out_pitch == (size_t)w && (l.uv.mode == 0 || s.uv_in_pitch == (size_t)w);

@@ -77,6 +77,12 @@ __device__ __forceinline__ bool rect_is_mid(uint32_t span, uint32_t presence)
 // one has overwritten): 0 = the small table's (clahe_interp16_kernel), 1 = ONE window of the mid kernel's table, if it runs,
 // 2 = clahe_interp16_wide_kernel gathers its pixels from the LUTs in L2.  All three kernels ask this with the same numbers, so a
 // frame is shared out by rectangles: a 12-bit frame with a hot pixel leaves four of its 81 rectangles to the gathers, not all.
+// OWNERSHIP INVARIANT.  For every frame of a launch, every pixel has exactly one writer among clahe_interp16_kernel,
+// clahe_interp16_mid_kernel and clahe_interp16_wide_kernel.  All three derive it from the same numbers: the union of the rectangle's four
+// tile ranges, the call's mid_runs flag, and the frame's in-place bit -- Frames::in_place(f), asked of the launch's frame policy.  The
+// strided policy answers for the whole launch (src_base == dst_base); a frame list (TableFrames) answers per frame (y_in == y_out),
+// so one list may mix in-place frames, shared out by rect_owner_in_place, with out-of-place ones, whose rectangles all belong to the
+// table kernels (rect_is_mid) and for which the wide kernel's workgroups return at once.
 __device__ __forceinline__ int rect_owner_in_place(uint32_t span, int mid_runs)
 {
     if (span < (uint32_t)kInterp16Entries) return 0;
@@ -194,16 +200,17 @@ __device__ __forceinline__ void hist16_fast_vec(uint32_t* h16, const u32x4& q, u
 // grid = (tiles, frames), NT threads (1024 in tile_hist16_kernel), (4 << kWinBits) bytes of dynamic LDS.  steps in BYTES.
 // `vec` (host: no REFLECT_101 padding, tile_w % 8 == 0, 16-B aligned rows): a lane takes 8 pixels per 16-byte load with
 // four loads in flight; otherwise one pixel per lane per step with index reflection.
-template <int kWinBits, int NT = 1024>
+// Frames: where frame f of the launch lives (StridedSource over the kernel's arguments, or TableFrames: kernels/common.hip.h).
+template <int kWinBits, int NT = 1024, class Frames>
 __device__ __forceinline__ void tile_hist16_careful(uint32_t* h16 /* [1 << kWinBits] LDS */, uint32_t& s_lo, uint32_t& s_hi, uint32_t& s_or,
-                                                    const uint8_t* __restrict__ src_base, long long step, long long frame_stride,
+                                                    const Frames& fr, const long long& step,
                                                     const ClaheGeom& g, uint32_t* __restrict__ hist, Range16* __restrict__ ranges, int vec)
 {
     constexpr int kWin = 1 << kWinBits;
     const int t = threadIdx.x;
     const int tile = blockIdx.x, f = blockIdx.y;
     const int ty = tile / g.tiles_x, tx = tile - ty * g.tiles_x;
-    const uint8_t* src = src_base + (long long)f * frame_stride;
+    const uint8_t* src = fr.src_of(f);
     const size_t tile_id = (size_t)f * gridDim.x + tile;
     uint32_t* out = hist + tile_id * kHist16;
     const long long items = (long long)g.tile_h * g.tile_w;
@@ -336,7 +343,14 @@ __global__ __launch_bounds__(1024) void tile_hist16_kernel(const uint8_t* __rest
 {
     extern __shared__ uint32_t h16[];                            // [32768]
     __shared__ uint32_t s_lo, s_hi, s_or;
-    tile_hist16_careful<15>(h16, s_lo, s_hi, s_or, src_base, step, frame_stride, g, hist, ranges, vec);
+    tile_hist16_careful<15>(h16, s_lo, s_hi, s_or, StridedSource{src_base, frame_stride}, step, g, hist, ranges, vec);
+}
+__global__ __launch_bounds__(1024) void tile_hist16_frames_kernel(FrameList l, long long step, ClaheGeom g, uint32_t* __restrict__ hist,
+                                                                 Range16* __restrict__ ranges, int vec)
+{
+    extern __shared__ uint32_t h16[];
+    __shared__ uint32_t s_lo, s_hi, s_or;
+    tile_hist16_careful<15>(h16, s_lo, s_hi, s_or, TableFrames{l}, step, g, hist, ranges, vec);
 }
 
 // ---- 12-bit fast path -----------------------------------------------------------------------------------------------------
@@ -409,13 +423,14 @@ __device__ __forceinline__ void hint_roll(uint32_t* h)
 }
 
 // grid = (tiles, frames), NT threads, 4096 * COPIES * 4 bytes of dynamic LDS; vector geometry only (the host checks: no padding,
-// tile_w % 8 == 0, 16-B aligned rows).  A thread owns 4096 / NT consecutive bins in the LUT stage.
-template <int NT, int COPIES>
-__global__ __launch_bounds__(NT, 8) void tile_hist12_kernel(const uint8_t* __restrict__ src_base, long long step, long long frame_stride,
-                                                        ClaheGeom g, uint32_t* __restrict__ hist, Range16* __restrict__ ranges,
-                                                        float lut_scale16, int clip16, uint16_t* __restrict__ luts,
-                                                        uint32_t* __restrict__ sync, Range16* __restrict__ frame_ranges, uint32_t* __restrict__ frame_done,
-                                                        uint32_t* __restrict__ shift_hint)
+// tile_w % 8 == 0, 16-B aligned rows -- for a frame list, every Y input of the launch).  A thread owns 4096 / NT consecutive bins in
+// the LUT stage.
+template <int NT, int COPIES, class Frames>
+__device__ __forceinline__ void tile_hist12_body(const Frames& fr, const long long& step,
+                                                 const ClaheGeom& g, uint32_t* __restrict__ hist, Range16* __restrict__ ranges,
+                                                 float lut_scale16, int clip16, uint16_t* __restrict__ luts,
+                                                 uint32_t* __restrict__ sync, Range16* __restrict__ frame_ranges, uint32_t* __restrict__ frame_done,
+                                                 uint32_t* __restrict__ shift_hint)
 {
     static_assert(COPIES == 2 || COPIES == 4, "copies");
     constexpr int NW = NT / 64, BPT = kBins12 / NT;                // waves; bins per thread
@@ -428,7 +443,7 @@ __global__ __launch_bounds__(NT, 8) void tile_hist12_kernel(const uint8_t* __res
     const int tile = blockIdx.x, f = blockIdx.y;
     const size_t tile_id = (size_t)f * gridDim.x + tile;
     const int ty = tile / g.tiles_x, tx = tile - ty * g.tiles_x;
-    const uint8_t* src = src_base + (long long)f * frame_stride;
+    const uint8_t* src = fr.src_of(f);
     const int slots = g.tile_w >> 3;
     const int vitems = g.tile_h * slots;
     const uint8_t* tbase = src + (long long)ty * g.tile_h * step + (long long)tx * g.tile_w * 2;
@@ -552,7 +567,7 @@ __global__ __launch_bounds__(NT, 8) void tile_hist12_kernel(const uint8_t* __res
     };
     if (lost) {                                                   // uniform over the workgroup: redo the tile the careful way
         __syncthreads();
-        tile_hist16_careful<kCarefulBits, NT>(h16, s_lo, s_hi, s_or, src_base, step, frame_stride, g, hist, ranges, 1);   // its counters fill the same LDS
+        tile_hist16_careful<kCarefulBits, NT>(h16, s_lo, s_hi, s_or, fr, step, g, hist, ranges, 1);   // its counters fill the same LDS
         if (t == 0) { arrive(false, 0u, 0u); settle_frame(); }      // (after the sweeps: nothing of the arrival is live across them)
         return;
     }
@@ -660,6 +675,25 @@ __global__ __launch_bounds__(NT, 8) void tile_hist12_kernel(const uint8_t* __res
     for (int j = 0; j < BPT / 4; ++j)
         *reinterpret_cast<uint2*>(luts + tile_id * kHist16 + b0 + 4 * j) = make_uint2(packed[2 * j], packed[2 * j + 1]);
     if (t == 0) { Range16 r; r.lo = lo | (chunk_bits(lo, hi) << 16); r.hi = hi | (sft << 16) | (sft ? kHistCompressed : 0u) | kLutDone; ranges[tile_id] = r; settle_frame(); }
+}
+template <int NT, int COPIES>
+__global__ __launch_bounds__(NT, 8) void tile_hist12_kernel(const uint8_t* __restrict__ src_base, long long step, long long frame_stride,
+                                                        ClaheGeom g, uint32_t* __restrict__ hist, Range16* __restrict__ ranges,
+                                                        float lut_scale16, int clip16, uint16_t* __restrict__ luts,
+                                                        uint32_t* __restrict__ sync, Range16* __restrict__ frame_ranges, uint32_t* __restrict__ frame_done,
+                                                        uint32_t* __restrict__ shift_hint)
+{
+    tile_hist12_body<NT, COPIES>(StridedSource{src_base, frame_stride}, step, g, hist, ranges, lut_scale16, clip16, luts, sync, frame_ranges,
+                                 frame_done, shift_hint);
+}
+template <int NT, int COPIES>
+__global__ __launch_bounds__(NT, 8) void tile_hist12_frames_kernel(FrameList l, long long step,
+                                                               ClaheGeom g, uint32_t* __restrict__ hist, Range16* __restrict__ ranges,
+                                                               float lut_scale16, int clip16, uint16_t* __restrict__ luts,
+                                                               uint32_t* __restrict__ sync, Range16* __restrict__ frame_ranges, uint32_t* __restrict__ frame_done,
+                                                               uint32_t* __restrict__ shift_hint)
+{
+    tile_hist12_body<NT, COPIES>(TableFrames{l}, step, g, hist, ranges, lut_scale16, clip16, luts, sync, frame_ranges, frame_done, shift_hint);
 }
 
 // grid = (tiles, frames), 1024 threads.  Works in the frame's COMPRESSED domain j = value >> shift (shift = the smallest of its tiles'
@@ -833,9 +867,8 @@ __global__ __launch_bounds__(1024) void tile_lut16_kernel(const uint32_t* __rest
 // ENTRIES / THREADS: the table and the workgroup (8192 / 512: clahe_interp16_kernel; 16384 / 1024: clahe_interp16_mid_kernel).
 // `id`: the work item (clahe_interp16_kernel: the workgroup's index).  mid_runs: clahe_interp16_mid_kernel is part of this call and takes
 // the rectangles rect_is_mid() names; everybody else's are the small table's.
-template <bool FMA, int ENTRIES, int THREADS>
-__device__ __forceinline__ void interp16_item(long long id, const uint8_t* __restrict__ src_base, long long src_step, long long src_frame,
-                                              uint8_t* __restrict__ dst_base, long long dst_step, long long dst_frame,
+template <bool FMA, int ENTRIES, int THREADS, class Frames>
+__device__ __forceinline__ void interp16_item(long long id, const Frames& frames, long long src_step, long long dst_step,
                                               const ClaheGeom& g, const uint16_t* __restrict__ luts,
                                               const Range16* __restrict__ frame_ranges, int subs, int n_frames,
                                               const Range16* __restrict__ tile_ranges, int mid_runs, const WideHint& wide_hint)
@@ -883,7 +916,7 @@ __device__ __forceinline__ void interp16_item(long long id, const uint8_t* __res
         presence = range_mask(r00.lo) | range_mask(r01.lo) | range_mask(r10.lo) | range_mask(r11.lo);
     }
     const uint32_t start = fr.lo & ~3u;
-    if (src_base == dst_base) {                                     // in place: by rectangles (rect_owner_in_place), uniform
+    if (frames.in_place(f)) {                                       // in place: by rectangles (rect_owner_in_place), uniform
         const int owner = rect_owner_in_place(fr.hi - start, mid_runs);
         if (!MID && owner != 0) { if (t == 0 && fr.hi - start < (uint32_t)kInterp16MidEntries) wide_seen(wide_hint); return; }
         if (MID && owner != 1) return;
@@ -919,8 +952,8 @@ __device__ __forceinline__ void interp16_item(long long id, const uint8_t* __res
     const int g_lo = x_lo >> 3, ngroups = ((x_hi + 7) >> 3) - g_lo;
     const int phases = max(1, THREADS / ngroups);
     const int passes = (ngroups + THREADS - 1) / THREADS;          // > 1 only for tiles wider than 8 * THREADS pixels
-    const uint8_t* src = src_base + (long long)f * src_frame;
-    uint8_t* dst = dst_base + (long long)f * dst_frame;
+    const uint8_t* src = frames.src_of(f);
+    uint8_t* dst = frames.dst_of(f);
 
     // Which windows does this workgroup's rectangle populate at all?  (One extra read of its pixels: real images are locally much
     // narrower than their frame.)  Bit w of s_windows: some owned pixel has (value - start) / ENTRIES == w; at most 8 (mid kernel: 4) windows.
@@ -1143,8 +1176,19 @@ __global__ __launch_bounds__(kInterp16Threads) void clahe_interp16_kernel(const 
                                                                          int mid_runs, WideHint wide_hint)
 {
     hint_roll(shift_hint);
-    interp16_item<FMA, kInterp16Entries, kInterp16Threads>(blockIdx.x, src_base, src_step, src_frame, dst_base, dst_step, dst_frame, g, luts,
-                                                           frame_ranges, subs, n_frames, tile_ranges, mid_runs, wide_hint);
+    interp16_item<FMA, kInterp16Entries, kInterp16Threads>(blockIdx.x, StridedPair{src_base, src_frame, dst_base, dst_frame}, src_step, dst_step,
+                                                           g, luts, frame_ranges, subs, n_frames, tile_ranges, mid_runs, wide_hint);
+}
+template <bool FMA>
+__global__ __launch_bounds__(kInterp16Threads) void clahe_interp16_frames_kernel(FrameList l, long long src_step, long long dst_step,
+                                                                                ClaheGeom g, const uint16_t* __restrict__ luts,
+                                                                                const Range16* __restrict__ frame_ranges, int subs, int n_frames,
+                                                                                const Range16* __restrict__ tile_ranges, uint32_t* shift_hint,
+                                                                                int mid_runs, WideHint wide_hint)
+{
+    hint_roll(shift_hint);
+    interp16_item<FMA, kInterp16Entries, kInterp16Threads>(blockIdx.x, TableFrames{l}, src_step, dst_step, g, luts, frame_ranges, subs, n_frames,
+                                                           tile_ranges, mid_runs, wide_hint);
 }
 
 // PERSISTENT: grid = min(work items, CUs rounded to a multiple of 8) workgroups of 1024 threads with 128 KiB of dynamic LDS (one per CU
@@ -1152,12 +1196,11 @@ __global__ __launch_bounds__(kInterp16Threads) void clahe_interp16_kernel(const 
 // item for item (same `subs`, same XCD dealing: item & 7 -- the grid is a multiple of 8, so a workgroup stays on its XCD).  Frames whose
 // whole range fits the small table are known from a bit mask built once per workgroup.  In place it keeps to frames of at most 16384
 // values (one window per rectangle); wider ones are the gathering kernel's, whole.
-template <bool FMA>
-__global__ __launch_bounds__(kInterp16MidThreads) void clahe_interp16_mid_kernel(const uint8_t* __restrict__ src_base, long long src_step, long long src_frame,
-                                                                                uint8_t* __restrict__ dst_base, long long dst_step, long long dst_frame,
-                                                                                ClaheGeom g, const uint16_t* __restrict__ luts,
-                                                                                const Range16* __restrict__ frame_ranges, int subs, int n_frames,
-                                                                                const Range16* __restrict__ tile_ranges)
+template <bool FMA, class Frames>
+__device__ __forceinline__ void interp16_mid_body(const Frames& frames, long long src_step, long long dst_step,
+                                                  const ClaheGeom& g, const uint16_t* __restrict__ luts,
+                                                  const Range16* __restrict__ frame_ranges, int subs, int n_frames,
+                                                  const Range16* __restrict__ tile_ranges)
 {
     __shared__ unsigned long long s_wide[16];                        // bit f % 64 of word f / 64: frame f may hold such a rectangle (<= 1024 frames per launch)
     const int t = threadIdx.x;
@@ -1183,9 +1226,26 @@ __global__ __launch_bounds__(kInterp16MidThreads) void clahe_interp16_mid_kernel
         const int f = n_frames - 1 - (int)(row / ((long long)subs * bands));
         if (!((s_wide[(f >> 6) & 15] >> (f & 63)) & 1ull)) continue;  // uniform: no such rectangle in this frame
         __syncthreads();                                            // the previous item's table is no longer read
-        interp16_item<FMA, kInterp16MidEntries, kInterp16MidThreads>(id, src_base, src_step, src_frame, dst_base, dst_step, dst_frame, g, luts,
+        interp16_item<FMA, kInterp16MidEntries, kInterp16MidThreads>(id, frames, src_step, dst_step, g, luts,
                                                                      frame_ranges, subs, n_frames, tile_ranges, 1, none);
     }
+}
+template <bool FMA>
+__global__ __launch_bounds__(kInterp16MidThreads) void clahe_interp16_mid_kernel(const uint8_t* __restrict__ src_base, long long src_step, long long src_frame,
+                                                                                uint8_t* __restrict__ dst_base, long long dst_step, long long dst_frame,
+                                                                                ClaheGeom g, const uint16_t* __restrict__ luts,
+                                                                                const Range16* __restrict__ frame_ranges, int subs, int n_frames,
+                                                                                const Range16* __restrict__ tile_ranges)
+{
+    interp16_mid_body<FMA>(StridedPair{src_base, src_frame, dst_base, dst_frame}, src_step, dst_step, g, luts, frame_ranges, subs, n_frames, tile_ranges);
+}
+template <bool FMA>
+__global__ __launch_bounds__(kInterp16MidThreads) void clahe_interp16_mid_frames_kernel(FrameList l, long long src_step, long long dst_step,
+                                                                                       ClaheGeom g, const uint16_t* __restrict__ luts,
+                                                                                       const Range16* __restrict__ frame_ranges, int subs, int n_frames,
+                                                                                       const Range16* __restrict__ tile_ranges)
+{
+    interp16_mid_body<FMA>(TableFrames{l}, src_step, dst_step, g, luts, frame_ranges, subs, n_frames, tile_ranges);
 }
 
 // IN-PLACE calls, the RECTANGLES whose populated range does not fit one window of a table (rect_owner_in_place; full-range 16-bit
@@ -1194,17 +1254,17 @@ __global__ __launch_bounds__(kInterp16MidThreads) void clahe_interp16_mid_kernel
 // the grid is kept small: grid = (min(items, max(512, 2048 / frames)), 1, frames) workgroups walking (row, 256-pixel block) items in row-major order
 // with stride gridDim.x -- the rows in flight at any moment are neighbours, so the LUTs they gather from (two tile rows) stay in L2
 // (rows strided over the whole image measured 2x slower: all 64 tiles' LUTs in use at once).
-__global__ __launch_bounds__(kThreads) void clahe_interp16_wide_kernel(const uint8_t* __restrict__ src_base, long long src_step, long long src_frame,
-                                                                      uint8_t* __restrict__ dst_base, long long dst_step, long long dst_frame,
-                                                                      ClaheGeom g, const uint16_t* __restrict__ luts,
-                                                                      const Range16* __restrict__ frame_ranges, int mid_runs,
-                                                                      const Range16* __restrict__ tile_ranges)
+template <class Frames>
+__device__ __forceinline__ void interp16_wide_body(const Frames& frames, long long src_step, long long dst_step,
+                                                   const ClaheGeom& g, const uint16_t* __restrict__ luts,
+                                                   const Range16* __restrict__ frame_ranges, int mid_runs,
+                                                   const Range16* __restrict__ tile_ranges)
 {
     const int f = blockIdx.z;
     const Range16 fr = frame_ranges[f];
     const uint32_t sft = range_shift(fr.hi);                        // the LUTs are stored at index value >> sft
-    // a frame whose whole range is one window of a table that runs has no rectangle for this kernel; nor has a call that is not in place
-    if ((range_hi(fr.hi) >> sft) - ((fr.lo >> sft) & ~3u) < (uint32_t)(mid_runs ? kInterp16MidEntries : kInterp16Entries) || src_base != dst_base) return;
+    // a frame whose whole range is one window of a table that runs has no rectangle for this kernel; nor has a frame that is not in place
+    if ((range_hi(fr.hi) >> sft) - ((fr.lo >> sft) & ~3u) < (uint32_t)(mid_runs ? kInterp16MidEntries : kInterp16Entries) || !frames.in_place(f)) return;
     const Range16* tr = tile_ranges + (size_t)f * g.tiles_x * g.tiles_y;
     // Which rectangles -- (tile pair, band) -- are this kernel's?  (rect_owner_in_place on the range of the rectangle's four tiles, as the
     // table kernels compute it.)  Worked out once per workgroup into LDS, one byte per rectangle, so that a pixel costs one LDS read and
@@ -1231,8 +1291,8 @@ __global__ __launch_bounds__(kThreads) void clahe_interp16_wide_kernel(const uin
     const uint16_t* lf = luts + (size_t)f * g.tiles_x * g.tiles_y * kHist16;
     const int bx = (g.width + kThreads - 1) / kThreads;
     const long long items = (long long)bx * g.height;
-    const uint8_t* src = src_base + (long long)f * src_frame;
-    uint8_t* dst = dst_base + (long long)f * dst_frame;
+    const uint8_t* src = frames.src_of(f);
+    uint8_t* dst = frames.dst_of(f);
     constexpr int kChains = 4;                                       // independent pixel -> gather -> store chains per lane and iteration:
     for (long long it0 = blockIdx.x; it0 < items; it0 += (long long)kChains * gridDim.x) {   // the kernel is bound by memory latency
         int xs[kChains], ys[kChains];
@@ -1280,6 +1340,22 @@ __global__ __launch_bounds__(kThreads) void clahe_interp16_wide_kernel(const uin
         }
     }
 }
+__global__ __launch_bounds__(kThreads) void clahe_interp16_wide_kernel(const uint8_t* __restrict__ src_base, long long src_step, long long src_frame,
+                                                                      uint8_t* __restrict__ dst_base, long long dst_step, long long dst_frame,
+                                                                      ClaheGeom g, const uint16_t* __restrict__ luts,
+                                                                      const Range16* __restrict__ frame_ranges, int mid_runs,
+                                                                      const Range16* __restrict__ tile_ranges)
+{
+    interp16_wide_body(StridedPair{src_base, src_frame, dst_base, dst_frame}, src_step, dst_step, g, luts, frame_ranges, mid_runs, tile_ranges);
+}
+// frame lists: launched when some frame of the launch is in place; the workgroups of the others return at once
+__global__ __launch_bounds__(kThreads) void clahe_interp16_wide_frames_kernel(FrameList l, long long src_step, long long dst_step,
+                                                                             ClaheGeom g, const uint16_t* __restrict__ luts,
+                                                                             const Range16* __restrict__ frame_ranges, int mid_runs,
+                                                                             const Range16* __restrict__ tile_ranges)
+{
+    interp16_wide_body(TableFrames{l}, src_step, dst_step, g, luts, frame_ranges, mid_runs, tile_ranges);
+}
 
 // ---- value-major LUT layout for the interpolation ---------------------------------------------------------------
 // The four entries a pixel needs -- LUT[ty1][tx1][v], [ty1][tx2][v], [ty2][tx1][v], [ty2][tx2][v] -- sit in four different
@@ -1306,10 +1382,10 @@ __global__ __launch_bounds__(kThreads) void transpose_lut16_kernel(const uint16_
 }
 
 // as clahe_interp16_kernel, gathering from the value-major layout
-__global__ __launch_bounds__(kThreads) void clahe_interp16T_kernel(const uint8_t* __restrict__ src_base, long long src_step, long long src_frame,
-                                                                  uint8_t* __restrict__ dst_base, long long dst_step, long long dst_frame,
-                                                                  ClaheGeom g, const uint16_t* __restrict__ lutT,
-                                                                  const Range16* __restrict__ frame_ranges, uint32_t* shift_hint)
+template <class Frames>
+__device__ __forceinline__ void interp16T_body(const Frames& frames, long long src_step, long long dst_step,
+                                               const ClaheGeom& g, const uint16_t* __restrict__ lutT,
+                                               const Range16* __restrict__ frame_ranges, uint32_t* shift_hint)
 {
     hint_roll(shift_hint);
     const int f = blockIdx.z, y = blockIdx.y;
@@ -1324,14 +1400,27 @@ __global__ __launch_bounds__(kThreads) void clahe_interp16T_kernel(const uint8_t
     int ty1 = floor_f32_to_int(tyf);
     const float ya = __fsub_rn(tyf, (float)ty1), ya1 = __fsub_rn(1.0f, ya);
     int ty2 = ty1 + 1; ty1 = max(ty1, 0); ty2 = min(ty2, g.tiles_y - 1);
-    const uint32_t v = (uint32_t)*reinterpret_cast<const uint16_t*>(src_base + (long long)f * src_frame + (long long)y * src_step + 2 * (long long)x)
+    const uint32_t v = (uint32_t)*reinterpret_cast<const uint16_t*>(frames.src_of(f) + (long long)y * src_step + 2 * (long long)x)
                        >> range_shift(frame_ranges[f].hi);       // the LUTs are stored at index value >> shift
     const uint16_t* e = lutT + ((size_t)f * kHist16 + v) * tiles;
     const float a = (float)e[ty1 * g.tiles_x + tx1], b = (float)e[ty1 * g.tiles_x + tx2];
     const float c = (float)e[ty2 * g.tiles_x + tx1], d = (float)e[ty2 * g.tiles_x + tx2];
     int r = __float2int_rn(g.contract ? clahe_blend_f<true>(a, b, c, d, xa, xa1, ya, ya1) : clahe_blend_f<false>(a, b, c, d, xa, xa1, ya, ya1));
     r = r < 0 ? 0 : (r > 65535 ? 65535 : r);
-    *reinterpret_cast<uint16_t*>(dst_base + (long long)f * dst_frame + (long long)y * dst_step + 2 * (long long)x) = (uint16_t)r;
+    *reinterpret_cast<uint16_t*>(frames.dst_of(f) + (long long)y * dst_step + 2 * (long long)x) = (uint16_t)r;
+}
+__global__ __launch_bounds__(kThreads) void clahe_interp16T_kernel(const uint8_t* __restrict__ src_base, long long src_step, long long src_frame,
+                                                                  uint8_t* __restrict__ dst_base, long long dst_step, long long dst_frame,
+                                                                  ClaheGeom g, const uint16_t* __restrict__ lutT,
+                                                                  const Range16* __restrict__ frame_ranges, uint32_t* shift_hint)
+{
+    interp16T_body(StridedPair{src_base, src_frame, dst_base, dst_frame}, src_step, dst_step, g, lutT, frame_ranges, shift_hint);
+}
+__global__ __launch_bounds__(kThreads) void clahe_interp16T_frames_kernel(FrameList l, long long src_step, long long dst_step,
+                                                                         ClaheGeom g, const uint16_t* __restrict__ lutT,
+                                                                         const Range16* __restrict__ frame_ranges, uint32_t* shift_hint)
+{
+    interp16T_body(TableFrames{l}, src_step, dst_step, g, lutT, frame_ranges, shift_hint);
 }
 
 }  // namespace mi

@@ -50,7 +50,7 @@ constexpr int kFramesPerLaunch = 64;
 struct FramePlanes { const uint8_t* y_in; const uint8_t* uv_in; uint8_t* y_out; uint8_t* uv_out; };
 struct UVRows {
     long long src_step, dst_step;     // bytes between UV rows
-    long long row_bytes;              // W
+    long long row_bytes;              // W (P010 frames: 2 * W)
     int rows;                         // H / 2; 0 = no UV work
     int mode;                         // 0 = fill 128, 1 = copy
 };
@@ -70,10 +70,20 @@ struct StridedSource {                // the same for kernels that only read: ba
     const long long& frame_stride;
     __device__ __forceinline__ const uint8_t* src_of(long long f) const { return base + f * frame_stride; }
 };
+struct StridedPair {                  // the 16-bit kernels: input and output base pointers and frame strides as separate arguments;
+    const uint8_t* __restrict__ const& src_base;      // the whole launch is in place or not (src_base == dst_base)
+    const long long& src_frame;
+    uint8_t* __restrict__ const& dst_base;
+    const long long& dst_frame;
+    __device__ __forceinline__ const uint8_t* src_of(long long f) const { return src_base + f * src_frame; }
+    __device__ __forceinline__ uint8_t* dst_of(long long f) const { return dst_base + f * dst_frame; }
+    __device__ __forceinline__ bool in_place(long long) const { return src_base == dst_base; }
+};
 struct TableFrames {                  // frame f at the addresses the table holds
     const FrameList& l;
     __device__ __forceinline__ const uint8_t* src_of(long long f) const { return l.f[f].y_in; }
     __device__ __forceinline__ uint8_t* dst_of(long long f) const { return l.f[f].y_out; }
+    __device__ __forceinline__ bool in_place(long long f) const { return l.f[f].y_in == l.f[f].y_out; }   // decided per frame
 };
 
 struct Split16 { long long head, nvec, tail; };

@@ -42,5 +42,6 @@ using namespace mi;
 #include "host/clahe16.inc.hpp"
 #include "host/p010.inc.hpp"            // 16-bit 4:2:0 frames: CLAHE on Y (clahe16) + the chroma kernel
 #include "host/nv12_frames.inc.hpp"     // NV12 frames as a list of pitched plane addresses (decoder surfaces, tensor lists)
+#include "host/p010_frames.inc.hpp"     // P010 frames as such a list (the 16-bit kernels' *_frames_kernel entries)
 #include "host/pipe.inc.hpp"
 #include "host/diff.inc.hpp"

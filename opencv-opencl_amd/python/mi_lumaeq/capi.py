@@ -45,6 +45,7 @@ DECLARED_SYMBOLS = [
     "mi_device_pci_bus_id", "mi_thread_bind_near_device",
     "mi_clahe_p010", "mi_clahe_p010_batch_dev",
     "mi_equalize_hist_nv12_frames_dev", "mi_clahe_nv12_frames_dev",
+    "mi_clahe_p010_frames_dev",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -149,6 +150,7 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_p010_batch_dev.argtypes = [vp, vp, vp, i, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_nv12_frames_dev.argtypes = [vp, C.POINTER(Nv12FrameDev), i, i, i, sz, sz, sz, sz, i, vp]
     L.mi_clahe_nv12_frames_dev.argtypes = [vp, C.POINTER(Nv12FrameDev), i, i, i, sz, sz, sz, sz, i, d, i, i, vp]
+    L.mi_clahe_p010_frames_dev.argtypes = [vp, C.POINTER(Nv12FrameDev), i, i, i, sz, sz, sz, sz, i, d, i, i, vp]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -508,6 +510,15 @@ class Context:
         self._chk(self._L.mi_clahe_p010_batch_dev(self._h, _dptr(d_in), _dptr(d_out), int(width), int(height), int(n_frames),
                                                 int(uv_mode), float(clip_limit), int(tiles_x), int(tiles_y), stream),
                   "mi_clahe_p010_batch_dev")
+
+    def clahe_p010_frames(self, inputs, outputs, width, height, uv_mode=UV_FILL128, clip_limit=2.0, tiles_x=8, tiles_y=8,
+                          y_in_pitch=None, uv_in_pitch=None, y_out_pitch=None, uv_out_pitch=None, stream=0):
+        """mi_clahe_p010_frames_dev: a list of P010 / P012 / P016 frames, each its own pitched (y, uv) planes -- 2-D int16 / uint16 torch
+        CUDA tensors (W samples per row; the row stride in bytes gives the pitch) or raw device addresses; outputs None = in place.
+        A pitch not given is the tensors' row stride, or 2 * W."""
+        arr, n, p = _frame_list(inputs, outputs, 2 * int(width), (y_in_pitch, uv_in_pitch, y_out_pitch, uv_out_pitch), "clahe_p010_frames")
+        self._chk(self._L.mi_clahe_p010_frames_dev(self._h, arr, n, int(width), int(height), p[0], p[1], p[2], p[3], int(uv_mode),
+                                                 float(clip_limit), int(tiles_x), int(tiles_y), stream), "mi_clahe_p010_frames_dev")
 
     # ---- colour-domain neighbours (N3) ----
     @staticmethod
