@@ -256,7 +256,10 @@ mi_status mi_clahe_u16_batch_dev(mi_ctx* ctx, const void* d_src, size_t src_step
  *   see mi_host_register); the chroma half is written on the host while the GPU works on Y.
  * mi_clahe_p010_batch_dev: n_frames frames at a frame pitch of 3*W*H bytes, stream-ordered like the other batched device forms;
  *   d_in == d_out allowed; capturable into a hipGraph after one eager call of the same shape. */
-enum { MI_FMT_NV12 = 0, MI_FMT_P010 = 1 };   /* P010 = any 16-bit LE 4:2:0 semi-planar frame: P010 / P012 / P016 */
+/* MI_FMT_YUY2 / MI_FMT_UYVY: packed 8-bit 4:2:2 frames, see mi_*_packed422* below.  MI_FMT_YUY2 = luma at byte offset 0 of each 2-byte
+ * pixel (YUY2 / YUYV / YVYU: the chroma order is irrelevant, chroma is only copied or filled), MI_FMT_UYVY = luma at byte offset 1
+ * (UYVY / VYUY). */
+enum { MI_FMT_NV12 = 0, MI_FMT_P010 = 1, MI_FMT_YUY2 = 2, MI_FMT_UYVY = 3 };   /* P010 = any 16-bit LE 4:2:0 semi-planar frame: P010 / P012 / P016 */
 mi_status mi_clahe_p010(mi_ctx* ctx, const uint16_t* in, uint16_t* out, int width, int height,
                         mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
 mi_status mi_clahe_p010_batch_dev(mi_ctx* ctx, const void* d_in, void* d_out, int width, int height, int n_frames,
@@ -281,6 +284,45 @@ typedef mi_nv12_frame_dev mi_p010_frame_dev;
 mi_status mi_clahe_p010_frames_dev(mi_ctx* ctx, const mi_p010_frame_dev* frames, int n_frames, int width, int height,
                                    size_t y_in_pitch, size_t uv_in_pitch, size_t y_out_pitch, size_t uv_out_pitch,
                                    mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y, void* stream);
+
+/* ---- equalizeHist and CLAHE on packed 4:2:2 frames: YUY2 / UYVY (what a capture device hands over: v4l2, SDI / HDMI cards) ----------
+ * A frame is H rows of W 2-byte pixels, 2*W bytes per row at `pitch` bytes: macropixels Y0 U Y1 V (MI_FMT_YUY2) or U Y0 V Y1
+ * (MI_FMT_UYVY).  Luma sample (x, y) is byte y * pitch + 2 * x + off, off = 0 (MI_FMT_YUY2) / 1 (MI_FMT_UYVY).  In OpenCV terms: the
+ * Mat(H, W, CV_8UC2, data, pitch) view, cv::extractChannel(frame, y, off), cv::equalizeHist / CLAHE::apply on y, cv::insertChannel.
+ *   luma   : byte for byte what mi_equalize_hist_u8_batch_dev / mi_clahe_u8_batch_dev return on the gathered W x H plane (same
+ *            clahe_fp_contract option, same REFLECT_101 padding when W or H is not divisible by the tile grid), written in place in
+ *            the packed output frame; no plane is gathered or scattered.
+ *   chroma : MI_UV_COPY copies the chroma bytes, MI_UV_FILL128 writes 128.  In place (d_out == d_in, equal pitch and frame stride)
+ *            with MI_UV_COPY leaves them as they are.
+ * Nothing outside the 2*W bytes of each output row is written: not the pitch padding, not the gap between frames.
+ * `width` is even, `height` any value >= 1 (4:2:2 has no vertical subsampling).  Pointers, pitches and frame strides are multiples of
+ * 4 -- a macropixel is always one aligned dword, and an ROI with an even x origin stays legal; 16-byte alignment is NOT required.
+ * pitch >= 2*W.
+ * _batch_dev forms: frame f at base + f * frame_stride; stream rules, MI_STREAM_CTX, hipGraph capture after one eager call of the
+ *   same shape and MI_ERR_BUSY while a pipe has frames pending as the other batched device forms.  These forms never take the fused
+ *   equalizeHist kernel nor the single-launch histogram + LUT kernel (option two_kernel_max_frames does not apply); their launches
+ *   are charged to the profiling slots MI_K_HIST, MI_K_EQ_LUT, MI_K_LUT_APPLY, MI_K_TILE_HIST, MI_K_TILE_LUT, MI_K_CLAHE_INTERP by role.
+ * mi_equalize_hist_packed422 / mi_clahe_packed422: host frames, synchronous, in == out allowed, like mi_equalize_hist_nv12 /
+ *   mi_clahe_nv12 -- except that the whole frame crosses the bus in both directions (there is no luma plane to send on its own) and
+ *   the kernels write the chroma.  Pitched host frames are accepted: only the 2*W bytes of each row are read and written.  Whatever
+ *   the call returns, no copy on in / out is in flight any more when it returns.
+ * Errors, MI_ERR_BAD_ARG: a null ctx or frame pointer, an odd width, a negative size, a pitch < 2*W, a pointer / pitch / frame stride
+ * that is not a multiple of 4, a format other than the two, a bad uv_mode, tiles <= 0.  width, height or n_frames of 0: MI_OK, nothing
+ * written.  Sizes and tile grids beyond what the planar forms accept: what those answer (MI_ERR_UNSUPPORTED).  Partially overlapping
+ * input and output: undefined, as for the other batched forms. */
+mi_status mi_equalize_hist_packed422_batch_dev(mi_ctx* ctx,
+                                               const void* d_in, size_t in_pitch, size_t in_frame_stride,
+                                               void* d_out, size_t out_pitch, size_t out_frame_stride,
+                                               int width, int height, int n_frames, int format, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_packed422_batch_dev(mi_ctx* ctx,
+                                       const void* d_in, size_t in_pitch, size_t in_frame_stride,
+                                       void* d_out, size_t out_pitch, size_t out_frame_stride,
+                                       int width, int height, int n_frames, int format, mi_uv_mode uv_mode,
+                                       double clip_limit, int tiles_x, int tiles_y, void* stream);
+mi_status mi_equalize_hist_packed422(mi_ctx* ctx, const uint8_t* in, size_t in_pitch, uint8_t* out, size_t out_pitch,
+                                     int width, int height, int format, mi_uv_mode uv_mode);
+mi_status mi_clahe_packed422(mi_ctx* ctx, const uint8_t* in, size_t in_pitch, uint8_t* out, size_t out_pitch,
+                             int width, int height, int format, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
 
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at
@@ -342,7 +384,12 @@ mi_status mi_host_unregister(void* ptr);
  *   format     MI_FMT_NV12 (0, the default of a zeroed config) or MI_FMT_P010 (16-bit frames of 3*W*H bytes, see mi_clahe_p010;
  *              in / out are then those frames' bytes).  P010 takes MI_OP_CLAHE only -- the other ops answer MI_ERR_UNSUPPORTED at
  *              mi_pipe_create -- and runs it through the 16-bit path; under MI_PIPE_UV_HOST only Y crosses and the waiting thread
- *              writes the chroma, under MI_PIPE_UV_DEVICE whole frames cross and a kernel writes it.  Default depth by frame bytes. */
+ *              writes the chroma, under MI_PIPE_UV_DEVICE whole frames cross and a kernel writes it.  Default depth by frame bytes.
+ *              MI_FMT_YUY2 / MI_FMT_UYVY: packed 4:2:2 frames of 2*W*H bytes, tight (pitch 2*W), W even, any H (see
+ *              mi_equalize_hist_packed422); MI_OP_EQUALIZE and MI_OP_CLAHE, MI_OP_CHANNELS answers MI_ERR_UNSUPPORTED.  There is no
+ *              luma plane to send on its own: whole frames cross the bus in both directions and the kernels write the chroma --
+ *              that is what MI_PIPE_UV_AUTO and MI_PIPE_UV_DEVICE mean here, MI_PIPE_UV_HOST answers MI_ERR_UNSUPPORTED at
+ *              mi_pipe_create.  Default depth by frame bytes. */
 typedef struct mi_pipe mi_pipe;
 enum { MI_OP_EQUALIZE = 0, MI_OP_CLAHE = 1, MI_OP_CHANNELS = 2 };
 enum { MI_PIPE_UV_AUTO = 0, MI_PIPE_UV_HOST = 1, MI_PIPE_UV_DEVICE = 2 };
@@ -354,7 +401,7 @@ typedef struct mi_pipe_config {
     int tiles_x, tiles_y;        /* MI_OP_CLAHE */
     int depth;
     int uv_policy;
-    int format;                  /* MI_FMT_NV12 | MI_FMT_P010 (appended in 0.3: keep it the last member) */
+    int format;                  /* MI_FMT_NV12 | MI_FMT_P010 | MI_FMT_YUY2 | MI_FMT_UYVY (appended in 0.3: keep it the last member) */
 } mi_pipe_config;
 mi_status mi_pipe_create(mi_ctx* ctx, const mi_pipe_config* cfg, mi_pipe** out);
 void      mi_pipe_destroy(mi_pipe* pipe);

@@ -29,7 +29,8 @@
 // UV handling: "host" (default for Y-only ops) moves only the Y plane over the bus and fills / copies the UV half on the
 // host inside mi_pipe_wait while the engines are busy; "device" ships whole NV12 frames and lets the kernels do it.
 // Format: NV12 (8-bit) or P010 (16-bit samples, any of P010 / P012 / P016: the same layout with every size doubled; CLAHE only,
-// through the 16-bit path, and the chroma half is 0x8000-filled / copied by mi_host::p010_chroma or p010_uv_kernel).
+// through the 16-bit path, and the chroma half is 0x8000-filled / copied by mi_host::p010_chroma or p010_uv_kernel), or packed 4:2:2
+// (YUY2 / UYVY, 2*W*H bytes: whole frames cross in both directions, host/packed422.inc.hpp runs the op and writes the chroma).
 
 struct PipeSlot {
     int lane = 0;                                                 // which of the two copy streams per direction carries this frame
@@ -87,6 +88,11 @@ mi_status pipe_run_op(mi_pipe* p, PipeSlot& sl)
     mi_ctx* c = p->c;
     const mi_pipe_config& g = p->cfg;
     const size_t fstride = p->ybytes + p->uvbytes;
+    if (g.format == MI_FMT_YUY2 || g.format == MI_FMT_UYVY) {     // packed 4:2:2: the whole frame, luma in place, chroma by the same kernels
+        const size_t row = (size_t)g.width * 2;
+        const P422Args a{sl.d_in, row, fstride, sl.d_out, row, fstride, g.width, g.height, 1, g.format, g.uv_mode};
+        return packed422_dev(c, p->s_k, a, g.op == MI_OP_CLAHE ? 1 : 0, g.clip_limit, g.tiles_x, g.tiles_y);
+    }
     if (g.op == MI_OP_CHANNELS) return nv12_bgr_equalize_dev(c, p->s_k, sl.d_in, fstride, sl.d_out, fstride, g.width, g.height, 1);
     if (g.format == MI_FMT_P010) {                                // 16-bit frames: CLAHE on the 2W-pitch Y plane, the chroma kernel when asked
         mi_status st = clahe16_dev(c, p->s_k, sl.d_in, (size_t)g.width * 2, fstride, sl.d_out, (size_t)g.width * 2, fstride, g.width, g.height, 1,
@@ -163,8 +169,10 @@ mi_status mi_pipe_create(mi_ctx* c, const mi_pipe_config* cfg, mi_pipe** out)
     if (!cfg || !out) return fail(c, MI_ERR_BAD_ARG, "null config / out");
     *out = nullptr;
     if (cfg->width <= 0 || cfg->height <= 0) return fail(c, MI_ERR_BAD_ARG, "pipe needs a positive frame size");
-    if ((cfg->width & 1) || (cfg->height & 1)) return fail(c, MI_ERR_BAD_ARG, "NV12 / P010 frames have even width and height");
-    if (cfg->format != MI_FMT_NV12 && cfg->format != MI_FMT_P010) return fail(c, MI_ERR_BAD_ARG, "bad format");
+    const bool packed = cfg->format == MI_FMT_YUY2 || cfg->format == MI_FMT_UYVY;
+    if (!packed && cfg->format != MI_FMT_NV12 && cfg->format != MI_FMT_P010) return fail(c, MI_ERR_BAD_ARG, "bad format");
+    if (packed && (cfg->width & 1)) return fail(c, MI_ERR_BAD_ARG, "packed 4:2:2 frames have an even width");
+    if (!packed && ((cfg->width & 1) || (cfg->height & 1))) return fail(c, MI_ERR_BAD_ARG, "NV12 / P010 frames have even width and height");
     if ((long long)cfg->width * cfg->height > 0x7fffffffLL / 3) return fail(c, MI_ERR_UNSUPPORTED, "frame too large");
     if (cfg->op != MI_OP_EQUALIZE && cfg->op != MI_OP_CLAHE && cfg->op != MI_OP_CHANNELS) return fail(c, MI_ERR_BAD_ARG, "bad op");
     // equalizeHist has no 16-bit form in OpenCV (it asserts CV_8UC1): P010 frames take CLAHE only
@@ -172,18 +180,22 @@ mi_status mi_pipe_create(mi_ctx* c, const mi_pipe_config* cfg, mi_pipe** out)
     if (cfg->uv_mode != MI_UV_FILL128 && cfg->uv_mode != MI_UV_COPY) return fail(c, MI_ERR_BAD_ARG, "bad uv_mode");
     if (cfg->op == MI_OP_CLAHE && (cfg->tiles_x <= 0 || cfg->tiles_y <= 0)) return fail(c, MI_ERR_BAD_ARG, "tile grid must be >= 1x1");
     if (cfg->uv_policy < MI_PIPE_UV_AUTO || cfg->uv_policy > MI_PIPE_UV_DEVICE) return fail(c, MI_ERR_BAD_ARG, "bad uv_policy");
+    // packed 4:2:2 frames have no luma plane to send on its own and no per-channel form
+    if (packed && cfg->op == MI_OP_CHANNELS) return fail(c, MI_ERR_UNSUPPORTED, "packed 4:2:2 frames: MI_OP_EQUALIZE and MI_OP_CLAHE only");
+    if (packed && cfg->uv_policy == MI_PIPE_UV_HOST) return fail(c, MI_ERR_UNSUPPORTED, "packed 4:2:2 frames: the kernels write the chroma (MI_PIPE_UV_AUTO / MI_PIPE_UV_DEVICE)");
     if (c->pipes_open > 0) return fail(c, MI_ERR_BUSY, "this context already has a pipe: one pipe per context (the pipe uses the context's scratch)");
     mi_pipe* p = new (std::nothrow) mi_pipe();
     if (!p) return fail(c, MI_ERR_OOM, "pipe allocation failed");
     p->c = c; p->cfg = *cfg;
     // NV12: W*H luma bytes + W*H/2 chroma bytes; P010: twice both (16-bit samples)
-    p->ybytes = (size_t)cfg->width * cfg->height * (cfg->format == MI_FMT_P010 ? 2 : 1); p->uvbytes = p->ybytes / 2;
+    // packed 4:2:2: 2*W*H bytes, all of them "luma" as far as the transfers are concerned
+    p->ybytes = (size_t)cfg->width * cfg->height * (cfg->format == MI_FMT_NV12 ? 1 : 2); p->uvbytes = packed ? 0 : p->ybytes / 2;
     // Default depth by frame size (profiles/r04_t_*, r04_u_*): one thread that submits and waits on 4K frames is fastest with THREE in
     // flight (5.44-5.59 k frames/s; four: 4.74-4.81 k, two: 3.8-4.3 k -- a fourth frame only deepens the copy lanes' queues), while
     // 1080p frames, bound by their per-frame launch sequence, want more (six: 17.2 k, four: 15.8 k, three: 13.0 k through the pool)
     p->cfg.depth = cfg->depth > 0 ? std::max(2, std::min(16, cfg->depth)) : (p->ybytes + p->uvbytes >= ((size_t)8 << 20) ? 3 : 6);
     // the channel op needs chroma on the device; otherwise the UV half stays on the host unless asked for
-    p->uv_dev = cfg->op == MI_OP_CHANNELS || cfg->uv_policy == MI_PIPE_UV_DEVICE;
+    p->uv_dev = cfg->op == MI_OP_CHANNELS || cfg->uv_policy == MI_PIPE_UV_DEVICE || packed;
     p->xfer_in = p->ybytes + ((p->uv_dev && (cfg->op == MI_OP_CHANNELS || cfg->uv_mode == MI_UV_COPY)) ? p->uvbytes : 0);
     p->xfer_out = p->ybytes + (p->uv_dev ? p->uvbytes : 0);
     auto bail = [&](mi_status st) { pipe_free(p); return st; };

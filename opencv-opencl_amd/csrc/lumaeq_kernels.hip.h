@@ -30,6 +30,7 @@
 //   kernels/color_clahe.hip.h     CLAHE on the luma of interleaved BGR in two passes (N3)
 //   kernels/diff.hip.h            absdiff + analyzeDiff: the reference's own device-vs-CPU check (1frameMeasure.cpp:91-100)
 //   kernels/p010.hip.h            chroma half of 16-bit 4:2:0 frames (P010 / P012 / P016): copy or fill 0x8000
+//   kernels/packed422.hip.h       the pixel-touching stages on packed 4:2:2 frames (YUY2 / UYVY): luma at a 2-byte sample stride
 #pragma once
 #include "kernels/common.hip.h"
 #include "kernels/equalize.hip.h"
@@ -40,3 +41,4 @@
 #include "kernels/color_clahe.hip.h"
 #include "kernels/diff.hip.h"
 #include "kernels/p010.hip.h"
+#include "kernels/packed422.hip.h"

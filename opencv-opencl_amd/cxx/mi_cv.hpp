@@ -438,6 +438,25 @@ inline void claheNV12(const unsigned char* in, unsigned char* out, int width, in
     detail::check(c, mi_clahe_nv12(c, in, out, width, height, (mi_uv_mode)uv, clipLimit, tiles.width, tiles.height), "mi_clahe_nv12");
 }
 
+// Packed 4:2:2 frames from a capture device (YUY2 / UYVY): rows of 2*W bytes at `pitch` (>= 2*W, a multiple of 4) in host memory.
+// cv::extractChannel + equalizeHist / CLAHE::apply + cv::insertChannel on the CV_8UC2 view, without the two extra passes: the luma
+// is equalized in place in the frame, the chroma copied or set to 128.  in == out is allowed.
+enum PackedFormat { FMT_YUY2 = MI_FMT_YUY2, FMT_UYVY = MI_FMT_UYVY };
+inline void equalizeHistPacked422(const unsigned char* in, size_t inPitch, unsigned char* out, size_t outPitch, int width, int height,
+                                  PackedFormat format, UVMode uv)
+{
+    mi_ctx* c = detail::thread_ctx();
+    detail::check(c, mi_equalize_hist_packed422(c, in, inPitch, out, outPitch, width, height, (int)format, (mi_uv_mode)uv),
+                  "mi_equalize_hist_packed422");
+}
+inline void clahePacked422(const unsigned char* in, size_t inPitch, unsigned char* out, size_t outPitch, int width, int height,
+                           PackedFormat format, UVMode uv, double clipLimit, Size tiles)
+{
+    mi_ctx* c = detail::thread_ctx();
+    detail::check(c, mi_clahe_packed422(c, in, inPitch, out, outPitch, width, height, (int)format, (mi_uv_mode)uv, clipLimit,
+                                        tiles.width, tiles.height), "mi_clahe_packed422");
+}
+
 // BASELINE.json config 5 read literally: cvtColor(COLOR_YUV2BGR_NV12) -> split -> equalizeHist on B, G and R -> merge ->
 // cvtColor(COLOR_BGR2YUV_I420) + U/V interleave, NV12 in -> NV12 out in one call (no file of the reference does this;
 // ColoropenCVCwqualHist.cpp itself is equalizeHistNV12(..., UV_COPY)).  Width and height must be even.

@@ -24,6 +24,7 @@ COLOR_YUV2BGR_NV12, COLOR_BGR2YUV_I420 = 93, 128
 OP_EQUALIZE, OP_CLAHE, OP_CHANNELS = 0, 1, 2
 PIPE_UV_AUTO, PIPE_UV_HOST, PIPE_UV_DEVICE = 0, 1, 2
 FMT_NV12, FMT_P010 = 0, 1              # MI_FMT_*: P010 = any 16-bit LE 4:2:0 semi-planar frame (P010 / P012 / P016)
+FMT_YUY2, FMT_UYVY = 2, 3              # packed 8-bit 4:2:2: luma at byte 0 (YUY2 / YUYV / YVYU) or byte 1 (UYVY / VYUY) of each 2-byte pixel
 ERR_BUSY = 6
 
 # every extern "C" symbol include/mi_lumaeq.h declares (tests check the .so exports them all)
@@ -46,6 +47,7 @@ DECLARED_SYMBOLS = [
     "mi_clahe_p010", "mi_clahe_p010_batch_dev",
     "mi_equalize_hist_nv12_frames_dev", "mi_clahe_nv12_frames_dev",
     "mi_clahe_p010_frames_dev",
+    "mi_equalize_hist_packed422_batch_dev", "mi_clahe_packed422_batch_dev", "mi_equalize_hist_packed422", "mi_clahe_packed422",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -151,6 +153,10 @@ def _load(p: Path) -> C.CDLL:
     L.mi_equalize_hist_nv12_frames_dev.argtypes = [vp, C.POINTER(Nv12FrameDev), i, i, i, sz, sz, sz, sz, i, vp]
     L.mi_clahe_nv12_frames_dev.argtypes = [vp, C.POINTER(Nv12FrameDev), i, i, i, sz, sz, sz, sz, i, d, i, i, vp]
     L.mi_clahe_p010_frames_dev.argtypes = [vp, C.POINTER(Nv12FrameDev), i, i, i, sz, sz, sz, sz, i, d, i, i, vp]
+    L.mi_equalize_hist_packed422_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, vp]
+    L.mi_clahe_packed422_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_packed422.argtypes = [vp, vp, sz, vp, sz, i, i, i, i]
+    L.mi_clahe_packed422.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, d, i, i]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -520,6 +526,62 @@ class Context:
         self._chk(self._L.mi_clahe_p010_frames_dev(self._h, arr, n, int(width), int(height), p[0], p[1], p[2], p[3], int(uv_mode),
                                                  float(clip_limit), int(tiles_x), int(tiles_y), stream), "mi_clahe_p010_frames_dev")
 
+    # ---- packed 4:2:2 frames: YUY2 / UYVY (capture devices) ----
+    @staticmethod
+    def _packed_host(a, width, name):
+        a = _host2d(a, name)
+        if a.shape[1] < 2 * width:
+            raise MiError(1, name, "a packed 4:2:2 frame is an H x pitch-bytes uint8 array with at least 2*W bytes per row")
+        return a
+
+    def equalize_hist_packed422(self, frame: np.ndarray, width: int, fmt: int = FMT_YUY2, uv_mode: int = UV_COPY,
+                                out: np.ndarray | None = None) -> np.ndarray:
+        """mi_equalize_hist_packed422 on a host frame: an H x pitch-bytes uint8 array (pitch = the row stride, >= 2*W; a view with
+        padded rows is fine).  `out` may be `frame` (in place); otherwise a new tight H x 2W array is returned."""
+        frame = self._packed_host(frame, width, "equalize_hist_packed422")
+        h = frame.shape[0]
+        if out is None:
+            out = np.empty((h, 2 * width), np.uint8)
+        out = self._packed_host(out, width, "equalize_hist_packed422")
+        self._chk(self._L.mi_equalize_hist_packed422(self._h, frame.ctypes.data, _step(frame), out.ctypes.data, _step(out),
+                                                   int(width), int(h), int(fmt), int(uv_mode)), "mi_equalize_hist_packed422")
+        return out
+
+    def clahe_packed422(self, frame: np.ndarray, width: int, fmt: int = FMT_YUY2, uv_mode: int = UV_COPY, clip_limit: float = 2.0,
+                        tiles_x: int = 8, tiles_y: int = 8, out: np.ndarray | None = None) -> np.ndarray:
+        """mi_clahe_packed422; arguments as equalize_hist_packed422, plus the CLAHE parameters."""
+        frame = self._packed_host(frame, width, "clahe_packed422")
+        h = frame.shape[0]
+        if out is None:
+            out = np.empty((h, 2 * width), np.uint8)
+        out = self._packed_host(out, width, "clahe_packed422")
+        self._chk(self._L.mi_clahe_packed422(self._h, frame.ctypes.data, _step(frame), out.ctypes.data, _step(out), int(width), int(h),
+                                           int(fmt), int(uv_mode), float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_packed422")
+        return out
+
+    def equalize_hist_packed422_batch_dev(self, d_in, d_out, width, height, n_frames, fmt=FMT_YUY2, uv_mode=UV_COPY,
+                                          in_pitch=None, in_frame=None, out_pitch=None, out_frame=None, stream=0):
+        """mi_equalize_hist_packed422_batch_dev: n_frames packed frames in device memory (torch tensors or raw addresses); pitches
+        default to 2*W, frame strides to pitch * H; d_out may be d_in (in place)."""
+        ip = 2 * width if in_pitch is None else in_pitch
+        op = 2 * width if out_pitch is None else out_pitch
+        fi = ip * height if in_frame is None else in_frame
+        fo = op * height if out_frame is None else out_frame
+        self._chk(self._L.mi_equalize_hist_packed422_batch_dev(self._h, _dptr(d_in), ip, fi, _dptr(d_out), op, fo, int(width), int(height),
+                                                             int(n_frames), int(fmt), int(uv_mode), stream),
+                  "mi_equalize_hist_packed422_batch_dev")
+
+    def clahe_packed422_batch_dev(self, d_in, d_out, width, height, n_frames, fmt=FMT_YUY2, uv_mode=UV_COPY, clip_limit=2.0,
+                                  tiles_x=8, tiles_y=8, in_pitch=None, in_frame=None, out_pitch=None, out_frame=None, stream=0):
+        """mi_clahe_packed422_batch_dev; arguments as equalize_hist_packed422_batch_dev, plus the CLAHE parameters."""
+        ip = 2 * width if in_pitch is None else in_pitch
+        op = 2 * width if out_pitch is None else out_pitch
+        fi = ip * height if in_frame is None else in_frame
+        fo = op * height if out_frame is None else out_frame
+        self._chk(self._L.mi_clahe_packed422_batch_dev(self._h, _dptr(d_in), ip, fi, _dptr(d_out), op, fo, int(width), int(height),
+                                                     int(n_frames), int(fmt), int(uv_mode), float(clip_limit), int(tiles_x),
+                                                     int(tiles_y), stream), "mi_clahe_packed422_batch_dev")
+
     # ---- colour-domain neighbours (N3) ----
     @staticmethod
     def _host3(a, name):
@@ -630,7 +692,8 @@ class Context:
 
 class Pipe:
     """mi_pipe wrapper: asynchronous in-order frame pipeline on one context.  NV12 (format=FMT_NV12): numpy uint8 arrays of W*H*3/2
-    bytes; P010 (format=FMT_P010, op=OP_CLAHE): contiguous uint16 arrays of W*H*3/2 samples, e.g. shape (3H/2, W).
+    bytes; P010 (format=FMT_P010, op=OP_CLAHE): contiguous uint16 arrays of W*H*3/2 samples, e.g. shape (3H/2, W); packed 4:2:2
+    (format=FMT_YUY2 / FMT_UYVY): contiguous uint8 arrays of 2*W*H bytes, e.g. shape (H, 2W).
     The arrays handed to submit() are kept alive until wait() returns them."""
 
     def __init__(self, ctx: Context, width: int, height: int, op: int = OP_EQUALIZE, uv_mode: int = UV_FILL128,
@@ -644,7 +707,10 @@ class Pipe:
         ctx._chk(self._ctx._L.mi_pipe_create(ctx._h, C.byref(cfg), C.byref(self._h)), "mi_pipe_create")
         self.format = int(format)
         self._dtype = np.uint16 if self.format == FMT_P010 else np.uint8
-        self.frame_bytes = width * height * 3 // 2 * np.dtype(self._dtype).itemsize
+        if self.format in (FMT_YUY2, FMT_UYVY):
+            self.frame_bytes = 2 * width * height
+        else:
+            self.frame_bytes = width * height * 3 // 2 * np.dtype(self._dtype).itemsize
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -670,7 +736,7 @@ class Pipe:
         """False when the pipe is full (MI_ERR_BUSY: call wait() first)."""
         for a in (frame_in, frame_out):
             if not isinstance(a, np.ndarray) or a.dtype != self._dtype or not a.flags.c_contiguous or a.nbytes < self.frame_bytes:
-                raise MiError(1, "mi_pipe_submit", "frames must be contiguous uint8 (NV12) / uint16 (P010) arrays of W*H*3/2 samples")
+                raise MiError(1, "mi_pipe_submit", "frames must be contiguous uint8 (NV12, packed 4:2:2) / uint16 (P010) arrays of a whole frame")
         rc = self._ctx._L.mi_pipe_submit(self._h, frame_in.ctypes.data, frame_out.ctypes.data, int(tag))
         if rc == ERR_BUSY:
             return False

@@ -3,7 +3,8 @@
 Y distributions:  D1 uniform bytes | D2 "natural low-contrast" (gradient + triangular noise,
 clamped to [16,200], ~60 populated bins) | D3 constant 128 | D4 two-valued 16/235 checkerboard |
 D5 full horizontal ramp.  UV plane: uniform bytes from seed ^ 0xA5A5 (so passthrough vs 128-fill
-is checkable).  seed = 0x5EED0000 + frame_index.  p010_frame(): the 16-bit 4:2:0 counterpart (P010 / P012 / P016 content).
+is checkable).  seed = 0x5EED0000 + frame_index.  p010_frame(): the 16-bit 4:2:0 counterpart (P010 / P012 / P016 content);
+packed422_frame(): the same luma interleaved with hashed chroma as a YUY2 / UYVY frame.
 """
 from __future__ import annotations
 
@@ -110,6 +111,18 @@ def uv_plane(width: int, height: int, frame_index: int = 0) -> np.ndarray:
 
 def nv12_frame(width: int, height: int, dist: str = "D1", frame_index: int = 0) -> np.ndarray:
     return np.concatenate([y_plane(width, height, dist, frame_index).reshape(-1), uv_plane(width, height, frame_index)])
+
+
+def packed422_frame(width: int, height: int, fmt: int = 2, dist: str = "D1", frame_index: int = 0) -> np.ndarray:
+    """A seeded packed 4:2:2 frame, shape (H, 2W) uint8: y_plane(width, height, dist, frame_index) at byte offset 0 of every 2-byte
+    pixel (fmt = 2, MI_FMT_YUY2) or 1 (fmt = 3, MI_FMT_UYVY), counter-hash chroma (seed ^ 0xA5A5, as the NV12 frames) at the other."""
+    if fmt not in (2, 3):
+        raise ValueError(f"packed422_frame: fmt must be 2 (YUY2) or 3 (UYVY), not {fmt!r}")
+    off = fmt - 2
+    out = np.empty((height, 2 * width), np.uint8)
+    out[:, off::2] = y_plane(width, height, dist, frame_index)
+    out[:, 1 - off::2] = random_bytes(width * height, frame_seed(frame_index) ^ 0xA5A5).reshape(height, width)
+    return out
 
 
 P010_CONTENT = {"p010": (10, 6), "p012": (12, 4), "p016": (16, 0)}      # luma bits, shift into the high bits of the word
