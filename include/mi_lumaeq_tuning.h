@@ -17,6 +17,11 @@
 #define MI_OPT_FUSED_VPT           "fused_vpt"           /* 8 / 16 / 20 / 24 (0 = default 20): 16-byte vectors a thread keeps in
                                                            * registers between the histogram and the apply pass (slice = 256 x VPT x 16 B) */
 #define MI_OPT_FUSED_ACQUIRE       "fused_acquire"       /* 1/0, default 1: agent-scope acquire before a consumer reads the LUT       */
+#define MI_OPT_FUSED_CACHE_POLICY  "fused_cache_policy"  /* 0 / 1 / 2, default 0: cache policy of the bytes the kernel touches once (Y loads,
+                                                           * Y' stores, UV tickets; never the hand-off words).  1 = plain loads and stores,
+                                                           * 2 = the streaming policy, 0 = streaming when the launch loads and stores more
+                                                           * bytes than the caches can keep until the next launch, plain below that.
+                                                           * Statistic "fused_last_policy" reads back what the last launch ran with      */
 
 /* equalizeHist on few frames */
 #define MI_OPT_TWO_KERNEL_MAX      "two_kernel_max_frames" /* 0..64, default 8: calls of up to this many frames (twice as many when a frame is
@@ -55,7 +60,7 @@
 #define MI_OPT_PIPE_COPY_STREAMS   "pipe_copy_streams"   /* 1 / 2, default 2: copy streams per direction of a pipe created afterwards:
                                                            * consecutive frames alternate between them                                */
 /* The same knobs from the environment, read by mi_ctx_create (for A/B runs of unmodified programs):
- * MI_LUMAEQ_FUSED, MI_LUMAEQ_FUSED_WGS_PER_CU, MI_LUMAEQ_FUSED_VPT, MI_LUMAEQ_FUSED_ACQUIRE, MI_LUMAEQ_HOST_COPY_THREADS,
+ * MI_LUMAEQ_FUSED, MI_LUMAEQ_FUSED_WGS_PER_CU, MI_LUMAEQ_FUSED_VPT, MI_LUMAEQ_FUSED_ACQUIRE, MI_LUMAEQ_FUSED_CACHE_POLICY, MI_LUMAEQ_HOST_COPY_THREADS,
  * MI_LUMAEQ_HOST_COPY_STREAMS, MI_LUMAEQ_PIPE_COPY_STREAMS. */
 
 #endif /* MI_LUMAEQ_TUNING_H_ */

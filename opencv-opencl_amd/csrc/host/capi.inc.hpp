@@ -146,6 +146,7 @@ mi_status mi_ctx_create(int device, mi_ctx** out)
     if (const char* e = getenv("MI_LUMAEQ_FUSED_WGS_PER_CU")) c->fused_wgs_per_cu = std::max(1, std::min(8, atoi(e)));
     if (const char* e = getenv("MI_LUMAEQ_FUSED_VPT")) { const int v = atoi(e); if (v == 8 || v == 16 || v == 20 || v == 24) c->fused_vpt = v; }
     if (const char* e = getenv("MI_LUMAEQ_FUSED_ACQUIRE")) c->fused_acquire = atoi(e) != 0;
+    if (const char* e = getenv("MI_LUMAEQ_FUSED_CACHE_POLICY")) { const int v = atoi(e); if (fused_cache_policy_known(v)) c->fused_cache_policy = v; }
     if (const char* e = getenv("MI_LUMAEQ_PIPE_COPY_STREAMS")) c->pipe_copy_streams = atoi(e) > 1 ? 2 : 1;      // A/B runs of nv12_stream
     if (const char* e = getenv("MI_LUMAEQ_PIPE_PRIVATE_STREAMS")) c->pipe_private_streams = atoi(e) != 0;
     if (const char* e = getenv("MI_LUMAEQ_HOST_COPY_STREAMS")) c->host_copy_streams = atoi(e) > 1 ? 2 : 1;
@@ -288,6 +289,11 @@ mi_status mi_ctx_set_option(mi_ctx* c, const char* name, int value)
     if (!strcmp(name, "fused_vpt") && value == 0) { c->fused_vpt = kVPT; return MI_OK; }
     if (!strcmp(name, "fused_vpt")) { if (value != 8 && value != 16 && value != 20 && value != 24) return fail(c, MI_ERR_BAD_ARG, "fused_vpt must be 0 (default), 8, 16, 20 or 24"); c->fused_vpt = value; return MI_OK; }
     if (!strcmp(name, "fused_acquire")) { c->fused_acquire = value != 0; return MI_OK; }
+    if (!strcmp(name, "fused_cache_policy")) {
+        if (!fused_cache_policy_known(value)) return fail(c, MI_ERR_BAD_ARG, "fused_cache_policy must be 0 (by size), 1 (plain) or 2 (streaming)");
+        c->fused_cache_policy = value;
+        return MI_OK;
+    }
     if (!strcmp(name, "bgr_fused")) { c->bgr_fused = value != 0; return MI_OK; }
     if (!strcmp(name, "clahe_hist_threads")) { if (value != 256 && value != 512) return fail(c, MI_ERR_BAD_ARG, "clahe_hist_threads must be 256 or 512"); c->clahe_hist_threads = value; return MI_OK; }
     if (!strcmp(name, "clahe_tiles_per_wg")) { if (value < 0 || value > 8) return fail(c, MI_ERR_BAD_ARG, "clahe_tiles_per_wg must be 0..8"); c->clahe_tiles_per_wg = value; return MI_OK; }
@@ -336,7 +342,9 @@ mi_status mi_ctx_synchronize(mi_ctx* c, void* stream)
 // stream the work ran on has been synchronised.  Host-side counters: "fused_demotions" (times the context gave the fused path up
 // for a while after repeated repairs), "fused_demoted" (1 while it is given up), "error_drains" (error exits that had to wait for
 // a stream before returning), "host_copies_shared" (staging copies the helper thread took half of), "clahe16_mid_launches" (16-bit
-// CLAHE calls that launched clahe_interp16_mid_kernel: by the pinned-memory hint, or always / never by option "clahe16_wide").
+// CLAHE calls that launched clahe_interp16_mid_kernel: by the pinned-memory hint, or always / never by option "clahe16_wide"),
+// "fused_last_policy" (cache-policy code of the last fused launch this context made, see equalize_fused_kernel; all ones before the first),
+// "fused_stream_min_bytes" (bytes a launch loads and stores from which fused_cache_policy = 0 chooses the streaming policy).
 mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
 {
     ENTER(c);
@@ -348,6 +356,8 @@ mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
     if (!strcmp(name, "host_planes_direct")) { *out = c->planes_direct; return MI_OK; }
     if (!strcmp(name, "host_copies_shared")) { *out = c->crew ? c->crew->shared_jobs() : 0; return MI_OK; }
     if (!strcmp(name, "clahe16_mid_launches")) { *out = c->c16_mid_launches; return MI_OK; }
+    if (!strcmp(name, "fused_last_policy")) { *out = (uint64_t)(int64_t)c->fused_last_policy; return MI_OK; }
+    if (!strcmp(name, "fused_stream_min_bytes")) { *out = (uint64_t)kFusedStreamMinBytes; return MI_OK; }
     static const char* names[4] = {"fused_fallbacks", "fused_frames_repaired", "fused_hard_errors", "fused_last_status"};
     for (int k = 0; k < 4; ++k)
         if (!strcmp(name, names[k])) {

@@ -122,6 +122,8 @@ struct mi_ctx {
     int fused_wgs_per_cu = 4;                                    // MI_LUMAEQ_FUSED_WGS_PER_CU
     int fused_vpt = kVPT;                                        // MI_LUMAEQ_FUSED_VPT (8, 16, 20, 24)
     int fused_acquire = 1;                                       // MI_LUMAEQ_FUSED_ACQUIRE
+    int fused_cache_policy = 0;                                  // option "fused_cache_policy": 0 = by the launch's bytes, 1 = plain, 2 = streaming
+    int fused_last_policy = -1;                                  // statistic "fused_last_policy": POL of the last fused launch (-1: none yet)
 #ifdef MI_TEST_HOOKS                                             // libmi_lumaeq_test.so only (csrc/Makefile): the product library has neither
     int fused_fault_inject = 0;                                  // option "fused_fault_inject": 0 off, 1..3 see kernels/equalize_fused.hip.h
     int fused_timeout_us = 0;                                    // option "fused_timeout_us": > 0 overrides fused_timeout_ms

@@ -95,6 +95,74 @@ bool fused_admit(mi_ctx* c)
     return true;
 }
 
+// ---- cache policy of the streamed bytes ---------------------------------------------------------------------
+// The fused kernel loads every Y byte once and never reads back what it stores, so to the caches its streams are pure
+// pollution -- provided nothing else finds them there.  A caller that runs the next launch (or its own next stage) over the
+// same frames does find them when the launch is small: everything a launch touches then still sits in the 256 MiB Infinity
+// Cache, and policy bits that keep lines out of the caches make that replay slower.  So the policy is a property of the
+// launch: kFusedPolStream when it loads and stores at least kFusedStreamMinBytes, plain below.
+// Option "fused_cache_policy" forces one (1 = plain, 2 = streaming); a library built with -DMI_FUSED_POLICY_MATRIX
+// (`make ab`: tools/fused_ab.py only) also takes 100 + POL for every policy of the matrix, with the default slice size.
+constexpr int kFusedPolPlain = 0;
+// Measured (profiles/r11_fused_cache_policy_matrix.txt: the 18 / 36 policies, one process, legs alternating, 200 launches a leg,
+// kernel time by the dispatch events): non-temporal Y loads AND Y' stores with the UV tickets left plain take 0.912 of the plain
+// kernel's time on 64 x 4K, 0.910 on 256 x 1080p, 0.984 with MI_UV_COPY; either half alone is worth 0.4-4 %, sc1 stores lose.
+// Over frame counts the same policy is 3.4 % SLOWER at 12 x 4K (237 MiB loaded and stored: the replay still finds the frames in the
+// 256 MiB Infinity Cache), 1 % faster at 32 x 1080p (158 MiB, inside the noise), 3.4 % faster at 16 x 4K and 5.3 % at 64 x 1080p
+// (316 MiB both), 9-13 % from 475 MiB up.  The threshold sits between the last loss and the first win.
+constexpr int kFusedPolStream = fused_pol(/*Y loads nt*/ 1, /*Y' stores nt*/ 1, /*UV stores plain*/ 0, /*UV loads plain*/ 0);
+constexpr long long kFusedStreamMinBytes = 300LL << 20;
+
+bool fused_cache_policy_known(int v)
+{
+    if (v >= 0 && v <= 2) return true;
+#ifdef MI_FUSED_POLICY_MATRIX
+    if (v >= 100 && fused_pol_valid(v - 100)) return true;
+#endif
+    return false;
+}
+
+int fused_pick_policy(const mi_ctx* c, long long launch_bytes)
+{
+    switch (c->fused_cache_policy) {
+        case 0: return launch_bytes >= kFusedStreamMinBytes ? kFusedPolStream : kFusedPolPlain;
+        case 1: return kFusedPolPlain;
+        case 2: return kFusedPolStream;
+        default: return c->fused_cache_policy - 100;             // matrix builds only (fused_cache_policy_known)
+    }
+}
+
+template <int POL>
+mi_status fused_launch(mi_ctx* c, hipStream_t s, int vpt, unsigned grid, const FusedJob& j)
+{
+    switch (vpt) {
+        case 8:  LAUNCH(c, s, MI_K_FUSED, (equalize_fused_kernel<8, POL>), dim3(grid), dim3(kThreads), 0, j); break;
+        case 20: LAUNCH(c, s, MI_K_FUSED, (equalize_fused_kernel<20, POL>), dim3(grid), dim3(kThreads), 0, j); break;
+        case 24: LAUNCH(c, s, MI_K_FUSED, (equalize_fused_kernel<24, POL>), dim3(grid), dim3(kThreads), 0, j); break;
+        case 16: LAUNCH(c, s, MI_K_FUSED, (equalize_fused_kernel<16, POL>), dim3(grid), dim3(kThreads), 0, j); break;
+        default: return fail(c, MI_ERR_BAD_ARG, "bad fused_vpt");
+    }
+    return MI_OK;
+}
+
+#ifdef MI_FUSED_POLICY_MATRIX
+template <int POL>
+mi_status fused_launch_matrix(mi_ctx* c, hipStream_t s, int vpt, unsigned grid, const FusedJob& j, int pol)
+{
+    if constexpr (POL >= 64) return fail(c, MI_ERR_BAD_ARG, "bad fused_cache_policy");
+    else {
+        if constexpr (fused_pol_valid(POL) && POL != kFusedPolPlain && POL != kFusedPolStream) {
+            if (pol == POL) {
+                if (vpt != kVPT) return fail(c, MI_ERR_BAD_ARG, "the policy matrix exists for the default fused_vpt only");
+                LAUNCH(c, s, MI_K_FUSED, (equalize_fused_kernel<kVPT, POL>), dim3(grid), dim3(kThreads), 0, j);
+                return MI_OK;
+            }
+        }
+        return fused_launch_matrix<POL + 1>(c, s, vpt, grid, j, pol);
+    }
+}
+#endif
+
 mi_status equalize_fused_dev(mi_ctx* c, hipStream_t s, const PlaneArgs& a, const UVJob* uv)
 {
     const long long ysz = (long long)a.width * a.height;
@@ -185,13 +253,19 @@ mi_status equalize_fused_dev(mi_ctx* c, hipStream_t s, const PlaneArgs& a, const
     j.host_hard = c->fused_hard_word ? c->fused_hard_word : j.host_repaired + kMirrorWords;
     const long long grid = std::min<long long>(tickets, (long long)c->cu_count * c->fused_wgs_per_cu);
     if (!c->capturing) c->fused_pair_open = true;
-    switch (vpt) {
-        case 8:  LAUNCH(c, s, MI_K_FUSED, equalize_fused_kernel<8>, dim3((unsigned)grid), dim3(kThreads), 0, j); break;
-        case 20: LAUNCH(c, s, MI_K_FUSED, equalize_fused_kernel<20>, dim3((unsigned)grid), dim3(kThreads), 0, j); break;
-        case 24: LAUNCH(c, s, MI_K_FUSED, equalize_fused_kernel<24>, dim3((unsigned)grid), dim3(kThreads), 0, j); break;
-        case 16: LAUNCH(c, s, MI_K_FUSED, equalize_fused_kernel<16>, dim3((unsigned)grid), dim3(kThreads), 0, j); break;
-        default: return fail(c, MI_ERR_BAD_ARG, "bad fused_vpt");
-    }
+    // bytes this launch loads and stores: Y in and out, UV out, UV in when it is copied
+    const long long uvb = j.U ? (long long)j.uv.bytes : 0;
+    const int pol = fused_pick_policy(c, (2 * ysz + uvb * (j.uv.mode ? 2 : 1)) * a.n_frames);
+    mi_status lst;
+    if (pol == kFusedPolPlain) lst = fused_launch<kFusedPolPlain>(c, s, vpt, (unsigned)grid, j);
+    else if (pol == kFusedPolStream) lst = fused_launch<kFusedPolStream>(c, s, vpt, (unsigned)grid, j);
+#ifdef MI_FUSED_POLICY_MATRIX
+    else lst = fused_launch_matrix<0>(c, s, vpt, (unsigned)grid, j, pol);
+#else
+    else lst = fail(c, MI_ERR_BAD_ARG, "bad fused_cache_policy");
+#endif
+    if (lst) return lst;
+    c->fused_last_policy = pol;
     // always: housekeeping in the normal case, stamp-driven repair when a bounded wait expired (kernels/equalize_fused.hip.h)
     const int fin_grid = (int)std::min<long long>(a.n_frames, (long long)c->cu_count * 4);
     LAUNCH(c, s, MI_K_FUSED_FINISH, fused_finish_kernel, dim3((unsigned)fin_grid), dim3(kThreads), 0, j);

@@ -301,6 +301,40 @@ __device__ __forceinline__ void uv_flat(const uint8_t* src, uint8_t* dst, long l
     }
 }
 
+// uv_flat with a cache policy on its 16-byte traffic (the fused kernel's UV tickets, whose bytes are touched once per launch):
+// ST_AUX is the aux operand of the buffer stores (0 plain, 2 nt, 16 sc1), LD_NT makes the copy's loads non-temporal.  Same split,
+// same byte stores at both ends, same bytes written as uv_flat; the stores go through a buffer descriptor over the aligned body
+// because only that form takes sc1.  (n < 2 GiB: the fused path's planes are counted in an int.)
+template <bool LD_NT, int ST_AUX>
+__device__ __forceinline__ void uv_flat_pol(const uint8_t* src, uint8_t* dst, long long n, int mode, int part, int nparts)
+{
+    const int t = threadIdx.x;
+    const Split16 s = split16(dst, n);
+    if (part == 0 && t < s.head) dst[t] = mode ? src[t] : (uint8_t)128;
+    if (part == nparts - 1 && t < s.tail) {
+        const long long o = s.head + (s.nvec << 4) + t;
+        dst[o] = mode ? src[o] : (uint8_t)128;
+    }
+    const long long v0 = s.nvec * part / nparts, v1 = s.nvec * (part + 1) / nparts;
+    const auto drsrc = __builtin_amdgcn_make_buffer_rsrc(dst + s.head, 0, (int)(s.nvec << 4), 0x00020000);
+    if (mode == 0) {
+        const u32x4 g = {0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};
+        for (long long i = v0 + t; i < v1; i += kThreads) __builtin_amdgcn_raw_buffer_store_b128(g, drsrc, (int)(i << 4), 0, ST_AUX);
+    } else {
+        const u32x4_u* sp = reinterpret_cast<const u32x4_u*>(src + s.head);
+        auto ld = [&](long long i) -> u32x4 { if constexpr (LD_NT) return __builtin_nontemporal_load(sp + i); else return sp[i]; };
+        long long i = v0 + t;
+        for (; i + 3 * kThreads < v1; i += 4 * kThreads) {
+            const u32x4 a = ld(i), b = ld(i + kThreads), c = ld(i + 2 * kThreads), d = ld(i + 3 * kThreads);
+            __builtin_amdgcn_raw_buffer_store_b128(a, drsrc, (int)(i << 4), 0, ST_AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(b, drsrc, (int)((i + kThreads) << 4), 0, ST_AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(c, drsrc, (int)((i + 2 * kThreads) << 4), 0, ST_AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(d, drsrc, (int)((i + 3 * kThreads) << 4), 0, ST_AUX);
+        }
+        for (; i < v1; i += kThreads) __builtin_amdgcn_raw_buffer_store_b128(ld(i), drsrc, (int)(i << 4), 0, ST_AUX);
+    }
+}
+
 // UV plane of pitched rows (a frame of a list): fill with 128 or copy.  This workgroup (`part` of `nparts`) takes a band of rows and
 // walks it as (row, 16-byte slot) items, four in flight per lane, stores aligned on each destination row; the unaligned bytes at both
 // ends of a row (at most 15 + 15) are byte stores.  Nothing outside the row_bytes of each row is touched.

@@ -117,10 +117,26 @@ __global__ __launch_bounds__(kThreads) void zero_words_kernel(uint32_t* p, size_
 //   2  the workgroups holding slices 0 and 1 of frame min(1, n-1), unless they are the last arriver, receive the LUT, then
 //      raise *status and leave without writing (a frame left partly written, its LUT published);
 //   3  the last arriver of frame 0 publishes a LUT whose checksum never matches and leaves (status 2 on the consumers).
-template <int VPT>
+//
+// POL (cache policy of the once-touched streams; the hand-off accesses -- ghist, cnt, ready, lutpub, sflag, status, the ticket
+// counter -- keep their policy whatever POL says, and POL == 0 is the kernel as it always was):
+//   bit 0      Y loads          0 plain, 1 nt
+//   bits 1-2   Y' stores        0 plain, 1 nt, 2 sc1
+//   bits 3-4   UV-ticket stores 0 plain, 1 nt, 2 sc1
+//   bit 5      UV-ticket loads  0 plain, 1 nt   (MI_UV_COPY only)
+constexpr int fused_pol(int y_ld, int y_st, int uv_st, int uv_ld) { return y_ld | (y_st << 1) | (uv_st << 3) | (uv_ld << 5); }
+constexpr bool fused_pol_valid(int pol) { return pol >= 0 && pol < 64 && ((pol >> 1) & 3) != 3 && ((pol >> 3) & 3) != 3; }
+constexpr int kAuxNt = 2, kAuxSc1 = 16;              // aux operand of the raw buffer builtins on gfx950
+constexpr int fused_aux(int sel) { return sel == 1 ? kAuxNt : sel == 2 ? kAuxSc1 : 0; }
+
+template <int VPT, int POL = 0>
 __global__ __launch_bounds__(kThreads, 4) void equalize_fused_kernel(FusedJob j)
 {
+    static_assert(fused_pol_valid(POL), "unknown cache policy");
     constexpr int kSliceVecs = kThreads * VPT;
+    constexpr int kYLoadAux = fused_aux(POL & 1), kYStoreAux = fused_aux((POL >> 1) & 3);
+    constexpr int kUVStoreAux = fused_aux((POL >> 3) & 3);
+    constexpr bool kUVLoadNt = ((POL >> 5) & 1) != 0;
     __shared__ uint32_t lds[256 * kCopies];          // slice histogram, then the replicated LUT
     __shared__ FusedShared sh;
     const int t = threadIdx.x;
@@ -142,8 +158,9 @@ __global__ __launch_bounds__(kThreads, 4) void equalize_fused_kernel(FusedJob j)
         const int f = (int)(k / P);
         const int r = (int)(k - (unsigned long long)f * P);
         if (r >= j.T) {                               // UV ticket (A7): 64 KiB of plain fill / copy
-            uv_flat(j.uv.src ? j.uv.src + (long long)f * j.uv.src_frame : nullptr, j.uv.dst + (long long)f * j.uv.dst_frame,
-                    j.uv.bytes, j.uv.mode, r - j.T, j.U);
+            const uint8_t* const uv_src = j.uv.src ? j.uv.src + (long long)f * j.uv.src_frame : nullptr;
+            if constexpr ((POL >> 3) == 0) uv_flat(uv_src, j.uv.dst + (long long)f * j.uv.dst_frame, j.uv.bytes, j.uv.mode, r - j.T, j.U);
+            else uv_flat_pol<kUVLoadNt, kUVStoreAux>(uv_src, j.uv.dst + (long long)f * j.uv.dst_frame, j.uv.bytes, j.uv.mode, r - j.T, j.U);
             if (t == 0) st_agent(j.sflag + k, epoch);
             continue;
         }
@@ -158,7 +175,7 @@ __global__ __launch_bounds__(kThreads, 4) void equalize_fused_kernel(FusedJob j)
         const int toff = t * 16;
         u32x4 q[VPT];
 #pragma unroll
-        for (int i = 0; i < VPT; ++i) q[i] = __builtin_amdgcn_raw_buffer_load_b128(srsrc, toff, i * (kThreads * 16), 0);
+        for (int i = 0; i < VPT; ++i) q[i] = __builtin_amdgcn_raw_buffer_load_b128(srsrc, toff, i * (kThreads * 16), kYLoadAux);
         for (int i = t; i < 256 * kCopies; i += kThreads) lds[i] = 0;
         __syncthreads();
         // ---- 2. slice histogram, publish with agent-scope atomics
@@ -265,7 +282,7 @@ __global__ __launch_bounds__(kThreads, 4) void equalize_fused_kernel(FusedJob j)
 #pragma unroll
         for (int i = 0; i < VPT; ++i) {
             launder(q[i]);                                          // re-extract the bytes here instead of keeping 256 of them live
-            __builtin_amdgcn_raw_buffer_store_b128(lut_vec(lds, q[i], copy), drsrc, toff, i * (kThreads * 16), 0);
+            __builtin_amdgcn_raw_buffer_store_b128(lut_vec(lds, q[i], copy), drsrc, toff, i * (kThreads * 16), kYStoreAux);
             __builtin_amdgcn_sched_barrier(0);                      // keep the bodies apart: the slice already owns 4*VPT VGPRs
         }
         if (t == 0) st_agent(j.sflag + k, epoch);                   // this ticket's output is on its way (complete at kernel end)

@@ -192,6 +192,27 @@ __global__ __launch_bounds__(256) void copy_y_fill_uv_kernel(const u32x4* __rest
     const u32x4 g = {0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};
     for (long long k = u0 + threadIdx.x; k < u1; k += 256) dp[nvec_y + k] = g;
 }
+// the same skeleton with a cache policy on each stream (aux operand of the buffer instructions: 0 plain, 2 nt, 16 sc1), as
+// equalize_fused_kernel<VPT, POL> applies them: does the CEILING move with the policy, or only the fused kernel's distance to it?
+template <int LD_AUX, int YST_AUX, int UVST_AUX>
+__global__ __launch_bounds__(256) void copy_y_fill_uv_pol_kernel(const u32x4* __restrict__ src, u32x4* __restrict__ dst, long long nvec_y, long long nvec_uv, long long frame_vec_stride)
+{
+    const int fbytes = (int)((nvec_y + nvec_uv) * 16);
+    const auto srs = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32x4*>(src + (long long)blockIdx.y * frame_vec_stride), 0, (int)(nvec_y * 16), 0x00020000);
+    const auto drs = __builtin_amdgcn_make_buffer_rsrc(dst + (long long)blockIdx.y * frame_vec_stride, 0, fbytes, 0x00020000);
+    const long long v0 = nvec_y * blockIdx.x / gridDim.x, v1 = nvec_y * (blockIdx.x + 1) / gridDim.x;
+    long long i = v0 + threadIdx.x;
+    auto ld = [&](long long k) { return __builtin_amdgcn_raw_buffer_load_b128(srs, (int)(k << 4), 0, LD_AUX); };
+    auto st = [&](long long k, u32x4 v) { __builtin_amdgcn_raw_buffer_store_b128(v, drs, (int)(k << 4), 0, YST_AUX); };
+    for (; i + 3 * 256 < v1; i += 4 * 256) {
+        const u32x4 a = ld(i), b = ld(i + 256), c = ld(i + 512), d = ld(i + 768);
+        st(i, a); st(i + 256, b); st(i + 512, c); st(i + 768, d);
+    }
+    for (; i < v1; i += 256) st(i, ld(i));
+    const long long u0 = nvec_uv * blockIdx.x / gridDim.x, u1 = nvec_uv * (blockIdx.x + 1) / gridDim.x;
+    const u32x4 g = {0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};
+    for (long long k = u0 + threadIdx.x; k < u1; k += 256) __builtin_amdgcn_raw_buffer_store_b128(g, drs, (int)((nvec_y + k) << 4), 0, UVST_AUX);
+}
 __global__ __launch_bounds__(256) void fill_kernel(u32x4* __restrict__ dst, long long nvec, long long frame_vec_stride)
 {
     u32x4* dp = dst + (long long)blockIdx.y * frame_vec_stride;
@@ -208,6 +229,7 @@ int main(int argc, char** argv)
     const int nf = argc > 1 ? atoi(argv[1]) : 64;
     const int dist = argc > 2 ? atoi(argv[2]) : 2;        // 1 uniform, 2 low-contrast, 3 constant
     const int rounds = argc > 3 ? atoi(argv[3]) : 15;
+    const bool ceil_only = argc > 4 && !strcmp(argv[4], "ceil");   // only the copy / fill ceilings and their cache-policy variants
     const int W = 3840, H = 2160;
     const long long ysz = (long long)W * H, fb = ysz + ysz / 2;
     const long long nvec = ysz / 16, fvs = fb / 16;
@@ -269,8 +291,19 @@ int main(int argc, char** argv)
       vs.push_back({"apply lut32x32 (shipped)", 2 * yb, [=](hipStream_t s) { hipLaunchKernelGGL((apply_var_kernel<1, false, false>), dim3(b, nf), dim3(256), 0, s, vin, vout, nvec, fvs, d_luts); }, {}});
       vs.push_back({"apply bpermute", 2 * yb, [=](hipStream_t s) { hipLaunchKernelGGL((apply_var_kernel<2, false, false>), dim3(b, nf), dim3(256), 0, s, vin, vout, nvec, fvs, d_luts); }, {}});
       vs.push_back({"apply lut32x32 nt-store", 2 * yb, [=](hipStream_t s) { hipLaunchKernelGGL((apply_var_kernel<1, true, false>), dim3(b, nf), dim3(256), 0, s, vin, vout, nvec, fvs, d_luts); }, {}});
+#define POLV(name, L, Y, U) vs.push_back({"copy Y + fill UV " name, 2.5 * yb, [=](hipStream_t s) { hipLaunchKernelGGL((copy_y_fill_uv_pol_kernel<L, Y, U>), dim3(b, nf), dim3(256), 0, s, vin, vout, nvec, nvec / 2, fvs); }, {}})
+      POLV("buf plain", 0, 0, 0);
+      POLV("ld nt", 2, 0, 0);
+      POLV("st nt", 0, 2, 2);
+      POLV("st sc1", 0, 16, 16);
+      POLV("ld nt st nt", 2, 2, 2);
+      POLV("ld nt st sc1", 2, 16, 16);
+      POLV("ld nt Y nt UV sc1", 2, 2, 16);
+      POLV("ld nt Y sc1 UV nt", 2, 16, 2);
+#undef POLV
       // cache-reuse experiments: run read_sum (stands for the hist pass) then apply; time only the apply
     }
+    if (ceil_only) vs.erase(std::remove_if(vs.begin(), vs.end(), [](const Variant& v) { return v.name.rfind("copy Y", 0) != 0 && v.name.rfind("fill", 0) != 0; }), vs.end());
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     for (int r = -2; r < rounds; ++r) {
         for (auto& v : vs) {
@@ -290,6 +323,7 @@ int main(int argc, char** argv)
         const float med = v.us[v.us.size() / 2], mn = v.us[0];
         printf("%-34s %10.1f %10.1f %12.1f\n", v.name.c_str(), med, mn, v.alg_bytes / (med * 1e-6) / 1e9);
     }
+    if (ceil_only) return 0;
     // --- ordering / Infinity-Cache reuse experiment: hist pass then apply pass, forward vs reverse, sub-batched
     auto seq = [&](int group, bool reverse, bool nt) {
         // processes nf frames in groups of `group`: hist(group) then apply(group)
