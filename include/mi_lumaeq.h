@@ -323,6 +323,34 @@ mi_status mi_equalize_hist_packed422(mi_ctx* ctx, const uint8_t* in, size_t in_p
                                      int width, int height, int format, mi_uv_mode uv_mode);
 mi_status mi_clahe_packed422(mi_ctx* ctx, const uint8_t* in, size_t in_pitch, uint8_t* out, size_t out_pitch,
                              int width, int height, int format, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
+/* mi_*_packed422_frames_dev: a LIST of packed 4:2:2 frames in device memory, each at its own address -- a capture device's buffer
+ * pool (v4l2, SDI / HDMI cards): every buffer its own allocation, rows padded to bytesperline, the base address at whatever alignment
+ * the driver gave it.  `frames` is a host array of n_frames entries, read only during the call; the pointers in it are device
+ * pointers on the context's device.  Every frame of one call has the same width (even), height (any value >= 1), format and the same
+ * two pitches (bytes between rows, each >= 2*W):
+ *   in  : H rows of 2*W bytes at in_pitch          out : H rows of 2*W bytes at out_pitch
+ * Addresses and pitches are multiples of 4; each frame may have its own alignment modulo 16 (slower never, different never).  The
+ * same input may appear in several entries.  The luma and the chroma of every frame are byte for byte what
+ * mi_*_packed422_batch_dev writes for that frame (same clahe_fp_contract option, same REFLECT_101 padding, same fallback for tile
+ * grids too wide for the LDS tables); nothing outside the 2*W bytes of an output row is written.
+ * In place is decided PER FRAME: a frame is in place when out == in (the two pitches must then be equal), and one list may mix
+ * in-place and out-of-place frames; in place with MI_UV_COPY leaves the chroma as it is.  Outputs of DIFFERENT frames that overlap
+ * each other give undefined results (not checked).  Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while a pipe has frames pending and
+ * hipGraph capture after one eager call of the same shape as mi_*_nv12_frames_dev; profiling slots by role as the _batch_dev forms
+ * above; never the fused equalizeHist kernel nor the single-launch histogram + LUT kernel.
+ * Errors, MI_ERR_BAD_ARG: a null ctx, a null `frames` with n_frames > 0, a negative size, an odd width, a format other than
+ * MI_FMT_YUY2 / MI_FMT_UYVY, a bad uv_mode, tiles <= 0, a pitch < 2*W, a pitch or address that is not a multiple of 4, a null in or
+ * out, out == in with unequal pitches, an output whose rows overlap the rows of its own frame's input other than exactly.  Sizes and
+ * tile grids beyond what the planar forms accept: what those answer (MI_ERR_UNSUPPORTED).  n_frames, width or height of 0: MI_OK,
+ * nothing written.  Nothing is enqueued unless every frame passes the checks. */
+typedef struct mi_packed422_frame_dev { const void* in; void* out; } mi_packed422_frame_dev;
+mi_status mi_equalize_hist_packed422_frames_dev(mi_ctx* ctx, const mi_packed422_frame_dev* frames, int n_frames,
+                                                int width, int height, size_t in_pitch, size_t out_pitch,
+                                                int format, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_packed422_frames_dev(mi_ctx* ctx, const mi_packed422_frame_dev* frames, int n_frames,
+                                        int width, int height, size_t in_pitch, size_t out_pitch,
+                                        int format, mi_uv_mode uv_mode,
+                                        double clip_limit, int tiles_x, int tiles_y, void* stream);
 
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at

@@ -49,8 +49,11 @@ Packed422 packed422_batch(const P422Args& a, int f0)
     return p;
 }
 
+// The stage sequences below take an optional frame list (kernels/packed422.hip.h Packed422List, mi_*_packed422_frames_dev: one chunk
+// of at most kPacked422FramesPerLaunch frames, a.n_frames of them, indices from 0): with one, every launch goes to the *_frames_kernel
+// entry of the same body -- same grids, same splits, same scratch -- and a.in / a.out / the frame strides are not used.
 template <int OFF>
-mi_status equalize422_dev(mi_ctx* c, hipStream_t s, const P422Args& a)
+mi_status equalize422_dev(mi_ctx* c, hipStream_t s, const P422Args& a, const Packed422List* fl = nullptr)
 {
     const long long frame_bytes = 2LL * a.width * a.height;
     for (int f0 = 0; f0 < a.n_frames; f0 += kMaxGridY) {
@@ -60,18 +63,21 @@ mi_status equalize422_dev(mi_ctx* c, hipStream_t s, const P422Args& a)
         mi_status st = grow_dev(c, &c->d_partial, &c->partial_bytes, (size_t)nf * B * 256 * sizeof(uint32_t));
         if (st) return st;
         if ((st = grow_dev(c, &c->d_luts, &c->luts_bytes, (size_t)nf * 256))) return st;
-        LAUNCH(c, s, MI_K_HIST, hist422_partial_kernel<OFF>, dim3(B, nf), dim3(kHistThreads), 0, p, c->d_partial);
+        if (fl) LAUNCH(c, s, MI_K_HIST, hist422_partial_frames_kernel<OFF>, dim3(B, nf), dim3(kHistThreads), 0, *fl, p, c->d_partial);
+        else    LAUNCH(c, s, MI_K_HIST, hist422_partial_kernel<OFF>, dim3(B, nf), dim3(kHistThreads), 0, p, c->d_partial);
         LAUNCH(c, s, MI_K_EQ_LUT, equalize_lut_kernel, dim3(nf), dim3(kThreads), 0,
                (const uint32_t*)c->d_partial, B, (int)((long long)a.width * a.height), c->d_luts, (int32_t*)nullptr);
         const int BA = blocks_per_frame(c, frame_bytes, a.height, nf, 2048);
-        LAUNCH(c, s, MI_K_LUT_APPLY, lut_apply422_kernel<OFF>, dim3(BA, nf), dim3(kThreads), 0, p, (const uint8_t*)c->d_luts);
+        if (fl) LAUNCH(c, s, MI_K_LUT_APPLY, lut_apply422_frames_kernel<OFF>, dim3(BA, nf), dim3(kThreads), 0, *fl, p, (const uint8_t*)c->d_luts);
+        else    LAUNCH(c, s, MI_K_LUT_APPLY, lut_apply422_kernel<OFF>, dim3(BA, nf), dim3(kThreads), 0, p, (const uint8_t*)c->d_luts);
     }
     return MI_OK;
 }
 
 // launch_tile_luts' splits and tile order (one tile per workgroup: the multi-tile variant has no packed sibling)
 template <int OFF>
-mi_status launch_tile_luts422(mi_ctx* c, hipStream_t s, const Packed422& p, const ClaheGeom& g, int nf, uint8_t* d_luts_out)
+mi_status launch_tile_luts422(mi_ctx* c, hipStream_t s, const Packed422& p, const ClaheGeom& g, int nf, uint8_t* d_luts_out,
+                              const Packed422List* fl = nullptr)
 {
     const int tiles = g.tiles_x * g.tiles_y;
     const long long tile_px = (long long)g.tile_w * g.tile_h;
@@ -82,8 +88,10 @@ mi_status launch_tile_luts422(mi_ctx* c, hipStream_t s, const Packed422& p, cons
     if (tiles > kMaxGridY) return fail(c, MI_ERR_UNSUPPORTED, "more than 65535 tiles per frame");
     uint8_t* direct = S == 1 ? d_luts_out : nullptr;
     const int xcd_map = (c->clahe_xcd_map && S == 1 && tiles % 8 == 0) ? 1 : 0;
-    LAUNCH(c, s, MI_K_TILE_HIST, (tile_hist422_kernel<OFF, 512>), dim3(S, tiles, nf), dim3(512), 0,
-           p.src, p.src_step, p.src_frame, g, c->d_partial, direct, xcd_map);
+    if (fl) LAUNCH(c, s, MI_K_TILE_HIST, (tile_hist422_frames_kernel<OFF, 512>), dim3(S, tiles, nf), dim3(512), 0,
+                   *fl, p.src_step, g, c->d_partial, direct, xcd_map);
+    else    LAUNCH(c, s, MI_K_TILE_HIST, (tile_hist422_kernel<OFF, 512>), dim3(S, tiles, nf), dim3(512), 0,
+                   p.src, p.src_step, p.src_frame, g, c->d_partial, direct, xcd_map);
     if (!direct)
         LAUNCH(c, s, MI_K_TILE_LUT, tile_lut_kernel, dim3(tiles, nf), dim3(kThreads), 0, (const uint32_t*)c->d_partial, S, g, d_luts_out);
     return MI_OK;
@@ -91,13 +99,15 @@ mi_status launch_tile_luts422(mi_ctx* c, hipStream_t s, const Packed422& p, cons
 
 // launch_interp's choice of tables, column segments, bands and sub-bands
 template <int OFF>
-mi_status launch_interp422(mi_ctx* c, hipStream_t s, const Packed422& p, const ClaheGeom& g, int nf, const uint8_t* d_luts)
+mi_status launch_interp422(mi_ctx* c, hipStream_t s, const Packed422& p, const ClaheGeom& g, int nf, const uint8_t* d_luts,
+                           const Packed422List* fl = nullptr)
 {
     const int npairs = g.tiles_x + 1;
     if (npairs > kMaxPairsLds) {
         if (g.height > kMaxGridY) return fail(c, MI_ERR_UNSUPPORTED, "height > 65535 with tiles_x > 62");
-        LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp422_global_kernel<OFF>, dim3((p.dwords + kThreads - 1) / kThreads, g.height, nf),
-               dim3(kThreads), 0, p, g, d_luts);
+        const dim3 grid((p.dwords + kThreads - 1) / kThreads, g.height, nf);
+        if (fl) LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp422_global_frames_kernel<OFF>, grid, dim3(kThreads), 0, *fl, p, g, d_luts);
+        else    LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp422_global_kernel<OFF>, grid, dim3(kThreads), 0, p, g, d_luts);
         return MI_OK;
     }
     const int ngroups = (g.width + kInterpPx - 1) / kInterpPx;
@@ -122,18 +132,25 @@ mi_status launch_interp422(mi_ctx* c, hipStream_t s, const Packed422& p, const C
     if ((npairs <= kMaxPairsLdsF32 || seg_tables) && c->clahe_float_tables) {
         const int cap = seg_tables ? seg_cap : kMaxPairsLdsF32;
         const size_t lds = (size_t)std::min(npairs, cap) * 256 * 4 * sizeof(float);
-        if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<true, true, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
-        else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<true, false, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
+        if (fl) {
+            if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_frames_kernel<true, true, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
+            else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_frames_kernel<true, false, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
+        } else if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<true, true, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
+        else                   LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<true, false, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
     } else {
         const size_t lds = (size_t)npairs * 256 * sizeof(uint32_t);
-        if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<false, true, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, kMaxPairsLds + 1);
-        else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<false, false, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, kMaxPairsLds + 1);
+        if (fl) {
+            if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_frames_kernel<false, true, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, kMaxPairsLds + 1);
+            else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_frames_kernel<false, false, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, kMaxPairsLds + 1);
+        } else if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<false, true, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, kMaxPairsLds + 1);
+        else                   LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<false, false, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, kMaxPairsLds + 1);
     }
     return MI_OK;
 }
 
 template <int OFF>
-mi_status clahe422_dev(mi_ctx* c, hipStream_t s, const P422Args& a, double clip_limit, int tiles_x, int tiles_y)
+mi_status clahe422_dev(mi_ctx* c, hipStream_t s, const P422Args& a, double clip_limit, int tiles_x, int tiles_y,
+                       const Packed422List* fl = nullptr)
 {
     ClaheGeom g;
     mi_status st = clahe_geometry(c, a.width, a.height, clip_limit, tiles_x, tiles_y, &g);
@@ -143,17 +160,18 @@ mi_status clahe422_dev(mi_ctx* c, hipStream_t s, const P422Args& a, double clip_
         const int nf = std::min(kMaxGridY, a.n_frames - f0);
         const Packed422 p = packed422_batch(a, f0);
         if ((st = grow_dev(c, &c->d_luts, &c->luts_bytes, (size_t)nf * tiles * 256))) return st;
-        if ((st = launch_tile_luts422<OFF>(c, s, p, g, nf, c->d_luts))) return st;
-        if ((st = launch_interp422<OFF>(c, s, p, g, nf, c->d_luts))) return st;
+        if ((st = launch_tile_luts422<OFF>(c, s, p, g, nf, c->d_luts, fl))) return st;
+        if ((st = launch_interp422<OFF>(c, s, p, g, nf, c->d_luts, fl))) return st;
     }
     return MI_OK;
 }
 
-// op: 0 equalizeHist, 1 CLAHE.  `a` has passed check_packed422.
-mi_status packed422_dev(mi_ctx* c, hipStream_t s, const P422Args& a, int op, double clip_limit, int tiles_x, int tiles_y)
+// op: 0 equalizeHist, 1 CLAHE.  `a` has passed check_packed422 (with a list: check_packed422_frames).
+mi_status packed422_dev(mi_ctx* c, hipStream_t s, const P422Args& a, int op, double clip_limit, int tiles_x, int tiles_y,
+                        const Packed422List* fl = nullptr)
 {
-    if (a.format == MI_FMT_UYVY) return op ? clahe422_dev<1>(c, s, a, clip_limit, tiles_x, tiles_y) : equalize422_dev<1>(c, s, a);
-    return op ? clahe422_dev<0>(c, s, a, clip_limit, tiles_x, tiles_y) : equalize422_dev<0>(c, s, a);
+    if (a.format == MI_FMT_UYVY) return op ? clahe422_dev<1>(c, s, a, clip_limit, tiles_x, tiles_y, fl) : equalize422_dev<1>(c, s, a, fl);
+    return op ? clahe422_dev<0>(c, s, a, clip_limit, tiles_x, tiles_y, fl) : equalize422_dev<0>(c, s, a, fl);
 }
 
 // Host frame: the whole frame goes up and comes back (there is no luma plane to send on its own), tight on the device; pinned tight

@@ -23,6 +23,36 @@ struct Packed422 {
     uint32_t keep, fill;              // chroma of an output dword: (input & keep) | fill -- copy: keep = chroma mask, fill128: fill = 0x80s
 };
 
+// A list of packed frames, each at its own addresses (mi_*_packed422_frames_dev): the {in, out} pairs travel BY VALUE in the kernel
+// arguments like common.hip.h's FrameList -- 16 B an entry, half of an NV12 entry -- and are read with scalar kernarg loads indexed by
+// the frame's grid coordinate.  The shape (pitches, dwords, rows, keep / fill) is the launch's Packed422, whose src / dst / *_frame a
+// table launch ignores.
+#ifndef MI_PACKED422_FRAMES_PER_LAUNCH
+#define MI_PACKED422_FRAMES_PER_LAUNCH 128      // 64 or 128: docs/experiments.md has the measurement
+#endif
+constexpr int kPacked422FramesPerLaunch = MI_PACKED422_FRAMES_PER_LAUNCH;
+static_assert(kPacked422FramesPerLaunch == 64 || kPacked422FramesPerLaunch == 128, "a table is 1 or 2 KiB of kernel arguments");
+struct Packed422Frame { const uint8_t* in; uint8_t* out; };
+struct Packed422List { Packed422Frame f[kPacked422FramesPerLaunch]; };
+
+// Where frame f of a launch lives (the two policies of common.hip.h, on packed frames).  The kernel bodies below are templates on
+// one of them: the batch kernels wrap them with the strided policy, which refers to the kernel's own Packed422 argument (the
+// arithmetic they always had; the tile histograms use common.hip.h's StridedSource on their src_base / frame_stride pair), the
+// *_frames_kernel entries with the table.
+struct Strided422 {
+    const Packed422& p;
+    __device__ __forceinline__ const uint8_t* src_of(long long f) const { return p.src + f * p.src_frame; }
+    __device__ __forceinline__ uint8_t* dst_of(long long f) const { return p.dst + f * p.dst_frame; }
+};
+// In place is a frame's own business here (in == out): the apply and interpolation stages are element-wise on a frame whose LUTs are
+// already final -- a lane reads a dword and writes that same dword -- so an in-place frame next to an out-of-place one needs no
+// ownership logic.
+struct Table422 {
+    const Packed422List& l;
+    __device__ __forceinline__ const uint8_t* src_of(long long f) const { return l.f[f].in; }
+    __device__ __forceinline__ uint8_t* dst_of(long long f) const { return l.f[f].out; }
+};
+
 template <int OFF> __device__ __forceinline__ uint32_t y0_of(uint32_t w) { return OFF ? (w >> 8) & 0xffu : w & 0xffu; }
 template <int OFF> __device__ __forceinline__ uint32_t y1_of(uint32_t w) { return OFF ? w >> 24 : (w >> 16) & 0xffu; }
 template <int OFF> __device__ __forceinline__ uint32_t put_y(uint32_t a, uint32_t b) { return OFF ? (a << 8) | (b << 24) : a | (b << 16); }
@@ -85,8 +115,8 @@ __device__ __forceinline__ void hist422_add(uint32_t* h, u32x4 q, int n, bool sk
 // K1p  histogram partials of the luma.  grid = (B, n_frames); partial[f][b][256] as hist_partial_kernel writes them.  A workgroup takes
 // a band of rows and walks it as (row, slot) items NT apart, four loads in flight per lane.  Reads the chroma too (same cache lines).
 // ---------------------------------------------------------------------------------------------
-template <int OFF>
-__global__ __launch_bounds__(kHistThreads) void hist422_partial_kernel(Packed422 p, uint32_t* __restrict__ partial)
+template <int OFF, class Frames>
+__device__ __forceinline__ void hist422_partial_body(const Packed422& p, const Frames& fr, uint32_t* __restrict__ partial)
 {
     constexpr int NT = kHistThreads;
     __shared__ uint32_t h[256 * kCopies];
@@ -94,7 +124,7 @@ __global__ __launch_bounds__(kHistThreads) void hist422_partial_kernel(Packed422
     const int t = threadIdx.x;
     const uint32_t copy = t & (kCopies - 1);
     const int r0 = (int)((long long)p.rows * blockIdx.x / gridDim.x), r1 = (int)((long long)p.rows * (blockIdx.x + 1) / gridDim.x);
-    const uint8_t* row0 = p.src + (long long)blockIdx.y * p.src_frame + (long long)r0 * p.src_step;
+    const uint8_t* row0 = fr.src_of(blockIdx.y) + (long long)r0 * p.src_step;
     const int S = slots422(p.dwords);
     const long long items = (long long)(r1 - r0) * S;
     int row = t / S, slot = t - row * S;
@@ -116,6 +146,16 @@ __global__ __launch_bounds__(kHistThreads) void hist422_partial_kernel(Packed422
     __syncthreads();
     if (t < 256) partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + t] = lds_hist_bin(h, t);
 }
+template <int OFF>
+__global__ __launch_bounds__(kHistThreads) void hist422_partial_kernel(Packed422 p, uint32_t* __restrict__ partial)
+{
+    hist422_partial_body<OFF>(p, Strided422{p}, partial);
+}
+template <int OFF>
+__global__ __launch_bounds__(kHistThreads) void hist422_partial_frames_kernel(Packed422List l, Packed422 p, uint32_t* __restrict__ partial)
+{
+    hist422_partial_body<OFF>(p, Table422{l}, partial);
+}
 
 // ---------------------------------------------------------------------------------------------
 // K3p  LUT apply on the luma, chroma copied or set to 128, one full dword written per macropixel.  grid = (B, n_frames).
@@ -129,8 +169,8 @@ __device__ __forceinline__ uint32_t lut422_dword(const uint32_t* lut, uint32_t w
     return put_y<OFF>(a, b) | (w & keep) | fill;
 }
 
-template <int OFF>
-__global__ __launch_bounds__(kThreads) void lut_apply422_kernel(Packed422 p, const uint8_t* __restrict__ luts)
+template <int OFF, class Frames>
+__device__ __forceinline__ void lut_apply422_body(const Packed422& p, const Frames& fr, const uint8_t* __restrict__ luts)
 {
     __shared__ uint32_t lut[256 * kCopies];
     // frames last-to-first: the histogram pass streamed the batch first-to-last, its tail is still in the Infinity Cache
@@ -143,8 +183,8 @@ __global__ __launch_bounds__(kThreads) void lut_apply422_kernel(Packed422 p, con
     __syncthreads();
     const uint32_t copy = t & (kCopies - 1);
     const int r0 = (int)((long long)p.rows * blockIdx.x / gridDim.x), r1 = (int)((long long)p.rows * (blockIdx.x + 1) / gridDim.x);
-    const uint8_t* src0 = p.src + (long long)f * p.src_frame + (long long)r0 * p.src_step;
-    uint8_t* dst0 = p.dst + (long long)f * p.dst_frame + (long long)r0 * p.dst_step;
+    const uint8_t* src0 = fr.src_of(f) + (long long)r0 * p.src_step;
+    uint8_t* dst0 = fr.dst_of(f) + (long long)r0 * p.dst_step;
     const int S = slots422(p.dwords);
     const long long items = (long long)(r1 - r0) * S;
     int row = t / S, slot = t - row * S;
@@ -171,15 +211,25 @@ __global__ __launch_bounds__(kThreads) void lut_apply422_kernel(Packed422 p, con
         }
     }
 }
+template <int OFF>
+__global__ __launch_bounds__(kThreads) void lut_apply422_kernel(Packed422 p, const uint8_t* __restrict__ luts)
+{
+    lut_apply422_body<OFF>(p, Strided422{p}, luts);
+}
+template <int OFF>
+__global__ __launch_bounds__(kThreads) void lut_apply422_frames_kernel(Packed422List l, Packed422 p, const uint8_t* __restrict__ luts)
+{
+    lut_apply422_body<OFF>(p, Table422{l}, luts);
+}
 
 // ---------------------------------------------------------------------------------------------
 // K4p  per-tile luma histograms (tile_hist_kernel's grid, splits, XCD map and LUT fold).  The in-frame columns [x0, x0 + in_w) of a
 // tile row are the dwords [x0 / 2, (x0 + in_w + 1) / 2): a tile that starts or ends on an odd column shares its first / last dword with
 // its neighbour and counts one luma of it.  Rows beyond the frame by index reflection; reflected columns (right border tiles) byte loads.
 // ---------------------------------------------------------------------------------------------
-template <int OFF, int NT>
-__global__ __launch_bounds__(NT) void tile_hist422_kernel(const uint8_t* __restrict__ src_base, long long step, long long frame_stride,
-                                                         ClaheGeom g, uint32_t* __restrict__ partial, uint8_t* __restrict__ luts, int xcd_map)
+template <int OFF, int NT, class Frames>
+__device__ __forceinline__ void tile_hist422_body(const Frames& fr, long long step, const ClaheGeom& g, uint32_t* __restrict__ partial,
+                                                  uint8_t* __restrict__ luts, int xcd_map)
 {
     __shared__ uint32_t h[256 * kCopies];                       // 32 KiB; the scans reuse h[0..3] once h is folded
     uint32_t* const s_wave = h;
@@ -191,7 +241,7 @@ __global__ __launch_bounds__(NT) void tile_hist422_kernel(const uint8_t* __restr
     const int ntiles = gridDim.y;
     const int tile = xcd_map ? ((int)(blockIdx.y & 7) * (ntiles >> 3) + (int)(blockIdx.y >> 3)) : (int)blockIdx.y;
     const int ty = tile / g.tiles_x, tx = tile - ty * g.tiles_x;
-    const uint8_t* src = src_base + (long long)f * frame_stride;
+    const uint8_t* src = fr.src_of(f);
     const int r0 = (int)((long long)g.tile_h * s / S), r1 = (int)((long long)g.tile_h * (s + 1) / S);
     const int x0 = tx * g.tile_w;
     const int in_w = max(0, min(g.tile_w, g.width - x0));     // columns of this tile that lie inside the frame
@@ -237,6 +287,18 @@ __global__ __launch_bounds__(NT) void tile_hist422_kernel(const uint8_t* __restr
     if (luts) luts[((size_t)f * gridDim.y + tile) * 256 + t] = tile_lut_value(bin, g, s_wave);     // host passes luts only when S == 1
     else partial[(((size_t)f * gridDim.y + tile) * S + s) * 256 + t] = bin;
 }
+template <int OFF, int NT>
+__global__ __launch_bounds__(NT) void tile_hist422_kernel(const uint8_t* __restrict__ src_base, long long step, long long frame_stride,
+                                                         ClaheGeom g, uint32_t* __restrict__ partial, uint8_t* __restrict__ luts, int xcd_map)
+{
+    tile_hist422_body<OFF, NT>(StridedSource{src_base, frame_stride}, step, g, partial, luts, xcd_map);
+}
+template <int OFF, int NT>
+__global__ __launch_bounds__(NT) void tile_hist422_frames_kernel(Packed422List l, long long step, ClaheGeom g, uint32_t* __restrict__ partial,
+                                                                uint8_t* __restrict__ luts, int xcd_map)
+{
+    tile_hist422_body<OFF, NT>(Table422{l}, step, g, partial, luts, xcd_map);
+}
 
 // ---------------------------------------------------------------------------------------------
 // K6p  bilinear interpolation of the tile LUTs on the luma (clahe_interp_kernel's grid, bands, pair tables and column segments).
@@ -259,9 +321,9 @@ __device__ __forceinline__ uint32_t scatter422_lo(uint32_t y, uint32_t c) { retu
 template <int OFF>
 __device__ __forceinline__ uint32_t scatter422_hi(uint32_t y, uint32_t c) { return __builtin_amdgcn_perm(c, y, OFF ? 0x03060204u : 0x07030502u); }
 
-template <bool FT, bool FMA, int OFF>
-__global__ __launch_bounds__(kThreads) void clahe_interp422_kernel(Packed422 p, ClaheGeom g, const uint8_t* __restrict__ luts,
-                                                                  int subs, int groups, int pair_cap)
+template <bool FT, bool FMA, int OFF, class Frames>
+__device__ __forceinline__ void clahe_interp422_body(const Packed422& p, const Frames& fr, const ClaheGeom g, const uint8_t* __restrict__ luts,
+                                                     int subs, int groups, int pair_cap)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t quad[];   // [(tiles_x + 1)][256] u32 quads, or f32x4 when FT
     f32x4* quadf = reinterpret_cast<f32x4*>(quad);
@@ -320,8 +382,8 @@ __global__ __launch_bounds__(kThreads) void clahe_interp422_kernel(Packed422 p, 
         pr = pr < 0 ? 0 : (pr >= npairs ? npairs - 1 : pr);
         poff[j] = pr << 8;
     }
-    const uint8_t* src = p.src + (long long)f * p.src_frame + 2LL * x0;
-    uint8_t* dst = p.dst + (long long)f * p.dst_frame + 2LL * x0;
+    const uint8_t* src = fr.src_of(f) + 2LL * x0;
+    uint8_t* dst = fr.dst_of(f) + 2LL * x0;
     const bool full = x0 + kInterpPx <= g.width;
     auto ty1_of = [&](int y) { return floor_f32_to_int(tile_coord<FMA>(y, g.inv_th)); };
     int ya_lo = y_lo, ya_hi = y_hi;
@@ -387,11 +449,23 @@ __global__ __launch_bounds__(kThreads) void clahe_interp422_kernel(Packed422 p, 
         }
     }
 }
+template <bool FT, bool FMA, int OFF>
+__global__ __launch_bounds__(kThreads) void clahe_interp422_kernel(Packed422 p, ClaheGeom g, const uint8_t* __restrict__ luts,
+                                                                  int subs, int groups, int pair_cap)
+{
+    clahe_interp422_body<FT, FMA, OFF>(p, Strided422{p}, g, luts, subs, groups, pair_cap);
+}
+template <bool FT, bool FMA, int OFF>
+__global__ __launch_bounds__(kThreads) void clahe_interp422_frames_kernel(Packed422List l, Packed422 p, ClaheGeom g, const uint8_t* __restrict__ luts,
+                                                                         int subs, int groups, int pair_cap)
+{
+    clahe_interp422_body<FT, FMA, OFF>(p, Table422{l}, g, luts, subs, groups, pair_cap);
+}
 
 // Fallback for tile grids too wide for the LDS pair table (clahe_interp_global_kernel's arithmetic): one macropixel per thread, the LUTs
 // gathered from global memory (L2).  grid = (ceil(W / 2 / 256), H, n_frames).
-template <int OFF>
-__global__ __launch_bounds__(kThreads) void clahe_interp422_global_kernel(Packed422 p, ClaheGeom g, const uint8_t* __restrict__ luts)
+template <int OFF, class Frames>
+__device__ __forceinline__ void clahe_interp422_global_body(const Packed422& p, const Frames& fr, const ClaheGeom& g, const uint8_t* __restrict__ luts)
 {
     const int f = blockIdx.z;
     const int y = blockIdx.y;
@@ -402,7 +476,7 @@ __global__ __launch_bounds__(kThreads) void clahe_interp422_global_kernel(Packed
     int ty1 = floor_f32_to_int(tyf);
     const float ya = __fsub_rn(tyf, (float)ty1), ya1 = __fsub_rn(1.0f, ya);
     int ty2 = ty1 + 1; ty1 = max(ty1, 0); ty2 = min(ty2, g.tiles_y - 1);
-    const uint32_t w = reinterpret_cast<const uint32_t*>(p.src + (long long)f * p.src_frame + (long long)y * p.src_step)[d];
+    const uint32_t w = reinterpret_cast<const uint32_t*>(fr.src_of(f) + (long long)y * p.src_step)[d];
     uint32_t e[2];
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
@@ -417,7 +491,17 @@ __global__ __launch_bounds__(kThreads) void clahe_interp422_global_kernel(Packed
                            ((uint32_t)lf[((size_t)ty2 * g.tiles_x + tx2) * 256 + v] << 24);
         e[b] = g.contract ? clahe_px<true>(q, xa, xa1, ya, ya1) : clahe_px<false>(q, xa, xa1, ya, ya1);
     }
-    reinterpret_cast<uint32_t*>(p.dst + (long long)f * p.dst_frame + (long long)y * p.dst_step)[d] = put_y<OFF>(e[0], e[1]) | (w & p.keep) | p.fill;
+    reinterpret_cast<uint32_t*>(fr.dst_of(f) + (long long)y * p.dst_step)[d] = put_y<OFF>(e[0], e[1]) | (w & p.keep) | p.fill;
+}
+template <int OFF>
+__global__ __launch_bounds__(kThreads) void clahe_interp422_global_kernel(Packed422 p, ClaheGeom g, const uint8_t* __restrict__ luts)
+{
+    clahe_interp422_global_body<OFF>(p, Strided422{p}, g, luts);
+}
+template <int OFF>
+__global__ __launch_bounds__(kThreads) void clahe_interp422_global_frames_kernel(Packed422List l, Packed422 p, ClaheGeom g, const uint8_t* __restrict__ luts)
+{
+    clahe_interp422_global_body<OFF>(p, Table422{l}, g, luts);
 }
 
 }  // namespace mi

@@ -44,5 +44,6 @@ using namespace mi;
 #include "host/nv12_frames.inc.hpp"     // NV12 frames as a list of pitched plane addresses (decoder surfaces, tensor lists)
 #include "host/p010_frames.inc.hpp"     // P010 frames as such a list (the 16-bit kernels' *_frames_kernel entries)
 #include "host/packed422.inc.hpp"      // packed 4:2:2 frames (YUY2 / UYVY): luma at a 2-byte sample stride, in place in the frame
+#include "host/packed422_frames.inc.hpp"   // packed 4:2:2 frames as a list of pitched buffers (a capture device's buffer pool)
 #include "host/pipe.inc.hpp"
 #include "host/diff.inc.hpp"

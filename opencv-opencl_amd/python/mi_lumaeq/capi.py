@@ -48,6 +48,7 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_nv12_frames_dev", "mi_clahe_nv12_frames_dev",
     "mi_clahe_p010_frames_dev",
     "mi_equalize_hist_packed422_batch_dev", "mi_clahe_packed422_batch_dev", "mi_equalize_hist_packed422", "mi_clahe_packed422",
+    "mi_equalize_hist_packed422_frames_dev", "mi_clahe_packed422_frames_dev",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -70,6 +71,11 @@ class _PipeConfig(C.Structure):
 class Nv12FrameDev(C.Structure):
     """mi_nv12_frame_dev: one NV12 frame of a list, its four plane addresses (device pointers)."""
     _fields_ = [("y_in", C.c_void_p), ("uv_in", C.c_void_p), ("y_out", C.c_void_p), ("uv_out", C.c_void_p)]
+
+
+class Packed422FrameDev(C.Structure):
+    """mi_packed422_frame_dev: one packed 4:2:2 frame of a list, its input and output address (device pointers)."""
+    _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p)]
 
 
 class MiError(RuntimeError):
@@ -157,6 +163,8 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_packed422_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_packed422.argtypes = [vp, vp, sz, vp, sz, i, i, i, i]
     L.mi_clahe_packed422.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, d, i, i]
+    L.mi_equalize_hist_packed422_frames_dev.argtypes = [vp, C.POINTER(Packed422FrameDev), i, i, i, sz, sz, i, i, vp]
+    L.mi_clahe_packed422_frames_dev.argtypes = [vp, C.POINTER(Packed422FrameDev), i, i, i, sz, sz, i, i, d, i, i, vp]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -269,6 +277,21 @@ def _frame_list(inputs, outputs, width, pitches, what):
         arr[k] = Nv12FrameDev(_dptr(y_in[k]), None if uv_in[k] is None else _dptr(uv_in[k]), _dptr(y_out[k]),
                                None if uv_out[k] is None else _dptr(uv_out[k]))
     return arr, len(inputs), p
+
+
+def _packed422_list(inputs, outputs, width, in_pitch, out_pitch, what):
+    """inputs / outputs: sequences of packed frames (torch CUDA tensors or raw device addresses); outputs None = in place.  Returns
+    the mi_packed422_frame_dev array, its length and the two pitches (given, else the 2-D tensors' row stride, else 2 * width)."""
+    inputs = list(inputs)
+    outputs = inputs if outputs is None else list(outputs)
+    if len(outputs) != len(inputs):
+        raise MiError(1, what, f"{len(inputs)} inputs but {len(outputs)} outputs")
+    ip = _plane_pitch(inputs, in_pitch, 2 * int(width), what)
+    op = _plane_pitch(outputs, out_pitch, 2 * int(width), what)
+    arr = (Packed422FrameDev * max(1, len(inputs)))()
+    for k in range(len(inputs)):
+        arr[k] = Packed422FrameDev(_dptr(inputs[k]), _dptr(outputs[k]))
+    return arr, len(inputs), ip, op
 
 
 _live_contexts: "weakref.WeakSet[Context]" = weakref.WeakSet()
@@ -581,6 +604,23 @@ class Context:
         self._chk(self._L.mi_clahe_packed422_batch_dev(self._h, _dptr(d_in), ip, fi, _dptr(d_out), op, fo, int(width), int(height),
                                                      int(n_frames), int(fmt), int(uv_mode), float(clip_limit), int(tiles_x),
                                                      int(tiles_y), stream), "mi_clahe_packed422_batch_dev")
+
+    def equalize_hist_packed422_frames(self, inputs, outputs, width, height, fmt=FMT_YUY2, uv_mode=UV_COPY, in_pitch=None,
+                                       out_pitch=None, stream=0):
+        """mi_equalize_hist_packed422_frames_dev.  inputs / outputs: lists of packed frames, each its own buffer -- torch CUDA tensors
+        or raw device addresses; outputs None = every frame in place.  A pitch left at None is the row stride of the 2-D tensors of
+        that side, or 2 * width."""
+        arr, n, ip, op = _packed422_list(inputs, outputs, width, in_pitch, out_pitch, "equalize_hist_packed422_frames")
+        self._chk(self._L.mi_equalize_hist_packed422_frames_dev(self._h, arr, n, int(width), int(height), ip, op, int(fmt), int(uv_mode),
+                                                              stream), "mi_equalize_hist_packed422_frames_dev")
+
+    def clahe_packed422_frames(self, inputs, outputs, width, height, fmt=FMT_YUY2, uv_mode=UV_COPY, clip_limit=2.0, tiles_x=8,
+                               tiles_y=8, in_pitch=None, out_pitch=None, stream=0):
+        """mi_clahe_packed422_frames_dev; arguments as equalize_hist_packed422_frames, plus the CLAHE parameters."""
+        arr, n, ip, op = _packed422_list(inputs, outputs, width, in_pitch, out_pitch, "clahe_packed422_frames")
+        self._chk(self._L.mi_clahe_packed422_frames_dev(self._h, arr, n, int(width), int(height), ip, op, int(fmt), int(uv_mode),
+                                                      float(clip_limit), int(tiles_x), int(tiles_y), stream),
+                  "mi_clahe_packed422_frames_dev")
 
     # ---- colour-domain neighbours (N3) ----
     @staticmethod
