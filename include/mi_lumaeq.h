@@ -351,6 +351,46 @@ mi_status mi_clahe_packed422_frames_dev(mi_ctx* ctx, const mi_packed422_frame_de
                                         int width, int height, size_t in_pitch, size_t out_pitch,
                                         int format, mi_uv_mode uv_mode,
                                         double clip_limit, int tiles_x, int tiles_y, void* stream);
+/* mi_*_packed422_to_nv12_batch_dev: packed 4:2:2 frames in, NV12 frames out, in the pass that equalizes -- capture card -> encoder
+ * without a format conversion of its own (every pipeline of the reference hands NV12 to its encoder).  The packed frame is read twice
+ * (histograms, then map) exactly as by mi_*_packed422_batch_dev; the second pass writes 1.5*W*H bytes instead of 2*W*H.
+ *   input  : exactly what mi_*_packed422_batch_dev takes.  `format` is MI_FMT_YUY2 or MI_FMT_UYVY; frame f lies at
+ *            d_in + f * in_frame_stride, H rows of 2*W bytes at in_pitch; the pointer, the pitch and the frame stride are multiples
+ *            of 4.  The input is never written.
+ *   output : frame f has a Y plane at d_y_out + f * out_frame_stride, H rows of W bytes at y_pitch, and a UV plane at
+ *            d_uv_out + f * out_frame_stride, H/2 rows of W bytes (interleaved U and V) at uv_pitch.  A tight NV12 batch is
+ *            d_uv_out = d_y_out + W*H, both pitches W, out_frame_stride = W*H*3/2; pitched encoder surfaces in one allocation are the
+ *            general case.  Both output pointers, both pitches and out_frame_stride are multiples of 4; y_pitch >= W, uv_pitch >= W.
+ *            Consequence: a TIGHT NV12 batch with W % 4 == 2 has a pitch that is not a multiple of 4 and is refused -- such a caller
+ *            pads the pitch.
+ *   luma   : byte for byte what mi_equalize_hist_u8_batch_dev / mi_clahe_u8_batch_dev return on the gathered W x H luma plane, hence
+ *            also what mi_*_packed422_batch_dev put into the packed output (same clahe_fp_contract option, REFLECT_101 padding when
+ *            the tile grid does not divide the frame, the same fallback for tile grids too wide for the LDS pair table).
+ *   chroma : MI_UV_FILL128 sets every UV byte to 128.  MI_UV_COPY keeps the chroma and halves it vertically: for UV row r, the U (and
+ *            the V) sample of macropixel m is the rounding mean of input rows 2r and 2r+1, (a + b + 1) >> 1 on the two input bytes.
+ *            No horizontal filtering and no change of siting.  OpenCV has no call for this conversion and the reference has none: the
+ *            rule is this header's own, it has no outside pin.
+ * Nothing outside the W bytes of each output row is written: not the pitch padding, not the space between the planes, not the gap
+ * between frames.  `width` is even; `height` is even too (NV12 has half as many chroma rows).
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of
+ * the same shape as mi_*_packed422_batch_dev.  Never the fused equalizeHist kernel nor the single-launch histogram + LUT kernel; the
+ * chroma is written by the launch that writes the luma (equalizeHist on up to one chunk of frames: one MI_K_HIST, one MI_K_EQ_LUT and
+ * one MI_K_LUT_APPLY launch, for either uv_mode); launches are charged to the existing profiling slots by role.
+ * Errors, MI_ERR_BAD_ARG: a null ctx or any null frame pointer, an odd width or an odd height, a negative size, in_pitch < 2*W,
+ * y_pitch < W or uv_pitch < W, any pointer / pitch / stride that is not a multiple of 4, a format other than the two, a bad uv_mode,
+ * tiles <= 0, d_y_out == d_in or d_uv_out == d_in (the layouts differ: there is no in-place form).  width, height or n_frames of 0:
+ * MI_OK, nothing written -- except that the shape rules come first: an odd width or an odd height is MI_ERR_BAD_ARG even when another
+ * size is 0 (as an odd width is for the packed forms).  Sizes and tile grids the planar forms refuse: the status they give (MI_ERR_UNSUPPORTED), nothing written.
+ * Any other overlap of input and output: undefined, not checked.  Nothing is enqueued unless all checks pass. */
+mi_status mi_equalize_hist_packed422_to_nv12_batch_dev(mi_ctx* ctx,
+        const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        void* d_y_out, size_t y_pitch, void* d_uv_out, size_t uv_pitch, size_t out_frame_stride,
+        int width, int height, int n_frames, int format, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_packed422_to_nv12_batch_dev(mi_ctx* ctx,
+        const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        void* d_y_out, size_t y_pitch, void* d_uv_out, size_t uv_pitch, size_t out_frame_stride,
+        int width, int height, int n_frames, int format, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
 
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at

@@ -97,17 +97,22 @@ mi_status launch_tile_luts422(mi_ctx* c, hipStream_t s, const Packed422& p, cons
     return MI_OK;
 }
 
-// launch_interp's choice of tables, column segments, bands and sub-bands
-template <int OFF>
-mi_status launch_interp422(mi_ctx* c, hipStream_t s, const Packed422& p, const ClaheGeom& g, int nf, const uint8_t* d_luts,
-                           const Packed422List* fl = nullptr)
+// launch_interp's choice of tables, column segments, bands and sub-bands, computed once for every writer of packed input (the packed
+// kernels below, the NV12 writers of packed422_nv12.inc.hpp).  global: the grid is too wide for the LDS pair table.
+struct Interp422Plan {
+    bool global, float_tables;
+    dim3 grid;
+    size_t lds;
+    int subs, groups, cap;
+};
+mi_status plan_interp422(mi_ctx* c, const ClaheGeom& g, int dwords, int nf, Interp422Plan* pl)
 {
     const int npairs = g.tiles_x + 1;
-    if (npairs > kMaxPairsLds) {
+    pl->global = npairs > kMaxPairsLds;
+    pl->float_tables = false; pl->lds = 0; pl->subs = pl->groups = pl->cap = 0;
+    if (pl->global) {
         if (g.height > kMaxGridY) return fail(c, MI_ERR_UNSUPPORTED, "height > 65535 with tiles_x > 62");
-        const dim3 grid((p.dwords + kThreads - 1) / kThreads, g.height, nf);
-        if (fl) LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp422_global_frames_kernel<OFF>, grid, dim3(kThreads), 0, *fl, p, g, d_luts);
-        else    LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp422_global_kernel<OFF>, grid, dim3(kThreads), 0, p, g, d_luts);
+        pl->grid = dim3((dwords + kThreads - 1) / kThreads, g.height, nf);
         return MI_OK;
     }
     const int ngroups = (g.width + kInterpPx - 1) / kInterpPx;
@@ -128,22 +133,45 @@ mi_status launch_interp422(mi_ctx* c, hipStream_t s, const Packed422& p, const C
     const int rows_per_band = g.tile_h + 2 * kBandMargin;
     const int subs = (int)std::max<long long>(1, std::min<long long>({want, (long long)std::max(1, rows_per_band / 8), 64LL}));
     if ((long long)bands * subs > 0x7fffffffLL || segs > kMaxGridY) return fail(c, MI_ERR_UNSUPPORTED, "image too wide");
-    const dim3 grid(bands * subs, nf, segs);
+    pl->grid = dim3(bands * subs, nf, segs);
+    pl->subs = subs; pl->groups = groups;
     if ((npairs <= kMaxPairsLdsF32 || seg_tables) && c->clahe_float_tables) {
-        const int cap = seg_tables ? seg_cap : kMaxPairsLdsF32;
-        const size_t lds = (size_t)std::min(npairs, cap) * 256 * 4 * sizeof(float);
+        pl->float_tables = true;
+        pl->cap = seg_tables ? seg_cap : kMaxPairsLdsF32;
+        pl->lds = (size_t)std::min(npairs, pl->cap) * 256 * 4 * sizeof(float);
+    } else {
+        pl->cap = kMaxPairsLds + 1;
+        pl->lds = (size_t)npairs * 256 * sizeof(uint32_t);
+    }
+    return MI_OK;
+}
+
+template <int OFF>
+mi_status launch_interp422(mi_ctx* c, hipStream_t s, const Packed422& p, const ClaheGeom& g, int nf, const uint8_t* d_luts,
+                           const Packed422List* fl = nullptr)
+{
+    Interp422Plan pl;
+    if (mi_status st = plan_interp422(c, g, p.dwords, nf, &pl)) return st;
+    const dim3 grid = pl.grid;
+    const size_t lds = pl.lds;
+    const int subs = pl.subs, groups = pl.groups, cap = pl.cap;
+    if (pl.global) {
+        if (fl) LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp422_global_frames_kernel<OFF>, grid, dim3(kThreads), 0, *fl, p, g, d_luts);
+        else    LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp422_global_kernel<OFF>, grid, dim3(kThreads), 0, p, g, d_luts);
+        return MI_OK;
+    }
+    if (pl.float_tables) {
         if (fl) {
             if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_frames_kernel<true, true, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
             else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_frames_kernel<true, false, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
         } else if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<true, true, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
         else                   LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<true, false, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
     } else {
-        const size_t lds = (size_t)npairs * 256 * sizeof(uint32_t);
         if (fl) {
-            if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_frames_kernel<false, true, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, kMaxPairsLds + 1);
-            else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_frames_kernel<false, false, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, kMaxPairsLds + 1);
-        } else if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<false, true, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, kMaxPairsLds + 1);
-        else                   LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<false, false, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, kMaxPairsLds + 1);
+            if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_frames_kernel<false, true, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
+            else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_frames_kernel<false, false, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
+        } else if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<false, true, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
+        else                   LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<false, false, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
     }
     return MI_OK;
 }

@@ -45,5 +45,6 @@ using namespace mi;
 #include "host/p010_frames.inc.hpp"     // P010 frames as such a list (the 16-bit kernels' *_frames_kernel entries)
 #include "host/packed422.inc.hpp"      // packed 4:2:2 frames (YUY2 / UYVY): luma at a 2-byte sample stride, in place in the frame
 #include "host/packed422_frames.inc.hpp"   // packed 4:2:2 frames as a list of pitched buffers (a capture device's buffer pool)
+#include "host/packed422_nv12.inc.hpp"     // packed 4:2:2 frames in, NV12 frames out (capture card -> encoder in one pass)
 #include "host/pipe.inc.hpp"
 #include "host/diff.inc.hpp"

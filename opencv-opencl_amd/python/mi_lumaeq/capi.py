@@ -49,6 +49,7 @@ DECLARED_SYMBOLS = [
     "mi_clahe_p010_frames_dev",
     "mi_equalize_hist_packed422_batch_dev", "mi_clahe_packed422_batch_dev", "mi_equalize_hist_packed422", "mi_clahe_packed422",
     "mi_equalize_hist_packed422_frames_dev", "mi_clahe_packed422_frames_dev",
+    "mi_equalize_hist_packed422_to_nv12_batch_dev", "mi_clahe_packed422_to_nv12_batch_dev",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -165,6 +166,8 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_packed422.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, d, i, i]
     L.mi_equalize_hist_packed422_frames_dev.argtypes = [vp, C.POINTER(Packed422FrameDev), i, i, i, sz, sz, i, i, vp]
     L.mi_clahe_packed422_frames_dev.argtypes = [vp, C.POINTER(Packed422FrameDev), i, i, i, sz, sz, i, i, d, i, i, vp]
+    L.mi_equalize_hist_packed422_to_nv12_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, vp, sz, sz, i, i, i, i, i, vp]
+    L.mi_clahe_packed422_to_nv12_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, vp, sz, sz, i, i, i, i, i, d, i, i, vp]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -621,6 +624,39 @@ class Context:
         self._chk(self._L.mi_clahe_packed422_frames_dev(self._h, arr, n, int(width), int(height), ip, op, int(fmt), int(uv_mode),
                                                       float(clip_limit), int(tiles_x), int(tiles_y), stream),
                   "mi_clahe_packed422_frames_dev")
+
+    @staticmethod
+    def _nv12_out(d_y_out, d_uv_out, width, height, y_pitch, uv_pitch, out_frame):
+        """Addresses and strides of the NV12 side; d_uv_out None: the UV plane directly behind the Y plane (y_pitch * H further)."""
+        yp = int(width) if y_pitch is None else int(y_pitch)
+        up = int(width) if uv_pitch is None else int(uv_pitch)
+        y = _dptr(d_y_out)
+        uv = _dptr(d_uv_out) if d_uv_out is not None else (y + yp * int(height) if y else y)
+        fo = yp * int(height) + up * (int(height) // 2) if out_frame is None else int(out_frame)
+        return y, yp, uv, up, fo
+
+    def equalize_hist_packed422_to_nv12_batch_dev(self, d_in, d_y_out, d_uv_out, width, height, n_frames, fmt=FMT_YUY2, uv_mode=UV_COPY,
+                                                  in_pitch=None, in_frame=None, y_pitch=None, uv_pitch=None, out_frame=None, stream=0):
+        """mi_equalize_hist_packed422_to_nv12_batch_dev: n_frames packed frames in, NV12 frames out (torch tensors or raw addresses).
+        Tight layouts are the defaults: in_pitch 2*W, in_frame in_pitch * H, y_pitch = uv_pitch = W, out_frame = y_pitch * H +
+        uv_pitch * H/2; d_uv_out None puts the UV plane directly behind the Y plane (one tight NV12 batch in d_y_out)."""
+        ip = 2 * width if in_pitch is None else in_pitch
+        fi = ip * height if in_frame is None else in_frame
+        y, yp, uv, up, fo = self._nv12_out(d_y_out, d_uv_out, width, height, y_pitch, uv_pitch, out_frame)
+        self._chk(self._L.mi_equalize_hist_packed422_to_nv12_batch_dev(self._h, _dptr(d_in), ip, fi, y, yp, uv, up, fo, int(width),
+                                                                     int(height), int(n_frames), int(fmt), int(uv_mode), stream),
+                  "mi_equalize_hist_packed422_to_nv12_batch_dev")
+
+    def clahe_packed422_to_nv12_batch_dev(self, d_in, d_y_out, d_uv_out, width, height, n_frames, fmt=FMT_YUY2, uv_mode=UV_COPY,
+                                          clip_limit=2.0, tiles_x=8, tiles_y=8, in_pitch=None, in_frame=None, y_pitch=None,
+                                          uv_pitch=None, out_frame=None, stream=0):
+        """mi_clahe_packed422_to_nv12_batch_dev; arguments as equalize_hist_packed422_to_nv12_batch_dev, plus the CLAHE parameters."""
+        ip = 2 * width if in_pitch is None else in_pitch
+        fi = ip * height if in_frame is None else in_frame
+        y, yp, uv, up, fo = self._nv12_out(d_y_out, d_uv_out, width, height, y_pitch, uv_pitch, out_frame)
+        self._chk(self._L.mi_clahe_packed422_to_nv12_batch_dev(self._h, _dptr(d_in), ip, fi, y, yp, uv, up, fo, int(width), int(height),
+                                                             int(n_frames), int(fmt), int(uv_mode), float(clip_limit), int(tiles_x),
+                                                             int(tiles_y), stream), "mi_clahe_packed422_to_nv12_batch_dev")
 
     # ---- colour-domain neighbours (N3) ----
     @staticmethod
