@@ -391,6 +391,56 @@ mi_status mi_clahe_packed422_to_nv12_batch_dev(mi_ctx* ctx,
         void* d_y_out, size_t y_pitch, void* d_uv_out, size_t uv_pitch, size_t out_frame_stride,
         int width, int height, int n_frames, int format, mi_uv_mode uv_mode,
         double clip_limit, int tiles_x, int tiles_y, void* stream);
+/* mi_*_packed422_to_nv12_frames_dev: the same conversion on a LIST of device frames, each at its own three addresses -- a capture
+ * device's buffer pool in (every YUY2 / UYVY buffer its own allocation, as for mi_*_packed422_frames_dev), an encoder's surface pool
+ * out (every NV12 surface its own pitched Y and UV plane, as for mi_*_nv12_frames_dev).  The contract is the union of the two forms it
+ * joins.  `frames` is a host array of n_frames entries, read only during the call; the pointers in it are device pointers on the
+ * context's device.  Every frame of one call has the same width, height, format and the same three pitches (bytes between rows):
+ *   in    : H rows of 2*W bytes at in_pitch >= 2*W       y_out : H rows of W bytes at y_pitch >= W
+ *   uv_out: H/2 rows of W bytes (interleaved U and V) at uv_pitch >= W
+ * Width and height are even.  Every address and every pitch is a multiple of 4; each frame may have its own alignment modulo 16
+ * (slower never by design, different bytes never).  As in the batch form, a TIGHT NV12 pitch with W % 4 == 2 is not a multiple of 4
+ * and is refused here: such a caller pads the pitch (the host form below accepts it).  The same input may appear in several entries.
+ * The luma and the chroma of every frame are byte for byte what mi_*_packed422_to_nv12_batch_dev writes for that frame: the same
+ * clahe_fp_contract option, REFLECT_101 padding, the same fallback for tile grids too wide for the LDS tables, (a + b + 1) >> 1 chroma
+ * under MI_UV_COPY and 128 under MI_UV_FILL128.  Nothing outside the W bytes of each output row is written; the inputs are never
+ * written.
+ * There is no in-place form (the layouts differ): MI_ERR_BAD_ARG when the rows of a frame's Y or UV output meet the rows of its own
+ * input, or when its Y rows meet its UV rows.  Outputs of DIFFERENT frames that overlap each other (or another frame's input) give
+ * undefined results and are not checked.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of
+ * the same shape as mi_*_packed422_frames_dev.  Never the fused equalizeHist kernel nor the single-launch histogram + LUT kernel;
+ * launches are charged to the existing profiling slots by role (equalizeHist: one MI_K_HIST, one MI_K_EQ_LUT and one MI_K_LUT_APPLY
+ * launch per chunk of the list, for either uv_mode).
+ * Errors, MI_ERR_BAD_ARG: a null ctx, a null `frames` with n_frames > 0, a null in / y_out / uv_out, an odd width or an odd height
+ * (refused even when another size is 0), a negative size, a format other than MI_FMT_YUY2 / MI_FMT_UYVY, a bad uv_mode, tiles <= 0,
+ * in_pitch < 2*W, y_pitch < W or uv_pitch < W, any address or pitch that is not a multiple of 4, the overlaps above.  Sizes and tile
+ * grids the planar forms refuse: the status they give (MI_ERR_UNSUPPORTED), nothing written.  n_frames, width or height of 0: MI_OK,
+ * nothing written.  Nothing is enqueued unless every frame passes the checks.
+ *
+ * mi_equalize_hist_packed422_to_nv12 / mi_clahe_packed422_to_nv12: ONE host frame, synchronous, like mi_*_packed422: the packed frame
+ * goes up (2 bytes per pixel), the two planes come back (1.5 bytes per pixel).  The input side follows the rules of mi_*_packed422
+ * (`in` and in_pitch multiples of 4, in_pitch >= 2*W; only the 2*W bytes of each row are read).  The output side is host memory the
+ * kernels never see: y_out and uv_out may lie at ANY address, y_pitch and uv_pitch are any values >= W -- a tight host NV12 frame with
+ * W % 4 == 2 is accepted (the device staging is pitched, the rows are copied out).  Only the W bytes of each output row are written.
+ * Planes in memory registered with mi_host_register (or otherwise found pinned) that are tight, with W % 4 == 0 for the outputs, are
+ * DMA'd as they are; everything else goes through the context's pinned staging (statistics "host_planes_direct" /
+ * "host_planes_staged", three planes a call).  Whatever the call returns, no copy on in / y_out / uv_out is in flight any more when it
+ * returns.  MI_ERR_BAD_ARG when the rows of an output plane meet the rows of the input or of the other plane; shape, mode, size and
+ * zero-size rules as the device form above. */
+typedef struct mi_packed422_nv12_frame_dev { const void* in; void* y_out; void* uv_out; } mi_packed422_nv12_frame_dev;
+mi_status mi_equalize_hist_packed422_to_nv12_frames_dev(mi_ctx* ctx, const mi_packed422_nv12_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t y_pitch, size_t uv_pitch,
+        int format, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_packed422_to_nv12_frames_dev(mi_ctx* ctx, const mi_packed422_nv12_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t y_pitch, size_t uv_pitch,
+        int format, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y, void* stream);
+mi_status mi_equalize_hist_packed422_to_nv12(mi_ctx* ctx, const uint8_t* in, size_t in_pitch,
+        uint8_t* y_out, size_t y_pitch, uint8_t* uv_out, size_t uv_pitch,
+        int width, int height, int format, mi_uv_mode uv_mode);
+mi_status mi_clahe_packed422_to_nv12(mi_ctx* ctx, const uint8_t* in, size_t in_pitch,
+        uint8_t* y_out, size_t y_pitch, uint8_t* uv_out, size_t uv_pitch,
+        int width, int height, int format, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
 
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at

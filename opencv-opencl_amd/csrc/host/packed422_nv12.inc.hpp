@@ -56,9 +56,20 @@ Packed422Nv12 packed422_nv12_batch(const P422Nv12Args& a, int f0)
     return p;
 }
 
+// One chunk of a frame list (mi_*_packed422_to_nv12_frames_dev, packed422_nv12_frames.inc.hpp): the inputs as the histogram stages'
+// Packed422List (they only read: out mirrors in, as in p422_nv12_args) and the three addresses of every frame for the writers.
+struct P422Nv12Lists {
+    Packed422List in;
+    Packed422Nv12List io;
+};
+
+// The stage sequences below take an optional chunk of a frame list (a.in.n_frames of its entries, indices from 0): with one, every
+// launch goes to the *_frames_kernel entry of the same body -- same grids, same splits, same scratch -- and the base addresses and
+// frame strides of `a` are not used.
+
 // equalize422_dev with the NV12 writer as its last stage: one MI_K_HIST, one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch per chunk
 template <int OFF>
-mi_status equalize422_nv12_dev(mi_ctx* c, hipStream_t s, const P422Nv12Args& a)
+mi_status equalize422_nv12_dev(mi_ctx* c, hipStream_t s, const P422Nv12Args& a, const P422Nv12Lists* fl = nullptr)
 {
     const int width = a.in.width, height = a.in.height;
     const long long frame_bytes = 2LL * width * height;
@@ -70,18 +81,21 @@ mi_status equalize422_nv12_dev(mi_ctx* c, hipStream_t s, const P422Nv12Args& a)
         mi_status st = grow_dev(c, &c->d_partial, &c->partial_bytes, (size_t)nf * B * 256 * sizeof(uint32_t));
         if (st) return st;
         if ((st = grow_dev(c, &c->d_luts, &c->luts_bytes, (size_t)nf * 256))) return st;
-        LAUNCH(c, s, MI_K_HIST, hist422_partial_kernel<OFF>, dim3(B, nf), dim3(kHistThreads), 0, pin, c->d_partial);
+        if (fl) LAUNCH(c, s, MI_K_HIST, hist422_partial_frames_kernel<OFF>, dim3(B, nf), dim3(kHistThreads), 0, fl->in, pin, c->d_partial);
+        else    LAUNCH(c, s, MI_K_HIST, hist422_partial_kernel<OFF>, dim3(B, nf), dim3(kHistThreads), 0, pin, c->d_partial);
         LAUNCH(c, s, MI_K_EQ_LUT, equalize_lut_kernel, dim3(nf), dim3(kThreads), 0,
                (const uint32_t*)c->d_partial, B, (int)((long long)width * height), c->d_luts, (int32_t*)nullptr);
         const int BA = blocks_per_frame(c, frame_bytes, height / 2, nf, 2048);       // bands of row pairs
-        LAUNCH(c, s, MI_K_LUT_APPLY, lut_apply422_nv12_kernel<OFF>, dim3(BA, nf), dim3(kThreads), 0, p, (const uint8_t*)c->d_luts);
+        if (fl) LAUNCH(c, s, MI_K_LUT_APPLY, lut_apply422_nv12_frames_kernel<OFF>, dim3(BA, nf), dim3(kThreads), 0, fl->io, p, (const uint8_t*)c->d_luts);
+        else    LAUNCH(c, s, MI_K_LUT_APPLY, lut_apply422_nv12_kernel<OFF>, dim3(BA, nf), dim3(kThreads), 0, p, (const uint8_t*)c->d_luts);
     }
     return MI_OK;
 }
 
 // launch_interp422 on the NV12 writers: the same plan (plan_interp422: tables, column segments, bands, sub-bands), other kernels
 template <int OFF>
-mi_status launch_interp422_nv12(mi_ctx* c, hipStream_t s, const Packed422Nv12& p, const ClaheGeom& g, int nf, const uint8_t* d_luts)
+mi_status launch_interp422_nv12(mi_ctx* c, hipStream_t s, const Packed422Nv12& p, const ClaheGeom& g, int nf, const uint8_t* d_luts,
+                                const Packed422Nv12List* fl = nullptr)
 {
     Interp422Plan pl;
     if (mi_status st = plan_interp422(c, g, p.dwords, nf, &pl)) return st;
@@ -89,19 +103,27 @@ mi_status launch_interp422_nv12(mi_ctx* c, hipStream_t s, const Packed422Nv12& p
     const size_t lds = pl.lds;
     const int subs = pl.subs, groups = pl.groups, cap = pl.cap;
     if (pl.global) {
-        LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp422_nv12_global_kernel<OFF>, grid, dim3(kThreads), 0, p, g, d_luts);
+        if (fl) LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp422_nv12_global_frames_kernel<OFF>, grid, dim3(kThreads), 0, *fl, p, g, d_luts);
+        else    LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp422_nv12_global_kernel<OFF>, grid, dim3(kThreads), 0, p, g, d_luts);
     } else if (pl.float_tables) {
-        if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_kernel<true, true, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
-        else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_kernel<true, false, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
+        if (fl) {
+            if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_frames_kernel<true, true, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
+            else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_frames_kernel<true, false, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
+        } else if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_kernel<true, true, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
+        else                   LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_kernel<true, false, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
     } else {
-        if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_kernel<false, true, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
-        else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_kernel<false, false, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
+        if (fl) {
+            if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_frames_kernel<false, true, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
+            else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_frames_kernel<false, false, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
+        } else if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_kernel<false, true, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
+        else                   LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_kernel<false, false, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
     }
     return MI_OK;
 }
 
 template <int OFF>
-mi_status clahe422_nv12_dev(mi_ctx* c, hipStream_t s, const P422Nv12Args& a, double clip_limit, int tiles_x, int tiles_y)
+mi_status clahe422_nv12_dev(mi_ctx* c, hipStream_t s, const P422Nv12Args& a, double clip_limit, int tiles_x, int tiles_y,
+                            const P422Nv12Lists* fl = nullptr)
 {
     ClaheGeom g;
     mi_status st = clahe_geometry(c, a.in.width, a.in.height, clip_limit, tiles_x, tiles_y, &g);
@@ -112,10 +134,18 @@ mi_status clahe422_nv12_dev(mi_ctx* c, hipStream_t s, const P422Nv12Args& a, dou
         const Packed422 pin = packed422_batch(a.in, f0);
         const Packed422Nv12 p = packed422_nv12_batch(a, f0);
         if ((st = grow_dev(c, &c->d_luts, &c->luts_bytes, (size_t)nf * tiles * 256))) return st;
-        if ((st = launch_tile_luts422<OFF>(c, s, pin, g, nf, c->d_luts))) return st;
-        if ((st = launch_interp422_nv12<OFF>(c, s, p, g, nf, c->d_luts))) return st;
+        if ((st = launch_tile_luts422<OFF>(c, s, pin, g, nf, c->d_luts, fl ? &fl->in : nullptr))) return st;
+        if ((st = launch_interp422_nv12<OFF>(c, s, p, g, nf, c->d_luts, fl ? &fl->io : nullptr))) return st;
     }
     return MI_OK;
+}
+
+// op: 0 equalizeHist, 1 CLAHE.  `a` has passed check_packed422_nv12 (with a list: check_packed422_nv12_frames).
+mi_status packed422_nv12_dev(mi_ctx* c, hipStream_t s, const P422Nv12Args& a, int op, double clip_limit, int tiles_x, int tiles_y,
+                             const P422Nv12Lists* fl = nullptr)
+{
+    if (a.in.format == MI_FMT_UYVY) return op ? clahe422_nv12_dev<1>(c, s, a, clip_limit, tiles_x, tiles_y, fl) : equalize422_nv12_dev<1>(c, s, a, fl);
+    return op ? clahe422_nv12_dev<0>(c, s, a, clip_limit, tiles_x, tiles_y, fl) : equalize422_nv12_dev<0>(c, s, a, fl);
 }
 
 }  // namespace

@@ -33,6 +33,31 @@ struct Strided422Nv12 {
     __device__ __forceinline__ uint8_t* uv_of(long long f) const { return p.uv + f * p.out_frame; }
 };
 
+// A list of such frames, each at its own three addresses (mi_*_packed422_to_nv12_frames_dev: a capture pool in, an encoder's surface
+// pool out).  The {in, y, uv} entries travel BY VALUE in the kernel arguments like Packed422List -- 24 B an entry -- and are read with
+// scalar kernarg loads indexed by the frame's grid coordinate.  The shape (pitches, dwords, rows, copy_uv) is the launch's
+// Packed422Nv12, whose src / y / uv / *_frame a table launch ignores.  128 entries are 3 KiB: with the largest remaining argument list
+// (the interpolation kernel's) and the 256 B of implicit arguments a code object carries behind the explicit ones, a launch stays
+// inside the 4 KiB of kernel arguments HIP accepts -- and the chunks are those of the histogram stages' Packed422List, so 256 frames
+// are two launches per stage.  64 builds too (-DMI_PACKED422_NV12_FRAMES_PER_LAUNCH=64); the host cuts both tables by the smaller one.
+#ifndef MI_PACKED422_NV12_FRAMES_PER_LAUNCH
+#define MI_PACKED422_NV12_FRAMES_PER_LAUNCH 128
+#endif
+constexpr int kPacked422Nv12FramesPerLaunch = MI_PACKED422_NV12_FRAMES_PER_LAUNCH;
+static_assert(kPacked422Nv12FramesPerLaunch == 64 || kPacked422Nv12FramesPerLaunch == 128, "a table is 1.5 or 3 KiB of kernel arguments");
+struct Packed422Nv12Frame { const uint8_t* in; uint8_t* y; uint8_t* uv; };
+struct Packed422Nv12List { Packed422Nv12Frame f[kPacked422Nv12FramesPerLaunch]; };
+static_assert(sizeof(Packed422Nv12Frame) == 24, "three addresses an entry");
+// clahe_interp422_nv12_frames_kernel(l, p, g, luts, subs, groups, pair_cap) is the longest list; 256: the implicit arguments
+static_assert(sizeof(Packed422Nv12List) + sizeof(Packed422Nv12) + 8 + sizeof(ClaheGeom) + 8 + sizeof(const uint8_t*) + 3 * sizeof(int) + 8 + 256 <= 4096,
+              "the table and the largest remaining argument list stay within HIP's 4 KiB of kernel arguments");
+struct Table422Nv12 {
+    const Packed422Nv12List& l;
+    __device__ __forceinline__ const uint8_t* src_of(long long f) const { return l.f[f].in; }
+    __device__ __forceinline__ uint8_t* y_of(long long f) const { return l.f[f].y; }
+    __device__ __forceinline__ uint8_t* uv_of(long long f) const { return l.f[f].uv; }
+};
+
 // per-byte (a + b + 1) >> 1 of four bytes at once: a | b = (a ^ b) + (a & b) and a + b = (a ^ b) + 2 * (a & b), so the rounded-up mean
 // is (a | b) - ((a ^ b) >> 1); masking the shifted difference with 0x7f keeps a neighbour's low bit out of each byte, and the
 // subtraction never borrows (each byte of the subtrahend is <= the same byte of a | b).
@@ -131,6 +156,11 @@ template <int OFF>
 __global__ __launch_bounds__(kThreads) void lut_apply422_nv12_kernel(Packed422Nv12 p, const uint8_t* __restrict__ luts)
 {
     lut_apply422_nv12_body<OFF>(p, Strided422Nv12{p}, luts);
+}
+template <int OFF>
+__global__ __launch_bounds__(kThreads) void lut_apply422_nv12_frames_kernel(Packed422Nv12List l, Packed422Nv12 p, const uint8_t* __restrict__ luts)
+{
+    lut_apply422_nv12_body<OFF>(p, Table422Nv12{l}, luts);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -289,6 +319,12 @@ __global__ __launch_bounds__(kThreads) void clahe_interp422_nv12_kernel(Packed42
 {
     clahe_interp422_nv12_body<FT, FMA, OFF>(p, Strided422Nv12{p}, g, luts, subs, groups, pair_cap);
 }
+template <bool FT, bool FMA, int OFF>
+__global__ __launch_bounds__(kThreads) void clahe_interp422_nv12_frames_kernel(Packed422Nv12List l, Packed422Nv12 p, ClaheGeom g,
+                                                                              const uint8_t* __restrict__ luts, int subs, int groups, int pair_cap)
+{
+    clahe_interp422_nv12_body<FT, FMA, OFF>(p, Table422Nv12{l}, g, luts, subs, groups, pair_cap);
+}
 
 // Fallback for tile grids too wide for the LDS pair table (clahe_interp422_global_kernel's arithmetic): one macropixel per thread, the
 // LUTs gathered from global memory (L2), two luma bytes to the Y plane as one 2-byte store; the thread of an even row also reads the
@@ -333,6 +369,12 @@ template <int OFF>
 __global__ __launch_bounds__(kThreads) void clahe_interp422_nv12_global_kernel(Packed422Nv12 p, ClaheGeom g, const uint8_t* __restrict__ luts)
 {
     clahe_interp422_nv12_global_body<OFF>(p, Strided422Nv12{p}, g, luts);
+}
+template <int OFF>
+__global__ __launch_bounds__(kThreads) void clahe_interp422_nv12_global_frames_kernel(Packed422Nv12List l, Packed422Nv12 p, ClaheGeom g,
+                                                                                     const uint8_t* __restrict__ luts)
+{
+    clahe_interp422_nv12_global_body<OFF>(p, Table422Nv12{l}, g, luts);
 }
 
 }  // namespace mi

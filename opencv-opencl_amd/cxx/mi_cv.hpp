@@ -456,6 +456,24 @@ inline void clahePacked422(const unsigned char* in, size_t inPitch, unsigned cha
     detail::check(c, mi_clahe_packed422(c, in, inPitch, out, outPitch, width, height, (int)format, (mi_uv_mode)uv, clipLimit,
                                         tiles.width, tiles.height), "mi_clahe_packed422");
 }
+// The same frames in, NV12 out (what the encoder takes) in the pass that equalizes: the Y plane (H rows of W bytes at yPitch) and the
+// interleaved UV plane (H/2 rows at uvPitch, the chroma halved vertically with rounding or set to 128) in host memory at any address
+// and any pitch >= W.  Width and height are even; the outputs may not overlap the input or each other.
+inline void equalizeHistPacked422ToNV12(const unsigned char* in, size_t inPitch, unsigned char* yOut, size_t yPitch,
+                                        unsigned char* uvOut, size_t uvPitch, int width, int height, PackedFormat format, UVMode uv)
+{
+    mi_ctx* c = detail::thread_ctx();
+    detail::check(c, mi_equalize_hist_packed422_to_nv12(c, in, inPitch, yOut, yPitch, uvOut, uvPitch, width, height, (int)format,
+                                                        (mi_uv_mode)uv), "mi_equalize_hist_packed422_to_nv12");
+}
+inline void clahePacked422ToNV12(const unsigned char* in, size_t inPitch, unsigned char* yOut, size_t yPitch,
+                                 unsigned char* uvOut, size_t uvPitch, int width, int height, PackedFormat format, UVMode uv,
+                                 double clipLimit, Size tiles)
+{
+    mi_ctx* c = detail::thread_ctx();
+    detail::check(c, mi_clahe_packed422_to_nv12(c, in, inPitch, yOut, yPitch, uvOut, uvPitch, width, height, (int)format,
+                                                (mi_uv_mode)uv, clipLimit, tiles.width, tiles.height), "mi_clahe_packed422_to_nv12");
+}
 
 // BASELINE.json config 5 read literally: cvtColor(COLOR_YUV2BGR_NV12) -> split -> equalizeHist on B, G and R -> merge ->
 // cvtColor(COLOR_BGR2YUV_I420) + U/V interleave, NV12 in -> NV12 out in one call (no file of the reference does this;

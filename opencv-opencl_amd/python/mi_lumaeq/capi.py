@@ -50,6 +50,8 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_packed422_batch_dev", "mi_clahe_packed422_batch_dev", "mi_equalize_hist_packed422", "mi_clahe_packed422",
     "mi_equalize_hist_packed422_frames_dev", "mi_clahe_packed422_frames_dev",
     "mi_equalize_hist_packed422_to_nv12_batch_dev", "mi_clahe_packed422_to_nv12_batch_dev",
+    "mi_equalize_hist_packed422_to_nv12_frames_dev", "mi_clahe_packed422_to_nv12_frames_dev",
+    "mi_equalize_hist_packed422_to_nv12", "mi_clahe_packed422_to_nv12",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -77,6 +79,12 @@ class Nv12FrameDev(C.Structure):
 class Packed422FrameDev(C.Structure):
     """mi_packed422_frame_dev: one packed 4:2:2 frame of a list, its input and output address (device pointers)."""
     _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p)]
+
+
+class Packed422Nv12FrameDev(C.Structure):
+    """mi_packed422_nv12_frame_dev: one frame of a packed 4:2:2 -> NV12 list, its input and its two output plane addresses (device
+    pointers)."""
+    _fields_ = [("in_", C.c_void_p), ("y_out", C.c_void_p), ("uv_out", C.c_void_p)]
 
 
 class MiError(RuntimeError):
@@ -168,6 +176,10 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_packed422_frames_dev.argtypes = [vp, C.POINTER(Packed422FrameDev), i, i, i, sz, sz, i, i, d, i, i, vp]
     L.mi_equalize_hist_packed422_to_nv12_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, vp, sz, sz, i, i, i, i, i, vp]
     L.mi_clahe_packed422_to_nv12_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, vp, sz, sz, i, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_packed422_to_nv12_frames_dev.argtypes = [vp, C.POINTER(Packed422Nv12FrameDev), i, i, i, sz, sz, sz, i, i, vp]
+    L.mi_clahe_packed422_to_nv12_frames_dev.argtypes = [vp, C.POINTER(Packed422Nv12FrameDev), i, i, i, sz, sz, sz, i, i, d, i, i, vp]
+    L.mi_equalize_hist_packed422_to_nv12.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, i]
+    L.mi_clahe_packed422_to_nv12.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, i, d, i, i]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -295,6 +307,22 @@ def _packed422_list(inputs, outputs, width, in_pitch, out_pitch, what):
     for k in range(len(inputs)):
         arr[k] = Packed422FrameDev(_dptr(inputs[k]), _dptr(outputs[k]))
     return arr, len(inputs), ip, op
+
+
+def _packed422_nv12_list(inputs, y_outputs, uv_outputs, width, in_pitch, y_pitch, uv_pitch, what):
+    """inputs / y_outputs / uv_outputs: sequences of equal length (torch CUDA tensors or raw device addresses).  Returns the
+    mi_packed422_nv12_frame_dev array, its length and the three pitches (given, else the 2-D tensors' row stride, else 2 * width for
+    the input and width for the planes)."""
+    inputs, y_outputs, uv_outputs = list(inputs), list(y_outputs), list(uv_outputs)
+    if not (len(inputs) == len(y_outputs) == len(uv_outputs)):
+        raise MiError(1, what, f"{len(inputs)} inputs but {len(y_outputs)} Y and {len(uv_outputs)} UV outputs")
+    ip = _plane_pitch(inputs, in_pitch, 2 * int(width), what)
+    yp = _plane_pitch(y_outputs, y_pitch, int(width), what)
+    up = _plane_pitch(uv_outputs, uv_pitch, int(width), what)
+    arr = (Packed422Nv12FrameDev * max(1, len(inputs)))()
+    for k in range(len(inputs)):
+        arr[k] = Packed422Nv12FrameDev(_dptr(inputs[k]), _dptr(y_outputs[k]), _dptr(uv_outputs[k]))
+    return arr, len(inputs), ip, yp, up
 
 
 _live_contexts: "weakref.WeakSet[Context]" = weakref.WeakSet()
@@ -657,6 +685,65 @@ class Context:
         self._chk(self._L.mi_clahe_packed422_to_nv12_batch_dev(self._h, _dptr(d_in), ip, fi, y, yp, uv, up, fo, int(width), int(height),
                                                              int(n_frames), int(fmt), int(uv_mode), float(clip_limit), int(tiles_x),
                                                              int(tiles_y), stream), "mi_clahe_packed422_to_nv12_batch_dev")
+
+    def equalize_hist_packed422_to_nv12_frames(self, inputs, y_outputs, uv_outputs, width, height, fmt=FMT_YUY2, uv_mode=UV_COPY,
+                                               in_pitch=None, y_pitch=None, uv_pitch=None, stream=0):
+        """mi_equalize_hist_packed422_to_nv12_frames_dev.  inputs: the packed frames, y_outputs / uv_outputs: the NV12 planes, each
+        its own buffer -- lists of torch CUDA tensors or raw device addresses, one entry per frame.  A pitch left at None is the row
+        stride of the 2-D tensors of that list, or the tight one (2 * width; width)."""
+        arr, n, ip, yp, up = _packed422_nv12_list(inputs, y_outputs, uv_outputs, width, in_pitch, y_pitch, uv_pitch,
+                                                  "equalize_hist_packed422_to_nv12_frames")
+        self._chk(self._L.mi_equalize_hist_packed422_to_nv12_frames_dev(self._h, arr, n, int(width), int(height), ip, yp, up, int(fmt),
+                                                                      int(uv_mode), stream),
+                  "mi_equalize_hist_packed422_to_nv12_frames_dev")
+
+    def clahe_packed422_to_nv12_frames(self, inputs, y_outputs, uv_outputs, width, height, fmt=FMT_YUY2, uv_mode=UV_COPY,
+                                       clip_limit=2.0, tiles_x=8, tiles_y=8, in_pitch=None, y_pitch=None, uv_pitch=None, stream=0):
+        """mi_clahe_packed422_to_nv12_frames_dev; arguments as equalize_hist_packed422_to_nv12_frames, plus the CLAHE parameters."""
+        arr, n, ip, yp, up = _packed422_nv12_list(inputs, y_outputs, uv_outputs, width, in_pitch, y_pitch, uv_pitch,
+                                                  "clahe_packed422_to_nv12_frames")
+        self._chk(self._L.mi_clahe_packed422_to_nv12_frames_dev(self._h, arr, n, int(width), int(height), ip, yp, up, int(fmt),
+                                                              int(uv_mode), float(clip_limit), int(tiles_x), int(tiles_y), stream),
+                  "mi_clahe_packed422_to_nv12_frames_dev")
+
+    def _nv12_host_out(self, width, h, y_out, uv_out, name):
+        """The two host planes of a packed 4:2:2 -> NV12 call: given (2-D uint8 arrays of at least W bytes per row, any pitch) or new
+        tight ones."""
+        if y_out is None:
+            y_out = np.empty((h, width), np.uint8)
+        if uv_out is None:
+            uv_out = np.empty((h // 2, width), np.uint8)
+        y_out, uv_out = _host2d(y_out, name), _host2d(uv_out, name)
+        if y_out.shape[1] < width or uv_out.shape[1] < width or y_out.shape[0] != h or uv_out.shape[0] != h // 2:
+            raise MiError(1, name, "the NV12 planes are an H x pitch and an H/2 x pitch uint8 array with at least W bytes per row")
+        return y_out, uv_out
+
+    def equalize_hist_packed422_to_nv12(self, frame: np.ndarray, width: int, fmt: int = FMT_YUY2, uv_mode: int = UV_COPY,
+                                        y_out: np.ndarray | None = None, uv_out: np.ndarray | None = None):
+        """mi_equalize_hist_packed422_to_nv12 on a host frame: an H x pitch-bytes uint8 array (pitch >= 2*W) in, the (Y, UV) planes
+        out -- `y_out` (H rows) / `uv_out` (H/2 rows) when given, views with padded rows or odd addresses included, else new tight
+        H x W and H/2 x W arrays."""
+        name = "equalize_hist_packed422_to_nv12"
+        frame = self._packed_host(frame, width, name)
+        h = frame.shape[0]
+        y_out, uv_out = self._nv12_host_out(int(width), h, y_out, uv_out, name)
+        self._chk(self._L.mi_equalize_hist_packed422_to_nv12(self._h, frame.ctypes.data, _step(frame), y_out.ctypes.data, _step(y_out),
+                                                           uv_out.ctypes.data, _step(uv_out), int(width), int(h), int(fmt),
+                                                           int(uv_mode)), "mi_equalize_hist_packed422_to_nv12")
+        return y_out, uv_out
+
+    def clahe_packed422_to_nv12(self, frame: np.ndarray, width: int, fmt: int = FMT_YUY2, uv_mode: int = UV_COPY,
+                                clip_limit: float = 2.0, tiles_x: int = 8, tiles_y: int = 8,
+                                y_out: np.ndarray | None = None, uv_out: np.ndarray | None = None):
+        """mi_clahe_packed422_to_nv12; arguments as equalize_hist_packed422_to_nv12, plus the CLAHE parameters."""
+        name = "clahe_packed422_to_nv12"
+        frame = self._packed_host(frame, width, name)
+        h = frame.shape[0]
+        y_out, uv_out = self._nv12_host_out(int(width), h, y_out, uv_out, name)
+        self._chk(self._L.mi_clahe_packed422_to_nv12(self._h, frame.ctypes.data, _step(frame), y_out.ctypes.data, _step(y_out),
+                                                   uv_out.ctypes.data, _step(uv_out), int(width), int(h), int(fmt), int(uv_mode),
+                                                   float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_packed422_to_nv12")
+        return y_out, uv_out
 
     # ---- colour-domain neighbours (N3) ----
     @staticmethod

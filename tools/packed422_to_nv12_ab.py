@@ -12,7 +12,17 @@ Bars: A reaches at least 0.95 x the frame rate of B in every row (A reads the sa
 B's 2; the margin is the +- 3 % box-to-box spread on both sides of the ratio), and A beats C in every row.
 After the timed legs each row runs 30 profiled calls of A and of B and records the p50 time of each kernel role, so that a row that
 misses the first bar names the stage that loses the time.
-    python tools/packed422_to_nv12_ab.py [--out DIR] [--calls N]   -> DIR/r13_packed422_to_nv12_ab.json and .txt (default DIR: profiles)"""
+    python tools/packed422_to_nv12_ab.py [--out DIR] [--calls N]   -> DIR/r13_packed422_to_nv12_ab.json and .txt (default DIR: profiles)
+
+Frame lists (mi_*_packed422_to_nv12_frames_dev), in the same run, same method, legs interleaved:
+    (L)  the list form over separately allocated buffers: every input its own allocation at pitch align(2W, 256), every Y and every UV
+         plane its own allocation at pitch align(W, 256) (a capture pool in, an encoder's surface pool out)
+    (a)  mi_*_packed422_to_nv12_batch_dev on the same pixels in one tight allocation
+    (b)  what a caller with pools had before the list form: a torch repack of every input buffer into a tight batch, the batch form,
+         a copy of every Y and UV plane out to its surface
+64 x 3840x2160 and 256 x 1920x1080 YUY2 frames per call, equalizeHist and CLAHE 8x8 clip 2.0, MI_UV_COPY; inputs never change.
+Expectation (recorded, not enforced): L at least 0.95 x the frame rate of (a) at 4K, and clearly ahead of (b) in every row.
+    -> DIR/r14_packed422_to_nv12_frames_ab.json and .txt      (--lists-only / --no-lists run one half)"""
 import argparse
 import json
 import sys
@@ -37,14 +47,119 @@ def pct(v, q):
     return v[min(len(v) - 1, int(q * (len(v) - 1) + 0.5))]
 
 
+def align(x, a):
+    return (x + a - 1) // a * a
+
+
+def timed(stream, legs, warmup, calls):
+    names = list(legs)
+    times = {k: [] for k in names}
+    for it in range(warmup + calls):
+        order = names[it % len(names):] + names[: it % len(names)]
+        for name in order:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            legs[name]()
+            e1.record(stream)
+            if it >= warmup:
+                times[name].append((e0, e1))
+        if it % 20 == 19:
+            torch.cuda.synchronize()
+    torch.cuda.synchronize()
+    out = {}
+    for name, ev in times.items():
+        ms = [a.elapsed_time(b) for a, b in ev]
+        out[name] = {"median_us": pct(ms, 0.5) * 1e3, "p10_us": pct(ms, 0.1) * 1e3, "p90_us": pct(ms, 0.9) * 1e3}
+    return out
+
+
+def frame_lists(ctx, args):
+    """The list-form rows: -> r14_packed422_to_nv12_frames_ab.{json,txt}"""
+    stream = torch.cuda.current_stream()
+    s = stream.cuda_stream
+    fmt, uv, clahe = FMT_YUY2, UV_COPY, (2.0, 8, 8)
+    rows, lines = [], []
+    for w, h, n in CASES:
+        g = torch.Generator(device="cuda:0")
+        g.manual_seed(0x5EED1400 + w + n)
+        d_in = torch.randint(0, 256, (n, h, 2 * w), dtype=torch.uint8, device="cuda:0", generator=g)
+        lane = d_in[:, :, 0::2]
+        lane.copy_(lane // 4 + 64)                               # low-contrast luma, random chroma
+        nv12 = torch.empty((n, h * 3 // 2, w), dtype=torch.uint8, device="cuda:0")
+        tmp_in, tmp_nv12 = torch.empty_like(d_in), torch.empty_like(nv12)
+        ip, op_ = align(2 * w, 256), align(w, 256)
+        ins = [torch.zeros(ip * h, dtype=torch.uint8, device="cuda:0").view(h, ip)[:, : 2 * w] for _ in range(n)]
+        ys = [torch.zeros(op_ * h, dtype=torch.uint8, device="cuda:0").view(h, op_)[:, :w] for _ in range(n)]
+        uvs = [torch.zeros(op_ * (h // 2), dtype=torch.uint8, device="cuda:0").view(h // 2, op_)[:, :w] for _ in range(n)]
+        for k in range(n):
+            ins[k].copy_(d_in[k])
+        for op in ("equalize", "clahe"):
+            def batch(a, b):
+                if op == "equalize":
+                    ctx.equalize_hist_packed422_to_nv12_batch_dev(a, b, None, w, h, n, fmt, uv, stream=s)
+                else:
+                    ctx.clahe_packed422_to_nv12_batch_dev(a, b, None, w, h, n, fmt, uv, *clahe, stream=s)
+
+            def frame_list():
+                if op == "equalize":
+                    ctx.equalize_hist_packed422_to_nv12_frames(ins, ys, uvs, w, h, fmt, uv, stream=s)
+                else:
+                    ctx.clahe_packed422_to_nv12_frames(ins, ys, uvs, w, h, fmt, uv, *clahe, stream=s)
+
+            def repack():
+                for k in range(n):
+                    tmp_in[k].copy_(ins[k])
+                batch(tmp_in, tmp_nv12)
+                for k in range(n):
+                    ys[k].copy_(tmp_nv12[k, :h])
+                    uvs[k].copy_(tmp_nv12[k, h:])
+
+            # the list's output is the batch's, frame by frame, before anything is timed
+            frame_list()
+            batch(d_in, nv12)
+            torch.cuda.synchronize()
+            for k in (0, n // 2, n - 1):
+                assert torch.equal(ys[k], nv12[k, :h]) and torch.equal(uvs[k], nv12[k, h:]), (w, h, n, op, k)
+            legs = {"L_list": frame_list, "a_batch": lambda: batch(d_in, nv12), "b_repack_batch_copy_out": repack}
+            res = {"width": w, "height": h, "frames_per_call": n, "op": op, "uv": "copy", "format": "YUY2", "calls": args.calls}
+            for name, r in timed(stream, legs, args.warmup, args.calls).items():
+                r["frames_per_s"] = n / (r["median_us"] * 1e-6)
+                res[name] = r
+            L = res["L_list"]["median_us"]
+            res["list_speed_over_batch_speed"] = res["a_batch"]["median_us"] / L
+            res["repack_over_list"] = res["b_repack_batch_copy_out"]["median_us"] / L
+            line = (f"{w}x{h} x{n:3d} {op:8s} " +
+                    "  ".join(f"{k} {res[k]['median_us']:8.1f} us [{res[k]['p10_us']:.1f} {res[k]['p90_us']:.1f}]" for k in legs) +
+                    f"  | list speed / batch speed {res['list_speed_over_batch_speed']:.3f}  repack / list {res['repack_over_list']:.2f}")
+            rows.append(res)
+            print(line, flush=True)
+            lines.append(line)
+        del d_in, nv12, tmp_in, tmp_nv12, ins, ys, uvs, legs
+        torch.cuda.empty_cache()
+    meta = {"device": torch.cuda.get_device_name(0), "library": mi_lumaeq.version(), "uv_mode": "copy", "format": "YUY2",
+            "clahe": {"clip": clahe[0], "tiles": list(clahe[1:])}, "input_pitch": "align(2W, 256)", "output_pitches": "align(W, 256)",
+            "expectation": "list speed / batch speed >= 0.95 at 4K; repack / list > 1 in every row (recorded, not enforced)"}
+    outdir = Path(args.out)
+    outdir.mkdir(parents=True, exist_ok=True)
+    (outdir / "r14_packed422_to_nv12_frames_ab.json").write_text(json.dumps({"meta": meta, "rows": rows}, indent=1) + "\n")
+    (outdir / "r14_packed422_to_nv12_frames_ab.txt").write_text("Frame lists" + __doc__.split("\nFrame lists")[1].split("\n    ->")[0] + "\n\n"
+                                                               + json.dumps(meta) + "\n" + "\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=str(ROOT / "profiles"))
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--lists-only", action="store_true", help="only the frame-list rows (r14)")
+    ap.add_argument("--no-lists", action="store_true", help="only the batch-form rows (r13)")
     args = ap.parse_args()
     assert args.calls >= 200 and args.warmup >= 20, "the method wants >= 20 warm-up and >= 200 timed calls"
     ctx = mi_lumaeq.Context(0)
+    if args.lists_only:
+        frame_lists(ctx, args)
+        ctx.close()
+        return
     stream = torch.cuda.current_stream()
     s = stream.cuda_stream
     fmt, off = FMT_YUY2, 0
@@ -142,6 +257,8 @@ def main():
     outdir.mkdir(parents=True, exist_ok=True)
     (outdir / "r13_packed422_to_nv12_ab.json").write_text(json.dumps({"meta": meta, "rows": rows}, indent=1) + "\n")
     (outdir / "r13_packed422_to_nv12_ab.txt").write_text(__doc__.split("\n    python")[0] + "\n\n" + json.dumps(meta) + "\n" + "\n".join(lines) + "\n")
+    if not args.no_lists:
+        frame_lists(ctx, args)
     ctx.close()
     bad = [(r["width"], r["op"], r["uv"]) for r in rows if r["A_rate_over_B_rate"] < 0.95 or r["A_rate_over_C_rate"] <= 1.0]
     if bad:
