@@ -49,27 +49,64 @@ Packed422 packed422_batch(const P422Args& a, int f0)
     return p;
 }
 
-// The stage sequences below take an optional frame list (kernels/packed422.hip.h Packed422List, mi_*_packed422_frames_dev: one chunk
-// of at most kPacked422FramesPerLaunch frames, a.n_frames of them, indices from 0): with one, every launch goes to the *_frames_kernel
-// entry of the same body -- same grids, same splits, same scratch -- and a.in / a.out / the frame strides are not used.
-template <int OFF>
-mi_status equalize422_dev(mi_ctx* c, hipStream_t s, const P422Args& a, const Packed422List* fl = nullptr)
+// The two entries of one kernel body: `frames` takes a chunk of a frame list in front of the arguments of `batch`.
+template <class KF, class KB> struct KernelPair { KF frames; KB batch; };
+template <class KF, class KB> KernelPair(KF, KB) -> KernelPair<KF, KB>;
+
+// One launch of a pair: the list entry when the call came with a frame list, else the batch entry.
+template <class KF, class KB, class L, class... A>
+mi_status launch_pair(mi_ctx* c, hipStream_t s, int kid, const KernelPair<KF, KB>& k, const L* fl, dim3 grid, dim3 block, size_t lds,
+                      const A&... args)
 {
-    const long long frame_bytes = 2LL * a.width * a.height;
-    for (int f0 = 0; f0 < a.n_frames; f0 += kMaxGridY) {
-        const int nf = std::min(kMaxGridY, a.n_frames - f0);
-        const Packed422 p = packed422_batch(a, f0);
-        const int B = blocks_per_frame(c, frame_bytes, a.height, nf, 256);
+    if (fl) LAUNCH(c, s, kid, k.frames, grid, block, lds, *fl, args...);
+    else    LAUNCH(c, s, kid, k.batch, grid, block, lds, args...);
+    return MI_OK;
+}
+
+// The stage sequences below are written once for every writer of packed input: W says what the last stage writes.
+//   Args          the host-side arguments of a call; input(a) is their packed side, all that the histogram stages see
+//   Block         the argument block of the writer's kernels, cut(a, f0) for the chunk of frames from f0
+//   List          the frame list its *_frames_kernel entries take
+//   apply_rows(h) the row units the LUT-apply grid is sized by
+//   K<OFF>        its kernels for luma byte offset OFF
+// PackedOut writes a packed frame; Nv12Out (packed422_nv12.inc.hpp) a Y plane and a UV plane.
+struct PackedOut {
+    using Args = P422Args;
+    using Block = Packed422;
+    using List = Packed422List;
+    static const P422Args& input(const Args& a) { return a; }
+    static Block cut(const Args& a, int f0) { return packed422_batch(a, f0); }
+    static int apply_rows(int height) { return height; }
+    template <int OFF> struct K {
+        static constexpr KernelPair apply{lut_apply422_frames_kernel<OFF>, lut_apply422_kernel<OFF>};
+        static constexpr KernelPair interp_global{clahe_interp422_global_frames_kernel<OFF>, clahe_interp422_global_kernel<OFF>};
+        template <bool FT, bool FMA>
+        static constexpr KernelPair interp{clahe_interp422_frames_kernel<FT, FMA, OFF>, clahe_interp422_kernel<FT, FMA, OFF>};
+    };
+};
+
+// The sequences take an optional chunk of a frame list (at most kPacked422FramesPerLaunch frames, input(a).n_frames of them, indices
+// from 0) as the histogram stages' Packed422List (they only read: a writer that has a list type of its own hands them one whose out
+// mirrors in) and as the writer's own list, both or neither: with one, every launch goes to the *_frames_kernel entry of the same
+// body -- same grids, same splits, same scratch -- and the base addresses and frame strides of `a` are not used.
+template <class W, int OFF>
+mi_status equalize422_dev(mi_ctx* c, hipStream_t s, const typename W::Args& a, const Packed422List* fl_in, const typename W::List* fl_out)
+{
+    const P422Args& in = W::input(a);
+    const long long frame_bytes = 2LL * in.width * in.height;
+    for (int f0 = 0; f0 < in.n_frames; f0 += kMaxGridY) {
+        const int nf = std::min(kMaxGridY, in.n_frames - f0);
+        const int B = blocks_per_frame(c, frame_bytes, in.height, nf, 256);
         mi_status st = grow_dev(c, &c->d_partial, &c->partial_bytes, (size_t)nf * B * 256 * sizeof(uint32_t));
         if (st) return st;
         if ((st = grow_dev(c, &c->d_luts, &c->luts_bytes, (size_t)nf * 256))) return st;
-        if (fl) LAUNCH(c, s, MI_K_HIST, hist422_partial_frames_kernel<OFF>, dim3(B, nf), dim3(kHistThreads), 0, *fl, p, c->d_partial);
-        else    LAUNCH(c, s, MI_K_HIST, hist422_partial_kernel<OFF>, dim3(B, nf), dim3(kHistThreads), 0, p, c->d_partial);
+        if ((st = launch_pair(c, s, MI_K_HIST, KernelPair{hist422_partial_frames_kernel<OFF>, hist422_partial_kernel<OFF>}, fl_in,
+                              dim3(B, nf), dim3(kHistThreads), 0, packed422_batch(in, f0), c->d_partial))) return st;
         LAUNCH(c, s, MI_K_EQ_LUT, equalize_lut_kernel, dim3(nf), dim3(kThreads), 0,
-               (const uint32_t*)c->d_partial, B, (int)((long long)a.width * a.height), c->d_luts, (int32_t*)nullptr);
-        const int BA = blocks_per_frame(c, frame_bytes, a.height, nf, 2048);
-        if (fl) LAUNCH(c, s, MI_K_LUT_APPLY, lut_apply422_frames_kernel<OFF>, dim3(BA, nf), dim3(kThreads), 0, *fl, p, (const uint8_t*)c->d_luts);
-        else    LAUNCH(c, s, MI_K_LUT_APPLY, lut_apply422_kernel<OFF>, dim3(BA, nf), dim3(kThreads), 0, p, (const uint8_t*)c->d_luts);
+               (const uint32_t*)c->d_partial, B, (int)((long long)in.width * in.height), c->d_luts, (int32_t*)nullptr);
+        const int BA = blocks_per_frame(c, frame_bytes, W::apply_rows(in.height), nf, 2048);
+        if ((st = launch_pair(c, s, MI_K_LUT_APPLY, W::template K<OFF>::apply, fl_out, dim3(BA, nf), dim3(kThreads), 0,
+                              W::cut(a, f0), (const uint8_t*)c->d_luts))) return st;
     }
     return MI_OK;
 }
@@ -77,7 +114,7 @@ mi_status equalize422_dev(mi_ctx* c, hipStream_t s, const P422Args& a, const Pac
 // launch_tile_luts' splits and tile order (one tile per workgroup: the multi-tile variant has no packed sibling)
 template <int OFF>
 mi_status launch_tile_luts422(mi_ctx* c, hipStream_t s, const Packed422& p, const ClaheGeom& g, int nf, uint8_t* d_luts_out,
-                              const Packed422List* fl = nullptr)
+                              const Packed422List* fl)
 {
     const int tiles = g.tiles_x * g.tiles_y;
     const long long tile_px = (long long)g.tile_w * g.tile_h;
@@ -97,8 +134,8 @@ mi_status launch_tile_luts422(mi_ctx* c, hipStream_t s, const Packed422& p, cons
     return MI_OK;
 }
 
-// launch_interp's choice of tables, column segments, bands and sub-bands, computed once for every writer of packed input (the packed
-// kernels below, the NV12 writers of packed422_nv12.inc.hpp).  global: the grid is too wide for the LDS pair table.
+// launch_interp's choice of tables, column segments, bands and sub-bands, the same for every writer of packed input.  global: the
+// grid is too wide for the LDS pair table.
 struct Interp422Plan {
     bool global, float_tables;
     dim3 grid;
@@ -146,60 +183,48 @@ mi_status plan_interp422(mi_ctx* c, const ClaheGeom& g, int dwords, int nf, Inte
     return MI_OK;
 }
 
-template <int OFF>
-mi_status launch_interp422(mi_ctx* c, hipStream_t s, const Packed422& p, const ClaheGeom& g, int nf, const uint8_t* d_luts,
-                           const Packed422List* fl = nullptr)
+// The one place that picks an interpolation kernel: the writer's family for the plan's tables, the arithmetic mode and OFF
+template <class W, int OFF>
+mi_status launch_interp422(mi_ctx* c, hipStream_t s, const typename W::Block& p, const ClaheGeom& g, int nf, const uint8_t* d_luts,
+                           const typename W::List* fl)
 {
+    using K = typename W::template K<OFF>;
     Interp422Plan pl;
     if (mi_status st = plan_interp422(c, g, p.dwords, nf, &pl)) return st;
-    const dim3 grid = pl.grid;
-    const size_t lds = pl.lds;
-    const int subs = pl.subs, groups = pl.groups, cap = pl.cap;
-    if (pl.global) {
-        if (fl) LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp422_global_frames_kernel<OFF>, grid, dim3(kThreads), 0, *fl, p, g, d_luts);
-        else    LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp422_global_kernel<OFF>, grid, dim3(kThreads), 0, p, g, d_luts);
-        return MI_OK;
-    }
-    if (pl.float_tables) {
-        if (fl) {
-            if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_frames_kernel<true, true, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
-            else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_frames_kernel<true, false, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
-        } else if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<true, true, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
-        else                   LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<true, false, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
-    } else {
-        if (fl) {
-            if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_frames_kernel<false, true, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
-            else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_frames_kernel<false, false, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
-        } else if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<false, true, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
-        else                   LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_kernel<false, false, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
-    }
-    return MI_OK;
+    if (pl.global) return launch_pair(c, s, MI_K_CLAHE_INTERP, K::interp_global, fl, pl.grid, dim3(kThreads), 0, p, g, d_luts);
+    const auto lds_tables = [&](const auto& k) {
+        return launch_pair(c, s, MI_K_CLAHE_INTERP, k, fl, pl.grid, dim3(kThreads), pl.lds, p, g, d_luts, pl.subs, pl.groups, pl.cap);
+    };
+    if (pl.float_tables) return g.contract ? lds_tables(K::template interp<true, true>) : lds_tables(K::template interp<true, false>);
+    return g.contract ? lds_tables(K::template interp<false, true>) : lds_tables(K::template interp<false, false>);
 }
 
-template <int OFF>
-mi_status clahe422_dev(mi_ctx* c, hipStream_t s, const P422Args& a, double clip_limit, int tiles_x, int tiles_y,
-                       const Packed422List* fl = nullptr)
+template <class W, int OFF>
+mi_status clahe422_dev(mi_ctx* c, hipStream_t s, const typename W::Args& a, double clip_limit, int tiles_x, int tiles_y,
+                       const Packed422List* fl_in, const typename W::List* fl_out)
 {
+    const P422Args& in = W::input(a);
     ClaheGeom g;
-    mi_status st = clahe_geometry(c, a.width, a.height, clip_limit, tiles_x, tiles_y, &g);
+    mi_status st = clahe_geometry(c, in.width, in.height, clip_limit, tiles_x, tiles_y, &g);
     if (st) return st;
     const int tiles = tiles_x * tiles_y;
-    for (int f0 = 0; f0 < a.n_frames; f0 += kMaxGridY) {
-        const int nf = std::min(kMaxGridY, a.n_frames - f0);
-        const Packed422 p = packed422_batch(a, f0);
+    for (int f0 = 0; f0 < in.n_frames; f0 += kMaxGridY) {
+        const int nf = std::min(kMaxGridY, in.n_frames - f0);
         if ((st = grow_dev(c, &c->d_luts, &c->luts_bytes, (size_t)nf * tiles * 256))) return st;
-        if ((st = launch_tile_luts422<OFF>(c, s, p, g, nf, c->d_luts, fl))) return st;
-        if ((st = launch_interp422<OFF>(c, s, p, g, nf, c->d_luts, fl))) return st;
+        if ((st = launch_tile_luts422<OFF>(c, s, packed422_batch(in, f0), g, nf, c->d_luts, fl_in))) return st;
+        if ((st = launch_interp422<W, OFF>(c, s, W::cut(a, f0), g, nf, c->d_luts, fl_out))) return st;
     }
     return MI_OK;
 }
 
-// op: 0 equalizeHist, 1 CLAHE.  `a` has passed check_packed422 (with a list: check_packed422_frames).
-mi_status packed422_dev(mi_ctx* c, hipStream_t s, const P422Args& a, int op, double clip_limit, int tiles_x, int tiles_y,
-                        const Packed422List* fl = nullptr)
+// op: 0 equalizeHist, 1 CLAHE.  `a` has passed the checks of its form (check_packed422*).
+template <class W>
+mi_status packed422_dev(mi_ctx* c, hipStream_t s, const typename W::Args& a, int op, double clip_limit, int tiles_x, int tiles_y,
+                        const Packed422List* fl_in = nullptr, const typename W::List* fl_out = nullptr)
 {
-    if (a.format == MI_FMT_UYVY) return op ? clahe422_dev<1>(c, s, a, clip_limit, tiles_x, tiles_y, fl) : equalize422_dev<1>(c, s, a, fl);
-    return op ? clahe422_dev<0>(c, s, a, clip_limit, tiles_x, tiles_y, fl) : equalize422_dev<0>(c, s, a, fl);
+    if (W::input(a).format == MI_FMT_UYVY)
+        return op ? clahe422_dev<W, 1>(c, s, a, clip_limit, tiles_x, tiles_y, fl_in, fl_out) : equalize422_dev<W, 1>(c, s, a, fl_in, fl_out);
+    return op ? clahe422_dev<W, 0>(c, s, a, clip_limit, tiles_x, tiles_y, fl_in, fl_out) : equalize422_dev<W, 0>(c, s, a, fl_in, fl_out);
 }
 
 // Host frame: the whole frame goes up and comes back (there is no luma plane to send on its own), tight on the device; pinned tight
@@ -216,7 +241,7 @@ mi_status packed422_host(mi_ctx* c, const P422Args& h, int op, double clip_limit
     P422Args d = h;
     d.in = c->d_stage_in; d.in_pitch = row; d.in_frame = bytes;
     d.out = c->d_stage_out; d.out_pitch = row; d.out_frame = bytes;
-    if ((st = packed422_dev(c, s, d, op, clip_limit, tiles_x, tiles_y))) return st;
+    if ((st = packed422_dev<PackedOut>(c, s, d, op, clip_limit, tiles_x, tiles_y))) return st;
     return stage_out(c, s, h.out, h.out_pitch, row, (size_t)h.height, drain);
 }
 
@@ -232,8 +257,7 @@ mi_status mi_equalize_hist_packed422_batch_dev(mi_ctx* c, const void* d_in, size
     const P422Args a{(const uint8_t*)d_in, in_pitch, in_frame_stride, (uint8_t*)d_out, out_pitch, out_frame_stride, width, height, n_frames, format, uv_mode};
     bool work = false;
     const mi_status st = check_packed422(c, a, false, 0, 0, &work);
-    if (st || !work) return st;
-    return packed422_dev(c, pick_stream(c, stream), a, 0, 0.0, 0, 0);
+    return (st || !work) ? st : packed422_dev<PackedOut>(c, pick_stream(c, stream), a, 0, 0.0, 0, 0);
 }
 
 mi_status mi_clahe_packed422_batch_dev(mi_ctx* c, const void* d_in, size_t in_pitch, size_t in_frame_stride,
@@ -245,8 +269,7 @@ mi_status mi_clahe_packed422_batch_dev(mi_ctx* c, const void* d_in, size_t in_pi
     const P422Args a{(const uint8_t*)d_in, in_pitch, in_frame_stride, (uint8_t*)d_out, out_pitch, out_frame_stride, width, height, n_frames, format, uv_mode};
     bool work = false;
     const mi_status st = check_packed422(c, a, true, tiles_x, tiles_y, &work);
-    if (st || !work) return st;
-    return packed422_dev(c, pick_stream(c, stream), a, 1, clip_limit, tiles_x, tiles_y);
+    return (st || !work) ? st : packed422_dev<PackedOut>(c, pick_stream(c, stream), a, 1, clip_limit, tiles_x, tiles_y);
 }
 
 mi_status mi_equalize_hist_packed422(mi_ctx* c, const uint8_t* in, size_t in_pitch, uint8_t* out, size_t out_pitch,
@@ -256,8 +279,7 @@ mi_status mi_equalize_hist_packed422(mi_ctx* c, const uint8_t* in, size_t in_pit
     const P422Args a{in, in_pitch, 0, out, out_pitch, 0, width, height, 1, format, uv_mode};
     bool work = false;
     const mi_status st = check_packed422(c, a, false, 0, 0, &work);
-    if (st || !work) return st;
-    return packed422_host(c, a, 0, 0.0, 0, 0);
+    return (st || !work) ? st : packed422_host(c, a, 0, 0.0, 0, 0);
 }
 
 mi_status mi_clahe_packed422(mi_ctx* c, const uint8_t* in, size_t in_pitch, uint8_t* out, size_t out_pitch,
@@ -267,8 +289,7 @@ mi_status mi_clahe_packed422(mi_ctx* c, const uint8_t* in, size_t in_pitch, uint
     const P422Args a{in, in_pitch, 0, out, out_pitch, 0, width, height, 1, format, uv_mode};
     bool work = false;
     const mi_status st = check_packed422(c, a, true, tiles_x, tiles_y, &work);
-    if (st || !work) return st;
-    return packed422_host(c, a, 1, clip_limit, tiles_x, tiles_y);
+    return (st || !work) ? st : packed422_host(c, a, 1, clip_limit, tiles_x, tiles_y);
 }
 
 }  // extern "C"

@@ -3,9 +3,8 @@
 //
 // A capture card's buffer pool is not one allocation at a fixed frame stride: every buffer is its own allocation, padded to
 // bytesperline, at whatever alignment the driver gave it.  The call is cut into chunks of kPacked422FramesPerLaunch frames; each
-// chunk's {in, out} pairs travel by value in the kernel arguments (Packed422List), and the chunk runs the stage sequence of
-// equalize422_dev / clahe422_dev through the same launch helpers, which pick the *_frames_kernel entries.  Same grids, same tile
-// splits, same bytes as the batch forms.
+// chunk's {in, out} pairs travel by value in the kernel arguments (Packed422List), and the chunk runs the stage sequences of
+// packed422.inc.hpp, whose launches pick the *_frames_kernel entries.  Same grids, same tile splits, same bytes as the batch forms.
 
 namespace {
 
@@ -51,7 +50,7 @@ mi_status packed422_frames_dev(mi_ctx* c, hipStream_t s, const mi_packed422_fram
         Packed422List l{};                                           // this chunk's frames of the list, from index 0
         for (int k = 0; k < nf; ++k) l.f[k] = Packed422Frame{(const uint8_t*)frames[f0 + k].in, (uint8_t*)frames[f0 + k].out};
         const P422Args a{l.f[0].in, sh.in_pitch, 0, l.f[0].out, sh.out_pitch, 0, sh.width, sh.height, nf, sh.format, sh.uv_mode};
-        const mi_status st = packed422_dev(c, s, a, op, clip_limit, tiles_x, tiles_y, &l);
+        const mi_status st = packed422_dev<PackedOut>(c, s, a, op, clip_limit, tiles_x, tiles_y, &l, &l);
         if (st) return st;
     }
     return MI_OK;
@@ -69,8 +68,7 @@ mi_status mi_equalize_hist_packed422_frames_dev(mi_ctx* c, const mi_packed422_fr
     const P422FramesShape sh{width, height, in_pitch, out_pitch, format, uv_mode};
     bool work = false;
     const mi_status st = check_packed422_frames(c, frames, n_frames, sh, false, 0, 0, &work);
-    if (st || !work) return st;
-    return packed422_frames_dev(c, pick_stream(c, stream), frames, n_frames, sh, 0, 0.0, 0, 0);
+    return (st || !work) ? st : packed422_frames_dev(c, pick_stream(c, stream), frames, n_frames, sh, 0, 0.0, 0, 0);
 }
 
 mi_status mi_clahe_packed422_frames_dev(mi_ctx* c, const mi_packed422_frame_dev* frames, int n_frames,
@@ -82,8 +80,7 @@ mi_status mi_clahe_packed422_frames_dev(mi_ctx* c, const mi_packed422_frame_dev*
     const P422FramesShape sh{width, height, in_pitch, out_pitch, format, uv_mode};
     bool work = false;
     const mi_status st = check_packed422_frames(c, frames, n_frames, sh, true, tiles_x, tiles_y, &work);
-    if (st || !work) return st;
-    return packed422_frames_dev(c, pick_stream(c, stream), frames, n_frames, sh, 1, clip_limit, tiles_x, tiles_y);
+    return (st || !work) ? st : packed422_frames_dev(c, pick_stream(c, stream), frames, n_frames, sh, 1, clip_limit, tiles_x, tiles_y);
 }
 
 }  // extern "C"

@@ -1,11 +1,11 @@
 // packed422_nv12.inc.hpp -- packed 4:2:2 frames in (YUY2 / UYVY), NV12 frames out: checks, launch sequences, extern "C" entry points
 // Included by ../mi_lumaeq.hip after packed422.inc.hpp (one translation unit; not a stand-alone header).
 //
-// capture -> equalize -> encoder without a format conversion of its own.  The histogram half is packed422.inc.hpp's, launch for launch
-// (hist422_partial_kernel -> equalize_lut_kernel; launch_tile_luts422): same scratch, same chunks, same grids and splits.  Only the
-// last stage differs: the pixel-writing kernels of kernels/packed422_nv12.hip.h put the new luma into a Y plane and the chroma of each
-// row pair, halved vertically, into an interleaved UV plane -- in the launch that writes the luma, there is no chroma launch.  Never
-// the fused kernel and never hist_lut_kernel, as the packed forms.
+// capture -> equalize -> encoder without a format conversion of its own.  The stage sequences are packed422.inc.hpp's own (one
+// MI_K_HIST, one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch per chunk; tile histograms -> interpolation): same scratch, same chunks, same
+// grids and splits.  Only the writer differs: the pixel-writing kernels of kernels/packed422_nv12.hip.h put the new luma into a Y plane
+// and the chroma of each row pair, halved vertically, into an interleaved UV plane -- in the launch that writes the luma, there is no
+// chroma launch.  Never the fused kernel and never hist_lut_kernel, as the packed forms.
 
 namespace {
 
@@ -56,97 +56,21 @@ Packed422Nv12 packed422_nv12_batch(const P422Nv12Args& a, int f0)
     return p;
 }
 
-// One chunk of a frame list (mi_*_packed422_to_nv12_frames_dev, packed422_nv12_frames.inc.hpp): the inputs as the histogram stages'
-// Packed422List (they only read: out mirrors in, as in p422_nv12_args) and the three addresses of every frame for the writers.
-struct P422Nv12Lists {
-    Packed422List in;
-    Packed422Nv12List io;
+// The writer of the stage sequences of packed422.inc.hpp that puts the new luma into a Y plane and the chroma into a UV plane
+struct Nv12Out {
+    using Args = P422Nv12Args;
+    using Block = Packed422Nv12;
+    using List = Packed422Nv12List;
+    static const P422Args& input(const Args& a) { return a.in; }
+    static Block cut(const Args& a, int f0) { return packed422_nv12_batch(a, f0); }
+    static int apply_rows(int height) { return height / 2; }                 // bands of row pairs
+    template <int OFF> struct K {
+        static constexpr KernelPair apply{lut_apply422_nv12_frames_kernel<OFF>, lut_apply422_nv12_kernel<OFF>};
+        static constexpr KernelPair interp_global{clahe_interp422_nv12_global_frames_kernel<OFF>, clahe_interp422_nv12_global_kernel<OFF>};
+        template <bool FT, bool FMA>
+        static constexpr KernelPair interp{clahe_interp422_nv12_frames_kernel<FT, FMA, OFF>, clahe_interp422_nv12_kernel<FT, FMA, OFF>};
+    };
 };
-
-// The stage sequences below take an optional chunk of a frame list (a.in.n_frames of its entries, indices from 0): with one, every
-// launch goes to the *_frames_kernel entry of the same body -- same grids, same splits, same scratch -- and the base addresses and
-// frame strides of `a` are not used.
-
-// equalize422_dev with the NV12 writer as its last stage: one MI_K_HIST, one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch per chunk
-template <int OFF>
-mi_status equalize422_nv12_dev(mi_ctx* c, hipStream_t s, const P422Nv12Args& a, const P422Nv12Lists* fl = nullptr)
-{
-    const int width = a.in.width, height = a.in.height;
-    const long long frame_bytes = 2LL * width * height;
-    for (int f0 = 0; f0 < a.in.n_frames; f0 += kMaxGridY) {
-        const int nf = std::min(kMaxGridY, a.in.n_frames - f0);
-        const Packed422 pin = packed422_batch(a.in, f0);
-        const Packed422Nv12 p = packed422_nv12_batch(a, f0);
-        const int B = blocks_per_frame(c, frame_bytes, height, nf, 256);
-        mi_status st = grow_dev(c, &c->d_partial, &c->partial_bytes, (size_t)nf * B * 256 * sizeof(uint32_t));
-        if (st) return st;
-        if ((st = grow_dev(c, &c->d_luts, &c->luts_bytes, (size_t)nf * 256))) return st;
-        if (fl) LAUNCH(c, s, MI_K_HIST, hist422_partial_frames_kernel<OFF>, dim3(B, nf), dim3(kHistThreads), 0, fl->in, pin, c->d_partial);
-        else    LAUNCH(c, s, MI_K_HIST, hist422_partial_kernel<OFF>, dim3(B, nf), dim3(kHistThreads), 0, pin, c->d_partial);
-        LAUNCH(c, s, MI_K_EQ_LUT, equalize_lut_kernel, dim3(nf), dim3(kThreads), 0,
-               (const uint32_t*)c->d_partial, B, (int)((long long)width * height), c->d_luts, (int32_t*)nullptr);
-        const int BA = blocks_per_frame(c, frame_bytes, height / 2, nf, 2048);       // bands of row pairs
-        if (fl) LAUNCH(c, s, MI_K_LUT_APPLY, lut_apply422_nv12_frames_kernel<OFF>, dim3(BA, nf), dim3(kThreads), 0, fl->io, p, (const uint8_t*)c->d_luts);
-        else    LAUNCH(c, s, MI_K_LUT_APPLY, lut_apply422_nv12_kernel<OFF>, dim3(BA, nf), dim3(kThreads), 0, p, (const uint8_t*)c->d_luts);
-    }
-    return MI_OK;
-}
-
-// launch_interp422 on the NV12 writers: the same plan (plan_interp422: tables, column segments, bands, sub-bands), other kernels
-template <int OFF>
-mi_status launch_interp422_nv12(mi_ctx* c, hipStream_t s, const Packed422Nv12& p, const ClaheGeom& g, int nf, const uint8_t* d_luts,
-                                const Packed422Nv12List* fl = nullptr)
-{
-    Interp422Plan pl;
-    if (mi_status st = plan_interp422(c, g, p.dwords, nf, &pl)) return st;
-    const dim3 grid = pl.grid;
-    const size_t lds = pl.lds;
-    const int subs = pl.subs, groups = pl.groups, cap = pl.cap;
-    if (pl.global) {
-        if (fl) LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp422_nv12_global_frames_kernel<OFF>, grid, dim3(kThreads), 0, *fl, p, g, d_luts);
-        else    LAUNCH(c, s, MI_K_CLAHE_INTERP, clahe_interp422_nv12_global_kernel<OFF>, grid, dim3(kThreads), 0, p, g, d_luts);
-    } else if (pl.float_tables) {
-        if (fl) {
-            if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_frames_kernel<true, true, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
-            else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_frames_kernel<true, false, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
-        } else if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_kernel<true, true, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
-        else                   LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_kernel<true, false, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
-    } else {
-        if (fl) {
-            if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_frames_kernel<false, true, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
-            else            LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_frames_kernel<false, false, OFF>), grid, dim3(kThreads), lds, *fl, p, g, d_luts, subs, groups, cap);
-        } else if (g.contract) LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_kernel<false, true, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
-        else                   LAUNCH(c, s, MI_K_CLAHE_INTERP, (clahe_interp422_nv12_kernel<false, false, OFF>), grid, dim3(kThreads), lds, p, g, d_luts, subs, groups, cap);
-    }
-    return MI_OK;
-}
-
-template <int OFF>
-mi_status clahe422_nv12_dev(mi_ctx* c, hipStream_t s, const P422Nv12Args& a, double clip_limit, int tiles_x, int tiles_y,
-                            const P422Nv12Lists* fl = nullptr)
-{
-    ClaheGeom g;
-    mi_status st = clahe_geometry(c, a.in.width, a.in.height, clip_limit, tiles_x, tiles_y, &g);
-    if (st) return st;
-    const int tiles = tiles_x * tiles_y;
-    for (int f0 = 0; f0 < a.in.n_frames; f0 += kMaxGridY) {
-        const int nf = std::min(kMaxGridY, a.in.n_frames - f0);
-        const Packed422 pin = packed422_batch(a.in, f0);
-        const Packed422Nv12 p = packed422_nv12_batch(a, f0);
-        if ((st = grow_dev(c, &c->d_luts, &c->luts_bytes, (size_t)nf * tiles * 256))) return st;
-        if ((st = launch_tile_luts422<OFF>(c, s, pin, g, nf, c->d_luts, fl ? &fl->in : nullptr))) return st;
-        if ((st = launch_interp422_nv12<OFF>(c, s, p, g, nf, c->d_luts, fl ? &fl->io : nullptr))) return st;
-    }
-    return MI_OK;
-}
-
-// op: 0 equalizeHist, 1 CLAHE.  `a` has passed check_packed422_nv12 (with a list: check_packed422_nv12_frames).
-mi_status packed422_nv12_dev(mi_ctx* c, hipStream_t s, const P422Nv12Args& a, int op, double clip_limit, int tiles_x, int tiles_y,
-                             const P422Nv12Lists* fl = nullptr)
-{
-    if (a.in.format == MI_FMT_UYVY) return op ? clahe422_nv12_dev<1>(c, s, a, clip_limit, tiles_x, tiles_y, fl) : equalize422_nv12_dev<1>(c, s, a, fl);
-    return op ? clahe422_nv12_dev<0>(c, s, a, clip_limit, tiles_x, tiles_y, fl) : equalize422_nv12_dev<0>(c, s, a, fl);
-}
 
 }  // namespace
 
@@ -161,9 +85,7 @@ mi_status mi_equalize_hist_packed422_to_nv12_batch_dev(mi_ctx* c, const void* d_
                                           width, height, n_frames, format, uv_mode);
     bool work = false;
     const mi_status st = check_packed422_nv12(c, a, false, 0, 0, &work);
-    if (st || !work) return st;
-    hipStream_t s = pick_stream(c, stream);
-    return format == MI_FMT_UYVY ? equalize422_nv12_dev<1>(c, s, a) : equalize422_nv12_dev<0>(c, s, a);
+    return (st || !work) ? st : packed422_dev<Nv12Out>(c, pick_stream(c, stream), a, 0, 0.0, 0, 0);
 }
 
 mi_status mi_clahe_packed422_to_nv12_batch_dev(mi_ctx* c, const void* d_in, size_t in_pitch, size_t in_frame_stride,
@@ -176,10 +98,7 @@ mi_status mi_clahe_packed422_to_nv12_batch_dev(mi_ctx* c, const void* d_in, size
                                           width, height, n_frames, format, uv_mode);
     bool work = false;
     const mi_status st = check_packed422_nv12(c, a, true, tiles_x, tiles_y, &work);
-    if (st || !work) return st;
-    hipStream_t s = pick_stream(c, stream);
-    return format == MI_FMT_UYVY ? clahe422_nv12_dev<1>(c, s, a, clip_limit, tiles_x, tiles_y)
-                                 : clahe422_nv12_dev<0>(c, s, a, clip_limit, tiles_x, tiles_y);
+    return (st || !work) ? st : packed422_dev<Nv12Out>(c, pick_stream(c, stream), a, 1, clip_limit, tiles_x, tiles_y);
 }
 
 }  // extern "C"

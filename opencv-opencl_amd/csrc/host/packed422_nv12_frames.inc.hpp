@@ -62,15 +62,16 @@ mi_status packed422_nv12_frames_dev(mi_ctx* c, hipStream_t s, const mi_packed422
 {
     for (int f0 = 0; f0 < n_frames; f0 += kP422Nv12Chunk) {
         const int nf = std::min(kP422Nv12Chunk, n_frames - f0);
-        P422Nv12Lists l{};                                           // this chunk's frames of the list, from index 0
+        Packed422List in{};                                          // this chunk's frames of the list, from index 0: the inputs for the
+        Packed422Nv12List io{};                                      // histogram stages, the three addresses of a frame for the writers
         for (int k = 0; k < nf; ++k) {
             const mi_packed422_nv12_frame_dev& f = frames[f0 + k];
-            l.in.f[k] = Packed422Frame{(const uint8_t*)f.in, (uint8_t*)const_cast<void*>(f.in)};       // read-only stages: out mirrors in
-            l.io.f[k] = Packed422Nv12Frame{(const uint8_t*)f.in, (uint8_t*)f.y_out, (uint8_t*)f.uv_out};
+            in.f[k] = Packed422Frame{(const uint8_t*)f.in, (uint8_t*)const_cast<void*>(f.in)};         // read-only stages: out mirrors in
+            io.f[k] = Packed422Nv12Frame{(const uint8_t*)f.in, (uint8_t*)f.y_out, (uint8_t*)f.uv_out};
         }
-        const P422Nv12Args a = p422_nv12_args(l.io.f[0].in, sh.in_pitch, 0, l.io.f[0].y, sh.y_pitch, l.io.f[0].uv, sh.uv_pitch, 0,
+        const P422Nv12Args a = p422_nv12_args(io.f[0].in, sh.in_pitch, 0, io.f[0].y, sh.y_pitch, io.f[0].uv, sh.uv_pitch, 0,
                                               sh.width, sh.height, nf, sh.format, sh.uv_mode);
-        const mi_status st = packed422_nv12_dev(c, s, a, op, clip_limit, tiles_x, tiles_y, &l);
+        const mi_status st = packed422_dev<Nv12Out>(c, s, a, op, clip_limit, tiles_x, tiles_y, &in, &io);
         if (st) return st;
     }
     return MI_OK;
@@ -116,7 +117,7 @@ mi_status packed422_nv12_host(mi_ctx* c, const P422Nv12Args& h, int op, double c
     if (!(py.direct && puv.direct) && (st = grow_pinned(c, &c->h_pin_out, &c->pin_out_bytes, ybytes + uvbytes))) return st;
     const P422Nv12Args d = p422_nv12_args(c->d_stage_in, row, bytes, c->d_stage_out, P, c->d_stage_out + ybytes, P, ybytes + uvbytes,
                                           h.in.width, h.in.height, 1, h.in.format, h.in.uv_mode);
-    if ((st = packed422_nv12_dev(c, s, d, op, clip_limit, tiles_x, tiles_y))) return st;
+    if ((st = packed422_dev<Nv12Out>(c, s, d, op, clip_limit, tiles_x, tiles_y))) return st;
     drain.watch(s);
     if ((st = enqueue_plane_out(c, s, c->d_stage_out, c->h_pin_out, py))) return st;
     if ((st = enqueue_plane_out(c, s, c->d_stage_out + ybytes, c->h_pin_out + ybytes, puv))) return st;
@@ -157,8 +158,7 @@ mi_status mi_equalize_hist_packed422_to_nv12_frames_dev(mi_ctx* c, const mi_pack
     const P422Nv12FramesShape sh{width, height, in_pitch, y_pitch, uv_pitch, format, uv_mode};
     bool work = false;
     const mi_status st = check_packed422_nv12_frames(c, frames, n_frames, sh, false, 0, 0, &work);
-    if (st || !work) return st;
-    return packed422_nv12_frames_dev(c, pick_stream(c, stream), frames, n_frames, sh, 0, 0.0, 0, 0);
+    return (st || !work) ? st : packed422_nv12_frames_dev(c, pick_stream(c, stream), frames, n_frames, sh, 0, 0.0, 0, 0);
 }
 
 mi_status mi_clahe_packed422_to_nv12_frames_dev(mi_ctx* c, const mi_packed422_nv12_frame_dev* frames, int n_frames,
@@ -170,8 +170,7 @@ mi_status mi_clahe_packed422_to_nv12_frames_dev(mi_ctx* c, const mi_packed422_nv
     const P422Nv12FramesShape sh{width, height, in_pitch, y_pitch, uv_pitch, format, uv_mode};
     bool work = false;
     const mi_status st = check_packed422_nv12_frames(c, frames, n_frames, sh, true, tiles_x, tiles_y, &work);
-    if (st || !work) return st;
-    return packed422_nv12_frames_dev(c, pick_stream(c, stream), frames, n_frames, sh, 1, clip_limit, tiles_x, tiles_y);
+    return (st || !work) ? st : packed422_nv12_frames_dev(c, pick_stream(c, stream), frames, n_frames, sh, 1, clip_limit, tiles_x, tiles_y);
 }
 
 mi_status mi_equalize_hist_packed422_to_nv12(mi_ctx* c, const uint8_t* in, size_t in_pitch, uint8_t* y_out, size_t y_pitch,
@@ -181,8 +180,7 @@ mi_status mi_equalize_hist_packed422_to_nv12(mi_ctx* c, const uint8_t* in, size_
     const P422Nv12Args h = p422_nv12_args(in, in_pitch, 0, y_out, y_pitch, uv_out, uv_pitch, 0, width, height, 1, format, uv_mode);
     bool work = false;
     const mi_status st = check_packed422_nv12_host(c, h, false, 0, 0, &work);
-    if (st || !work) return st;
-    return packed422_nv12_host(c, h, 0, 0.0, 0, 0);
+    return (st || !work) ? st : packed422_nv12_host(c, h, 0, 0.0, 0, 0);
 }
 
 mi_status mi_clahe_packed422_to_nv12(mi_ctx* c, const uint8_t* in, size_t in_pitch, uint8_t* y_out, size_t y_pitch,
@@ -193,8 +191,7 @@ mi_status mi_clahe_packed422_to_nv12(mi_ctx* c, const uint8_t* in, size_t in_pit
     const P422Nv12Args h = p422_nv12_args(in, in_pitch, 0, y_out, y_pitch, uv_out, uv_pitch, 0, width, height, 1, format, uv_mode);
     bool work = false;
     const mi_status st = check_packed422_nv12_host(c, h, true, tiles_x, tiles_y, &work);
-    if (st || !work) return st;
-    return packed422_nv12_host(c, h, 1, clip_limit, tiles_x, tiles_y);
+    return (st || !work) ? st : packed422_nv12_host(c, h, 1, clip_limit, tiles_x, tiles_y);
 }
 
 }  // extern "C"

@@ -91,7 +91,7 @@ mi_status pipe_run_op(mi_pipe* p, PipeSlot& sl)
     if (g.format == MI_FMT_YUY2 || g.format == MI_FMT_UYVY) {     // packed 4:2:2: the whole frame, luma in place, chroma by the same kernels
         const size_t row = (size_t)g.width * 2;
         const P422Args a{sl.d_in, row, fstride, sl.d_out, row, fstride, g.width, g.height, 1, g.format, g.uv_mode};
-        return packed422_dev(c, p->s_k, a, g.op == MI_OP_CLAHE ? 1 : 0, g.clip_limit, g.tiles_x, g.tiles_y);
+        return packed422_dev<PackedOut>(c, p->s_k, a, g.op == MI_OP_CLAHE ? 1 : 0, g.clip_limit, g.tiles_x, g.tiles_y);
     }
     if (g.op == MI_OP_CHANNELS) return nv12_bgr_equalize_dev(c, p->s_k, sl.d_in, fstride, sl.d_out, fstride, g.width, g.height, 1);
     if (g.format == MI_FMT_P010) {                                // 16-bit frames: CLAHE on the 2W-pitch Y plane, the chroma kernel when asked

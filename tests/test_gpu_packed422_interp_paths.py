@@ -1,0 +1,217 @@
+"""Every rung of the CLAHE interpolation ladder on packed 4:2:2 input (YUY2 / UYVY), through every device form: packed out and NV12
+out, each as a strided batch and as a list of frames.  The host picks the interpolation kernel from (writer, list or batch, float or
+quad tables, clahe_fp_contract, format, LDS or global tables); the four sizes below are the smallest that reach each branch of that
+choice, and the options clahe_float_tables and clahe_fp_contract are set both ways, so that every instantiation runs.
+
+    kMaxPairsLdsF32 = 15, kMaxPairsLds = 63, kInterpPx = 16, clahe_seg_pairs = 9 (default); pairs = tiles_x + 1
+    64 x 48,   8 x 8:   9 pairs <= 15: one float table; uchar quads when clahe_float_tables = 0
+    1792 x 8,  16 x 2:  17 pairs > 15, tile_w = 112: (9 - 3) * 112 / 16 = 42 >= 40 column groups per segment, so float tables on
+                        column segments (112 groups in ceil(112 / 42) = 3 segments); quads in one segment when clahe_float_tables = 0
+    64 x 8,    16 x 2:  17 pairs > 15, tile_w = 4: (9 - 3) * 4 / 16 = 1 < 40, quads whatever clahe_float_tables says
+    128 x 8,   64 x 2:  65 pairs > 63: the global-LUT kernel
+
+The expected luma is oracle.clahe on the gathered luma in the arithmetic mode of the call (oracle.set_fp_contract); chroma is copied
+(packed out) or the rounding mean of each row pair (NV12 out).  Every plane lies in a sentinel-filled allocation at a padded pitch,
+the WHOLE allocations are compared, and every comparison is exact bytes."""
+import numpy as np
+import pytest
+import torch
+
+import mi_lumaeq
+import oracle
+from mi_lumaeq import synth, UV_COPY, FMT_YUY2, FMT_UYVY
+
+pytestmark = pytest.mark.gpu
+SENT = 0x5A
+N = 3
+DISTS = ["D1", "D2", "D3"]
+CLIP = 2.0
+# (width, height, tiles_x, tiles_y): plain float tables, column-segment float tables, quad fallback of a wide grid, global LUTs
+SHAPES = [(64, 48, 8, 8), (1792, 8, 16, 2), (64, 8, 16, 2), (128, 8, 64, 2)]
+FORMS = ["packed_batch", "packed_list", "nv12_batch", "nv12_list"]
+FMTS = [FMT_YUY2, FMT_UYVY]
+# (clahe_float_tables, clahe_fp_contract); the first is the default pair, whose bytes the other pair with fp_contract 0 must repeat
+OPTIONS = [(1, 0), (0, 0), (1, 1), (0, 1)]
+OFFS = (4, 8, 12)                                                # bytes past a 16-byte boundary
+
+
+def stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def align4(x):
+    return (x + 3) & ~3
+
+
+def luma(frame, w, fmt):
+    return np.ascontiguousarray(frame[:, fmt - 2:2 * w:2])
+
+
+def chroma(frame, w, fmt):
+    return np.ascontiguousarray(frame[:, 3 - fmt:2 * w:2])
+
+
+def uv_mean(c):
+    """The header's chroma rule: UV row r is the per-byte rounding mean of chroma rows 2r and 2r+1."""
+    a, b = c[0::2], c[1::2]
+    return ((a.astype(np.uint16) + b + 1) >> 1).astype(np.uint8)
+
+
+_ref_cache = {}
+
+
+def y_ref(shape, k, contract):
+    """oracle.clahe on the luma of frame k of a shape (the same plane in both formats), computed once per arithmetic mode."""
+    key = (shape, k, contract)
+    if key not in _ref_cache:
+        w, h, tx, ty = shape
+        old = oracle.set_fp_contract(bool(contract))
+        try:
+            _ref_cache[key] = oracle.clahe(synth.y_plane(w, h, DISTS[k], 500 + k), CLIP, tx, ty)
+        finally:
+            oracle.set_fp_contract(old)
+    return _ref_cache[key]
+
+
+class Layout:
+    """Sentinel-filled device allocations and the planes placed in them, each as (allocation, byte offset, pitch)."""
+
+    def __init__(self):
+        self.bufs = []
+
+    def alloc(self, size):
+        b = torch.full((size,), SENT, dtype=torch.uint8, device="cuda:0")
+        assert b.data_ptr() % 16 == 0
+        self.bufs.append(b)
+        return len(self.bufs) - 1
+
+    def batch(self, pitch, fstride, off):
+        """N planes in one allocation, `fstride` bytes apart, the first `off` bytes in."""
+        b = self.alloc(off + fstride * N + 64)
+        return [(b, off + k * fstride, pitch) for k in range(N)]
+
+    def frames(self, rows, pitch, first):
+        """N planes, each in an allocation of its own at its own offset."""
+        offs = [OFFS[(first + k) % 3] for k in range(N)]
+        return [(self.alloc(o + pitch * rows + 64), o, pitch) for o in offs]
+
+    def ptr(self, at):
+        return self.bufs[at[0]].data_ptr() + at[1]
+
+    def image(self, painted):
+        """All allocations, concatenated, as they must read with `painted` = [(plane, pixels), ...] in them."""
+        imgs = [np.full(b.numel(), SENT, np.uint8) for b in self.bufs]
+        for (bi, off, pitch), px in painted:
+            rows, wb = px.shape
+            imgs[bi][off: off + pitch * rows].reshape(rows, pitch)[:, :wb] = px
+        return np.concatenate(imgs)
+
+    def upload(self, painted):
+        img = torch.from_numpy(self.image(painted)).to("cuda:0")
+        o = 0
+        for b in self.bufs:
+            b.copy_(img[o: o + b.numel()])
+            o += b.numel()
+
+    def host(self):
+        return torch.cat(self.bufs).cpu().numpy()
+
+
+class Case:
+    """One form on one shape: where its inputs and outputs lie, how it is called, what it must write."""
+
+    def __init__(self, form, shape):
+        self.form, self.shape = form, shape
+        w, h = shape[:2]
+        self.nv12, self.list = form.startswith("nv12"), form.endswith("list")
+        self.lay = lay = Layout()
+        self.in_pitch = 2 * w + 4
+        self.in_frame = self.in_pitch * h + 20
+        self.ins = lay.frames(h, self.in_pitch, 0) if self.list else lay.batch(self.in_pitch, self.in_frame, 4)
+        if self.nv12:
+            self.y_pitch, self.uv_pitch = align4(w) + 4, align4(w) + 20
+            self.out_frame = self.y_pitch * h + 12                          # one frame stride for both planes
+            if self.list:
+                self.ys, self.uvs = lay.frames(h, self.y_pitch, 1), lay.frames(h // 2, self.uv_pitch, 2)
+            else:
+                self.ys = lay.batch(self.y_pitch, self.out_frame, 8)
+                self.uvs = lay.batch(self.uv_pitch, self.out_frame, 12)
+        else:
+            self.out_pitch = 2 * w + 36
+            self.out_frame = self.out_pitch * h
+            self.outs = lay.frames(h, self.out_pitch, 1) if self.list else lay.batch(self.out_pitch, self.out_frame, 8)
+
+    def call(self, c, fmt):
+        w, h, tx, ty = self.shape
+        p = self.lay.ptr
+        ins = [p(a) for a in self.ins]
+        if self.nv12:
+            ys, uvs = [p(a) for a in self.ys], [p(a) for a in self.uvs]
+            if self.list:
+                c.clahe_packed422_to_nv12_frames(ins, ys, uvs, w, h, fmt, UV_COPY, CLIP, tx, ty, in_pitch=self.in_pitch,
+                                                 y_pitch=self.y_pitch, uv_pitch=self.uv_pitch, stream=stream())
+            else:
+                c.clahe_packed422_to_nv12_batch_dev(ins[0], ys[0], uvs[0], w, h, N, fmt, UV_COPY, CLIP, tx, ty, in_pitch=self.in_pitch,
+                                                    in_frame=self.in_frame, y_pitch=self.y_pitch, uv_pitch=self.uv_pitch,
+                                                    out_frame=self.out_frame, stream=stream())
+        else:
+            outs = [p(a) for a in self.outs]
+            if self.list:
+                c.clahe_packed422_frames(ins, outs, w, h, fmt, UV_COPY, CLIP, tx, ty, in_pitch=self.in_pitch,
+                                         out_pitch=self.out_pitch, stream=stream())
+            else:
+                c.clahe_packed422_batch_dev(ins[0], outs[0], w, h, N, fmt, UV_COPY, CLIP, tx, ty, in_pitch=self.in_pitch,
+                                            in_frame=self.in_frame, out_pitch=self.out_pitch, out_frame=self.out_frame, stream=stream())
+
+    def expected(self, frames, fmt, contract):
+        """The inputs as uploaded and the outputs of a call, as Layout.image takes them."""
+        w = self.shape[0]
+        painted = list(zip(self.ins, frames))
+        for k, f in enumerate(frames):
+            y = y_ref(self.shape, k, contract)
+            if self.nv12:
+                painted += [(self.ys[k], y), (self.uvs[k], uv_mean(chroma(f, w, fmt)))]
+            else:
+                out = f.copy()
+                out[:, fmt - 2::2] = y
+                painted.append((self.outs[k], out))
+        return painted
+
+
+@pytest.fixture(scope="module")
+def c():
+    with mi_lumaeq.Context(0) as ctx:
+        yield ctx
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%dx%d-%dx%d" % s)
+def test_every_rung(c, shape, form):
+    """Three frames per call; both formats, MI_UV_COPY, clahe_float_tables and clahe_fp_contract both ways.  The bytes are the
+    oracle's in the call's arithmetic mode, and with clahe_fp_contract = 0 also those of the default tables (the same bytes on
+    every path)."""
+    w, h = shape[:2]
+    case = Case(form, shape)
+    try:
+        for fmt in FMTS:
+            frames = [synth.packed422_frame(w, h, fmt, DISTS[k], 500 + k) for k in range(N)]
+            assert all(np.array_equal(luma(f, w, fmt), synth.y_plane(w, h, DISTS[k], 500 + k)) for k, f in enumerate(frames))
+            default = None
+            for float_tables, contract in OPTIONS:
+                why = (form, shape, fmt, float_tables, contract)
+                c.set_option("clahe_float_tables", float_tables)
+                c.set_option("clahe_fp_contract", contract)
+                case.lay.upload(list(zip(case.ins, frames)))                # also resets the outputs to the sentinel
+                case.call(c, fmt)
+                torch.cuda.synchronize()
+                got, want = case.lay.host(), case.lay.image(case.expected(frames, fmt, contract))
+                bad = np.flatnonzero(got != want)
+                print(why, "differing bytes:", bad.size, "first:", bad[:1])
+                assert bad.size == 0, (why, int(bad.size), bad[:8])
+                if (float_tables, contract) == (1, 0):
+                    default = got
+                elif contract == 0:
+                    assert np.array_equal(got, default), (why, "differs from clahe_float_tables = 1")
+    finally:
+        c.set_option("clahe_float_tables", 1)
+        c.set_option("clahe_fp_contract", 0)

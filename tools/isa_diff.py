@@ -29,13 +29,14 @@ def key(n): return re.sub(r'(equalize_fused_kernelILi\d+)ELi0E',r'\1E',n)
 Bk={key(n):n for n in B}
 same=diff=0
 for n in P:
-    bn=Bk.get(n)
+    bn=Bk.get(key(n))
     if bn is None: print('MISSING in branch',n); continue
     pb=[l.replace(n,'K') for l in P[n]]; bb=[l.replace(bn,'K') for l in B[bn]]
     if pb==bb and mp[n]==mb[bn]: same+=1
     else: diff+=1; print('DIFF',n,len(pb),len(bb),mp[n],mb[bn])
 print('parent kernels',len(P),'identical',same,'different',diff)
-new=[n for n in B if key(n) not in P]
+Pk={key(n) for n in P}
+new=[n for n in B if key(n) not in Pk]
 for n in new:
     body=B[n]
     c=collections.Counter()
