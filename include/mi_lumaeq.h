@@ -442,6 +442,53 @@ mi_status mi_clahe_packed422_to_nv12(mi_ctx* ctx, const uint8_t* in, size_t in_p
         uint8_t* y_out, size_t y_pitch, uint8_t* uv_out, size_t uv_pitch,
         int width, int height, int format, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
 
+/* mi_*_nv12_to_bgr*: NV12 frames in, interleaved 8-bit BGR (or RGB) images out, in the pass that equalizes -- decoder -> display, image
+ * writer or model without an NV12 intermediate.  Per frame the result is what OpenCV 4.4 gives for
+ *     cv::Mat y = nv12(Rect(0, 0, W, H));  cv::equalizeHist(y, y)  /  clahe->apply(y, y);        (Y only, UV untouched)
+ *     cv::cvtColor(nv12, bgr, cv::COLOR_YUV2BGR_NV12);                                           (COLOR_YUV2RGB_NV12 for MI_ORDER_RGB)
+ * and byte for byte what mi_equalize_hist_nv12_batch_dev / mi_clahe_nv12_batch_dev with MI_UV_COPY followed by
+ * mi_cvt_color_420_u8_batch_dev(..., MI_COLOR_YUV2BGR_NV12) writes in two calls: the same clahe_fp_contract option, the same REFLECT_101
+ * padding when the tile grid does not divide the frame, the same limits on sizes and tile grids.  The two calls move 8.5 bytes per
+ * pixel and need an NV12 batch in between; this form reads Y twice (histograms, then map), UV once, and writes 3 bytes per pixel: 5.5.
+ *   input  : frame f has a Y plane at d_y + f * in_frame_stride, H rows of W bytes at y_pitch >= W, and a UV plane at
+ *            d_uv + f * in_frame_stride, H/2 rows of W bytes (interleaved U and V) at uv_pitch >= W.  A tight NV12 batch is
+ *            d_uv = d_y + W*H, both pitches W, in_frame_stride = W*H*3/2; pitched decoder surfaces in one allocation are the general
+ *            case.  The input is never written.
+ *   output : frame f at d_out + f * out_frame_stride, H rows of 3*W bytes at out_pitch >= 3*W: B, G, R per pixel (MI_ORDER_BGR) or
+ *            R, G, B (MI_ORDER_RGB).  Only the 3*W bytes of each output row are written: not the pitch padding, not the gap between
+ *            frames.
+ * Width and height are even.  No alignment is required of any pointer, pitch or stride: when W % 16 == 0 and every pointer, pitch and
+ * frame stride is a multiple of 16 the kernels move 16 bytes per access, otherwise bytes -- slower, the same bytes out.
+ * equalizeHist maps the luma and converts in one kernel.  CLAHE does so for the common shape -- the tile grid divides the frame,
+ * tile width a multiple of 16, tiles_x <= 14, everything 16-byte aligned as above, clahe_fp_contract off; any other shape runs the planar
+ * CLAHE into a scratch Y plane of the context and converts from there: the same bytes in one more pass (statistics "nv12_bgr_onepass" /
+ * "nv12_bgr_twopass" count the calls of each kind).  Never the fused equalizeHist kernel nor the single-launch histogram + LUT kernel
+ * (option two_kernel_max_frames does not apply).  Launches are charged to the existing profiling slots by role: MI_K_HIST, MI_K_EQ_LUT,
+ * MI_K_TILE_HIST, MI_K_TILE_LUT for the histogram stages, MI_K_LUT_APPLY / MI_K_CLAHE_INTERP for the kernel that maps and converts,
+ * MI_K_COLOR for the conversion of the two-pass fallback.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of the
+ * same shape as the other batched device forms.
+ * mi_equalize_hist_nv12_to_bgr / mi_clahe_nv12_to_bgr: ONE tight NV12 frame in host memory (W*H*3/2 bytes) in, a CV_8UC3 image at
+ *   out_step >= 3*W out; synchronous, staged like mi_nv12_bgr_equalize / mi_cvt_color_420_u8 (images in pinned memory that are tight are
+ *   DMA'd as they are, everything else goes through the context's pinned staging).  Whatever the call returns, no copy on nv12_in / out is
+ *   in flight any more when it returns.  W*H beyond what mi_cvt_color_420_u8 accepts: MI_ERR_UNSUPPORTED.
+ * Errors, MI_ERR_BAD_ARG: a null ctx or plane pointer, an odd width or an odd height (refused even when another size is 0, as in the
+ * packed -> NV12 forms), a negative size, a pitch below its row (y_pitch < W, uv_pitch < W, out_pitch < 3*W), an `order` other than the
+ * two, tiles <= 0, d_out == d_y or d_out == d_uv (there is no in-place form).  Any other overlap of input and output: undefined, not
+ * checked.  width, height or n_frames of 0: MI_OK, nothing written.  Sizes and tile grids the planar forms refuse: the status they give
+ * (MI_ERR_UNSUPPORTED), nothing written.  Nothing is enqueued unless all checks pass. */
+enum { MI_ORDER_BGR = 0, MI_ORDER_RGB = 1 };
+mi_status mi_equalize_hist_nv12_to_bgr_batch_dev(mi_ctx* ctx, const void* d_y, size_t y_pitch, const void* d_uv, size_t uv_pitch,
+        size_t in_frame_stride, void* d_out, size_t out_pitch, size_t out_frame_stride,
+        int width, int height, int n_frames, int order, void* stream);
+mi_status mi_clahe_nv12_to_bgr_batch_dev(mi_ctx* ctx, const void* d_y, size_t y_pitch, const void* d_uv, size_t uv_pitch,
+        size_t in_frame_stride, void* d_out, size_t out_pitch, size_t out_frame_stride,
+        int width, int height, int n_frames, int order, double clip_limit, int tiles_x, int tiles_y, void* stream);
+mi_status mi_equalize_hist_nv12_to_bgr(mi_ctx* ctx, const uint8_t* nv12_in, uint8_t* out, size_t out_step,
+        int width, int height, int order);
+mi_status mi_clahe_nv12_to_bgr(mi_ctx* ctx, const uint8_t* nv12_in, uint8_t* out, size_t out_step,
+        int width, int height, int order, double clip_limit, int tiles_x, int tiles_y);
+
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at
  * OpenCVequalHist.cpp:115/:158).  Registering a pool's memory once lets the host-pointer forms DMA straight
@@ -611,7 +658,8 @@ mi_status mi_cvt_color_420_u8_batch_dev(mi_ctx* ctx, const void* d_src, size_t s
  * "host_planes_direct" (host planes -- inputs and outputs of the host forms and of pipe frames -- packed through the library's
  * pinned staging / DMA'd as the caller pinned them: the library never gives the runtime memory it did not find pinned),
  * "clahe16_mid_launches" (mi_clahe_u16* calls that launched the 16384-entry interpolation kernel for 14-bit content; see
- * MI_OPT_CLAHE16_WIDE in mi_lumaeq_tuning.h). */
+ * MI_OPT_CLAHE16_WIDE in mi_lumaeq_tuning.h), "nv12_bgr_onepass" / "nv12_bgr_twopass" (mi_*_nv12_to_bgr* calls that mapped and converted
+ * in one kernel / that took the planar CLAHE + conversion fallback). */
 mi_status mi_ctx_synchronize(mi_ctx* ctx, void* stream);
 mi_status mi_ctx_set_option(mi_ctx* ctx, const char* name, int value);
 mi_status mi_ctx_get_stat(mi_ctx* ctx, const char* name, uint64_t* out);

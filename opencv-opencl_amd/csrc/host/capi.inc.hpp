@@ -344,7 +344,9 @@ mi_status mi_ctx_synchronize(mi_ctx* c, void* stream)
 // a stream before returning), "host_copies_shared" (staging copies the helper thread took half of), "clahe16_mid_launches" (16-bit
 // CLAHE calls that launched clahe_interp16_mid_kernel: by the pinned-memory hint, or always / never by option "clahe16_wide"),
 // "fused_last_policy" (cache-policy code of the last fused launch this context made, see equalize_fused_kernel; all ones before the first),
-// "fused_stream_min_bytes" (bytes a launch loads and stores from which fused_cache_policy = 0 chooses the streaming policy).
+// "fused_stream_min_bytes" (bytes a launch loads and stores from which fused_cache_policy = 0 chooses the streaming policy),
+// "nv12_bgr_onepass" / "nv12_bgr_twopass" (mi_*_nv12_to_bgr* calls whose pixels were mapped and converted in one kernel / that ran the
+// planar CLAHE into scratch and the conversion after it).
 mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
 {
     ENTER(c);
@@ -368,6 +370,8 @@ mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
             *out = st4[k];
             return MI_OK;
         }
+    if (!strcmp(name, "nv12_bgr_onepass")) { *out = c->nv12_bgr_onepass; return MI_OK; }
+    if (!strcmp(name, "nv12_bgr_twopass")) { *out = c->nv12_bgr_twopass; return MI_OK; }
     return fail(c, MI_ERR_BAD_ARG, "unknown stat");
 }
 

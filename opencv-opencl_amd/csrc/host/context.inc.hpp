@@ -158,6 +158,8 @@ struct mi_ctx {
     mi_profile prof{};
     std::vector<float> samples[MI_K_COUNT];                      // per-launch durations since the last reset (ring of 65 536)
     size_t sample_pos[MI_K_COUNT] = {};
+    unsigned long long nv12_bgr_onepass = 0, nv12_bgr_twopass = 0;      // statistics "nv12_bgr_onepass" / "nv12_bgr_twopass": mi_*_nv12_to_bgr* calls whose pixels
+                                                                        // were mapped and converted in one kernel / that took the planar CLAHE + decode fallback
 };
 
 namespace {

@@ -32,6 +32,7 @@
 //   kernels/p010.hip.h            chroma half of 16-bit 4:2:0 frames (P010 / P012 / P016): copy or fill 0x8000
 //   kernels/packed422.hip.h       the pixel-touching stages on packed 4:2:2 frames (YUY2 / UYVY): luma at a 2-byte sample stride
 //   kernels/packed422_nv12.hip.h  the pixel-writing stages of packed 4:2:2 in, NV12 out: Y plane + vertically halved chroma in one pass
+//   kernels/nv12_bgr.hip.h         the pixel-writing stages of NV12 in, interleaved BGR / RGB out: LUT apply + decode, CLAHE blend + decode
 #pragma once
 #include "kernels/common.hip.h"
 #include "kernels/equalize.hip.h"
@@ -44,3 +45,4 @@
 #include "kernels/p010.hip.h"
 #include "kernels/packed422.hip.h"
 #include "kernels/packed422_nv12.hip.h"
+#include "kernels/nv12_bgr.hip.h"

@@ -475,6 +475,24 @@ inline void clahePacked422ToNV12(const unsigned char* in, size_t inPitch, unsign
                                                 (mi_uv_mode)uv, clipLimit, tiles.width, tiles.height), "mi_clahe_packed422_to_nv12");
 }
 
+// Tight NV12 frames from a decoder in, interleaved CV_8UC3 images out (BGR, or RGB) in the pass that equalizes: cv::equalizeHist /
+// CLAHE::apply on the Y plane + cv::cvtColor(COLOR_YUV2BGR_NV12) without the NV12 frame in between.  `out`: H rows of 3*W bytes at
+// outStep >= 3*W in host memory.  Width and height are even.
+enum ChannelOrder { ORDER_BGR = MI_ORDER_BGR, ORDER_RGB = MI_ORDER_RGB };
+inline void equalizeHistNV12ToBGR(const unsigned char* nv12, unsigned char* out, size_t outStep, int width, int height,
+                                  ChannelOrder order = ORDER_BGR)
+{
+    mi_ctx* c = detail::thread_ctx();
+    detail::check(c, mi_equalize_hist_nv12_to_bgr(c, nv12, out, outStep, width, height, (int)order), "mi_equalize_hist_nv12_to_bgr");
+}
+inline void claheNV12ToBGR(const unsigned char* nv12, unsigned char* out, size_t outStep, int width, int height, double clipLimit,
+                           Size tiles, ChannelOrder order = ORDER_BGR)
+{
+    mi_ctx* c = detail::thread_ctx();
+    detail::check(c, mi_clahe_nv12_to_bgr(c, nv12, out, outStep, width, height, (int)order, clipLimit, tiles.width, tiles.height),
+                  "mi_clahe_nv12_to_bgr");
+}
+
 // BASELINE.json config 5 read literally: cvtColor(COLOR_YUV2BGR_NV12) -> split -> equalizeHist on B, G and R -> merge ->
 // cvtColor(COLOR_BGR2YUV_I420) + U/V interleave, NV12 in -> NV12 out in one call (no file of the reference does this;
 // ColoropenCVCwqualHist.cpp itself is equalizeHistNV12(..., UV_COPY)).  Width and height must be even.

@@ -25,6 +25,7 @@ OP_EQUALIZE, OP_CLAHE, OP_CHANNELS = 0, 1, 2
 PIPE_UV_AUTO, PIPE_UV_HOST, PIPE_UV_DEVICE = 0, 1, 2
 FMT_NV12, FMT_P010 = 0, 1              # MI_FMT_*: P010 = any 16-bit LE 4:2:0 semi-planar frame (P010 / P012 / P016)
 FMT_YUY2, FMT_UYVY = 2, 3              # packed 8-bit 4:2:2: luma at byte 0 (YUY2 / YUYV / YVYU) or byte 1 (UYVY / VYUY) of each 2-byte pixel
+ORDER_BGR, ORDER_RGB = 0, 1            # MI_ORDER_*: channel order of the interleaved output of the NV12 -> BGR forms
 ERR_BUSY = 6
 
 # every extern "C" symbol include/mi_lumaeq.h declares (tests check the .so exports them all)
@@ -52,6 +53,7 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_packed422_to_nv12_batch_dev", "mi_clahe_packed422_to_nv12_batch_dev",
     "mi_equalize_hist_packed422_to_nv12_frames_dev", "mi_clahe_packed422_to_nv12_frames_dev",
     "mi_equalize_hist_packed422_to_nv12", "mi_clahe_packed422_to_nv12",
+    "mi_equalize_hist_nv12_to_bgr_batch_dev", "mi_clahe_nv12_to_bgr_batch_dev", "mi_equalize_hist_nv12_to_bgr", "mi_clahe_nv12_to_bgr",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -180,6 +182,10 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_packed422_to_nv12_frames_dev.argtypes = [vp, C.POINTER(Packed422Nv12FrameDev), i, i, i, sz, sz, sz, i, i, d, i, i, vp]
     L.mi_equalize_hist_packed422_to_nv12.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, i]
     L.mi_clahe_packed422_to_nv12.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, i, d, i, i]
+    L.mi_equalize_hist_nv12_to_bgr_batch_dev.argtypes = [vp, vp, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp]
+    L.mi_clahe_nv12_to_bgr_batch_dev.argtypes = [vp, vp, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_nv12_to_bgr.argtypes = [vp, vp, vp, sz, i, i, i]
+    L.mi_clahe_nv12_to_bgr.argtypes = [vp, vp, vp, sz, i, i, i, d, i, i]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -744,6 +750,68 @@ class Context:
                                                    uv_out.ctypes.data, _step(uv_out), int(width), int(h), int(fmt), int(uv_mode),
                                                    float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_packed422_to_nv12")
         return y_out, uv_out
+
+    # ---- NV12 in, interleaved BGR / RGB out in the pass that maps the luma ----
+    @staticmethod
+    def _nv12_in(d_y, d_uv, width, height, y_pitch, uv_pitch, in_frame):
+        """Addresses and strides of the NV12 side; d_uv None: the UV plane directly behind the Y plane (y_pitch * H further)."""
+        yp = int(width) if y_pitch is None else int(y_pitch)
+        up = int(width) if uv_pitch is None else int(uv_pitch)
+        y = _dptr(d_y)
+        uv = _dptr(d_uv) if d_uv is not None else (y + yp * int(height) if y else y)
+        fi = yp * int(height) + up * (int(height) // 2) if in_frame is None else int(in_frame)
+        return y, yp, uv, up, fi
+
+    def equalize_hist_nv12_to_bgr_batch_dev(self, d_y, d_uv, d_out, width, height, n_frames, order=ORDER_BGR, y_pitch=None, uv_pitch=None,
+                                            in_frame=None, out_pitch=None, out_frame=None, stream=0):
+        """mi_equalize_hist_nv12_to_bgr_batch_dev: n_frames NV12 frames in, interleaved BGR / RGB images out (torch tensors or raw
+        addresses).  Tight layouts are the defaults: y_pitch = uv_pitch = W, in_frame = y_pitch * H + uv_pitch * H/2, out_pitch 3*W,
+        out_frame = out_pitch * H; d_uv None puts the UV plane directly behind the Y plane (one tight NV12 batch in d_y)."""
+        y, yp, uv, up, fi = self._nv12_in(d_y, d_uv, width, height, y_pitch, uv_pitch, in_frame)
+        op = 3 * int(width) if out_pitch is None else int(out_pitch)
+        fo = op * int(height) if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_equalize_hist_nv12_to_bgr_batch_dev(self._h, y, yp, uv, up, fi, _dptr(d_out), op, fo, int(width), int(height),
+                                                               int(n_frames), int(order), stream),
+                  "mi_equalize_hist_nv12_to_bgr_batch_dev")
+
+    def clahe_nv12_to_bgr_batch_dev(self, d_y, d_uv, d_out, width, height, n_frames, order=ORDER_BGR, clip_limit=2.0, tiles_x=8, tiles_y=8,
+                                    y_pitch=None, uv_pitch=None, in_frame=None, out_pitch=None, out_frame=None, stream=0):
+        """mi_clahe_nv12_to_bgr_batch_dev; arguments as equalize_hist_nv12_to_bgr_batch_dev, plus the CLAHE parameters."""
+        y, yp, uv, up, fi = self._nv12_in(d_y, d_uv, width, height, y_pitch, uv_pitch, in_frame)
+        op = 3 * int(width) if out_pitch is None else int(out_pitch)
+        fo = op * int(height) if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_clahe_nv12_to_bgr_batch_dev(self._h, y, yp, uv, up, fi, _dptr(d_out), op, fo, int(width), int(height),
+                                                       int(n_frames), int(order), float(clip_limit), int(tiles_x), int(tiles_y), stream),
+                  "mi_clahe_nv12_to_bgr_batch_dev")
+
+    def _nv12_bgr_host(self, nv12, width, height, out, name):
+        if not isinstance(nv12, np.ndarray) or nv12.dtype != np.uint8 or not nv12.flags.c_contiguous:
+            raise MiError(2, name, "expected a contiguous uint8 ndarray")
+        if width >= 0 and height >= 0 and nv12.size != width * height * 3 // 2:
+            raise MiError(1, name, "NV12 frame must hold width*height*3/2 bytes")
+        if out is None:
+            out = np.empty((max(height, 0), max(width, 0), 3), np.uint8)
+        out = self._host3(out, name)
+        if out.shape[:2] != (height, width):
+            raise MiError(1, name, "out must be an H x W x 3 uint8 array (rows may be padded)")
+        return out, (int(out.strides[0]) if height > 1 else max(int(out.strides[0]), 3 * width))
+
+    def equalize_hist_nv12_to_bgr(self, nv12: np.ndarray, width: int, height: int, order: int = ORDER_BGR,
+                                  out: np.ndarray | None = None) -> np.ndarray:
+        """mi_equalize_hist_nv12_to_bgr on a tight host NV12 frame: the H x W x 3 image out -- `out` when given (a view with padded rows
+        included), else a new tight array."""
+        out, step = self._nv12_bgr_host(nv12, int(width), int(height), out, "equalize_hist_nv12_to_bgr")
+        self._chk(self._L.mi_equalize_hist_nv12_to_bgr(self._h, nv12.ctypes.data, out.ctypes.data, step, int(width), int(height), int(order)),
+                  "mi_equalize_hist_nv12_to_bgr")
+        return out
+
+    def clahe_nv12_to_bgr(self, nv12: np.ndarray, width: int, height: int, order: int = ORDER_BGR, clip_limit: float = 2.0,
+                          tiles_x: int = 8, tiles_y: int = 8, out: np.ndarray | None = None) -> np.ndarray:
+        """mi_clahe_nv12_to_bgr; arguments as equalize_hist_nv12_to_bgr, plus the CLAHE parameters."""
+        out, step = self._nv12_bgr_host(nv12, int(width), int(height), out, "clahe_nv12_to_bgr")
+        self._chk(self._L.mi_clahe_nv12_to_bgr(self._h, nv12.ctypes.data, out.ctypes.data, step, int(width), int(height), int(order),
+                                             float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_nv12_to_bgr")
+        return out
 
     # ---- colour-domain neighbours (N3) ----
     @staticmethod
