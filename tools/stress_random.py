@@ -1,6 +1,7 @@
 """Bounded random differential run, HIP vs oracle, aimed at the code paths a fixed test list visits only at a few points: ROI pitches
 (multiples of 16 and not) with random origins, wide CLAHE grids at sizes where the per-segment float tables apply, large batches of small
-tiles (several tiles per histogram workgroup), 16-bit CLAHE at random value ranges, the 4:2:0 codes at random aligned / unaligned sizes.
+tiles (several tiles per histogram workgroup), 16-bit CLAHE at random value ranges, the 4:2:0 codes at random aligned / unaligned sizes, NV12 in / BGR out
+at random pitched layouts (aligned and not) and tile grids on both sides of its one-pass conditions.
     python tools/stress_random.py [seconds] [seed] [option=value ...]        prints a line every ~15 s, exits non-zero on the first mismatch"""
 import sys, time
 sys.path.insert(0, "opencv-opencl_amd/python"); sys.path.insert(0, ".")
@@ -12,12 +13,12 @@ rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 ctx = mi_lumaeq.Context(0)
 for kv in sys.argv[3:]:                                          # name=value options for the whole run, e.g. clahe16_wide=2 (mid kernel always launched)
     k_, v_ = kv.split("="); ctx.set_option(k_, int(v_)); print("option", k_, "=", v_, flush=True)
-t0 = last = time.time(); n = {"roi": 0, "grid": 0, "small": 0, "c16": 0, "420": 0, "nv12": 0}
+t0 = last = time.time(); n = {"roi": 0, "grid": 0, "small": 0, "c16": 0, "420": 0, "nv12": 0, "nv12bgr": 0}
 def dev(a): return xfer.to_device(np.ascontiguousarray(a))
 def fail(what, *info):
     print("MISMATCH", what, info, flush=True); sys.exit(1)
 while time.time() - t0 < budget:
-    k = int(rng.integers(0, 6))
+    k = int(rng.integers(0, 7))
     if k == 0:      # ROI batch on the device: random pitches, origins, sizes
         w, h, nf = int(rng.integers(1, 700)), int(rng.integers(1, 90)), int(rng.integers(1, 6))
         sp = w + int(rng.integers(0, 40)); sp += (16 - sp % 16) % 16 if rng.integers(0, 2) else 0
@@ -82,6 +83,33 @@ while time.time() - t0 < budget:
         for f in range(nf):
             if not np.array_equal(out[f], oracle.nv12_frame(fr[f], w, h, uv_mode=uv, op=op, clip_limit=2.0, tiles_x=4, tiles_y=4)): fail("nv12", w, h, nf, uv, op, inplace, f)
         n["nv12"] += 1
+    elif k == 6:    # NV12 in, BGR / RGB out: pitched layouts, aligned (16-byte accesses, CLAHE in one pass where the grid allows) or not, both ops
+        w, h, nf = int(rng.integers(1, 40)) * (16 if rng.integers(0, 2) else 2), int(rng.integers(1, 60)) * 2, int(rng.integers(1, 5))
+        op, order = int(rng.integers(0, 2)), int(rng.integers(0, 2)); tx, ty = int(rng.integers(1, 17)), int(rng.integers(1, 6))
+        clip = float(rng.choice([0.0, 1.0, 2.0, 40.0]))
+        if op == 1 and w % 16 == 0 and rng.integers(0, 4): w, h = 16 * tx * int(rng.integers(1, 4)), 2 * ty * int(rng.integers(1, 12))
+        al = 16 if rng.integers(0, 4) else 1                           # every pitch, gap and offset a multiple of `al`
+        def pad(v): return (v + al - 1) // al * al + al * int(rng.integers(0, 40 // al + 1))
+        yp, up, opi = pad(w), pad(w), pad(3 * w); off, gap, fgap, ooff, ofgap = (pad(0) for _ in range(5))
+        uv_off = yp * h + gap; fi = uv_off + up * (h // 2) + fgap; fo = opi * h + ofgap
+        fr = rng.integers(0, 256, (nf, w * h * 3 // 2), dtype=np.uint8)
+        img = np.full(off + fi * nf + 64, 0x5A, np.uint8)
+        for f in range(nf):
+            o = off + f * fi
+            img[o: o + yp * h].reshape(h, yp)[:, :w] = fr[f, : w * h].reshape(h, w)
+            img[o + uv_off: o + uv_off + up * (h // 2)].reshape(h // 2, up)[:, :w] = fr[f, w * h:].reshape(h // 2, w)
+        d_in = dev(img); d_out = torch.full((ooff + fo * nf + 64,), 0x5A, dtype=torch.uint8, device="cuda")
+        a = (d_in.data_ptr() + off, d_in.data_ptr() + off + uv_off, d_out.data_ptr() + ooff, w, h, nf, order)
+        kw = dict(y_pitch=yp, uv_pitch=up, in_frame=fi, out_pitch=opi, out_frame=fo)
+        if op == 0: ctx.equalize_hist_nv12_to_bgr_batch_dev(*a, **kw)
+        else: ctx.clahe_nv12_to_bgr_batch_dev(*a, clip, tx, ty, **kw)
+        ctx.synchronize(); out = xfer.to_host(d_out); want = np.full(out.size, 0x5A, np.uint8)
+        for f in range(nf):
+            bgr = oracle.nv12_to_bgr(oracle.nv12_frame(fr[f], w, h, uv_mode=1, op=op, clip_limit=clip, tiles_x=tx, tiles_y=ty), w, h)
+            want[ooff + f * fo: ooff + f * fo + opi * h].reshape(h, opi)[:, : 3 * w] = (bgr if order == 0 else bgr[:, :, ::-1]).reshape(h, 3 * w)
+        if not np.array_equal(out, want): fail("nv12bgr", w, h, nf, op, order, clip, tx, ty, al, yp, up, opi, off, gap, fgap, ooff, ofgap, np.flatnonzero(out != want)[:8])
+        if not np.array_equal(xfer.to_host(d_in), img): fail("nv12bgr wrote its input", w, h, nf, op)
+        n["nv12bgr"] += 1
     else:           # 4:2:0 codes
         w, h = int(rng.integers(1, 60)) * (16 if rng.integers(0, 2) else 2), int(rng.integers(1, 40)) * 2
         bgr = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
