@@ -396,21 +396,41 @@ __device__ __forceinline__ u32x4 clahe_vec16_f32(const f32x4* quadf, u32x4 q, co
     return o;
 }
 
-// pair_cap: pairs the LDS table holds.  With tiles_x + 1 <= pair_cap the table covers every pair of the frame; otherwise each column
-// segment (blockIdx.z, `groups` 16-pixel groups wide -- the host sizes it so that a segment touches at most pair_cap pairs) stages only
-// the pairs ITS columns use, first pair = p0 below, and the float tables serve grids of up to 63 tiles across (16 x 16 on 4K: the
-// interpolation 322 -> see DESIGN.md).
-template <bool FT, bool FMA, class Frames>
-__device__ __forceinline__ void clahe_interp_body(const PlaneBatch& p, const Frames& fr, const ClaheGeom& g, const uint8_t* __restrict__ luts,
-                                                  int subs, int groups, int pair_cap)
+// ---------------------------------------------------------------------------------------------
+// The front of the interpolation stage, shared by clahe_interp_body below, clahe_interp422_body (packed422.hip.h) and
+// clahe_interp422_nv12_body (packed422_nv12.hip.h): these forms differ only in how a lane loads its 16 pixels and stores the result.
+// interp_stage() decodes frame, band and sub-band from the block index, stages the pair table into LDS (u32 quads, or f32x4
+// {a, c, b, d} when FT), barrier included, and cuts the band's rows into `subs` contiguous sub-ranges.
+//  * Frames are walked last-to-first: the histogram pass has just streamed the batch first-to-last, so its tail is what the
+//    memory-side Infinity Cache still holds.
+//  * pair_cap: pairs the LDS table holds.  With tiles_x + 1 <= pair_cap the table covers every pair of the frame; otherwise each
+//    column segment (blockIdx.z, `groups` 16-pixel groups wide -- the host sizes it so that a segment touches at most pair_cap pairs)
+//    stages only the pairs ITS columns use, first pair = p0, and the float tables serve grids of up to 63 tiles across (16 x 16 on
+//    4K: the interpolation 322 -> see DESIGN.md).
+//  * Rows of a band: ideal range [(band-0.5)*th, (band+0.5)*th), widened by kBandMargin rows each side.  The caller then trims
+//    [y_lo, y_hi) by the float-computed ty1, so that the decision is exactly the reference's: ty1 is monotone in y, so at most
+//    kBandMargin+1 steps per end with the reference's own float expression.  Rows of a lane: the first row >= the trimmed start
+//    that is congruent to y_lo + phase (mod phases), then + phases (sub-ranges are contiguous per block, phases interleave inside).
+// What could NOT be shared, because every form tried changed the generated code of the kernels it was used in:
+//  * the per-lane column weights (xa, xa1, xw, poff) and the row trim with the lane's first row stay written out in each of the five
+//    bodies, in the same words;
+//  * nv12_bgr_clahe_interp_kernel and bgr_clahe_interp_kernel (f32 tables, no segment window) keep their own copy of this whole front.
+// `g` is taken by value on purpose: by reference the planar kernels' code changes.  Whoever edits this function, or one of the
+// duplicated pieces, compares the kernels before and after (tools/isa_diff.py) and makes the change in every copy.
+// ---------------------------------------------------------------------------------------------
+struct InterpStage {
+    int f;               // frame of this workgroup
+    int ty1u;            // unclamped ty1 of every row of the band
+    int p0, npairs;      // first pair and number of pairs in this workgroup's LDS table
+    int y_lo, y_hi;      // rows of this sub-band, still widened by the margin
+};
+template <bool FT, bool FMA>
+__device__ __forceinline__ InterpStage interp_stage(uint32_t* quad, const ClaheGeom g, const uint8_t* __restrict__ luts, int subs, int groups, int pair_cap)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t quad[];   // [(tiles_x + 1)][256] u32 quads, or f32x4 when FT
     f32x4* quadf = reinterpret_cast<f32x4*>(quad);
-    // frames are walked last-to-first: the histogram pass has just streamed the batch first-to-last, so its tail is what the
-    // memory-side Infinity Cache still holds
     const int t = threadIdx.x, f = (int)gridDim.y - 1 - (int)blockIdx.y;
     const int band = blockIdx.x / subs, sub = blockIdx.x - band * subs;
-    const int ty1u = band - 1;                                // unclamped ty1 of every row of the band
+    const int ty1u = band - 1;
     const int ty1 = max(ty1u, 0), ty2 = min(ty1u + 1, g.tiles_y - 1);
     const uint8_t* lf = luts + (size_t)f * g.tiles_x * g.tiles_y * 256;
     const uint8_t* l1 = lf + (size_t)ty1 * g.tiles_x * 256;
@@ -436,18 +456,29 @@ __device__ __forceinline__ void clahe_interp_body(const PlaneBatch& p, const Fra
     }
     __syncthreads();
 
-    // rows of this band: ideal range [(band-0.5)*th, (band+0.5)*th), widened by kBandMargin rows each side and
-    // filtered by the float-computed ty1 so the decision is exactly the reference's.
     const int y_lo_band = (int)max(0LL, ((long long)(2 * band - 1) * g.tile_h) / 2 - kBandMargin);
     const int y_hi_band = (int)min((long long)g.height, ((long long)(2 * band + 1) * g.tile_h + 1) / 2 + kBandMargin);
     const int nrows = max(0, y_hi_band - y_lo_band);
     const int y_lo = y_lo_band + (int)((long long)nrows * sub / subs);
     const int y_hi = y_lo_band + (int)((long long)nrows * (sub + 1) / subs);
+    return {f, ty1u, p0, npairs, y_lo, y_hi};
+}
+
+template <bool FT, bool FMA, class Frames>
+__device__ __forceinline__ void clahe_interp_body(const PlaneBatch& p, const Frames& fr, const ClaheGeom& g, const uint8_t* __restrict__ luts,
+                                                  int subs, int groups, int pair_cap)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t quad[];   // [(tiles_x + 1)][256] u32 quads, or f32x4 when FT
+    f32x4* quadf = reinterpret_cast<f32x4*>(quad);
+    const InterpStage st = interp_stage<FT, FMA>(quad, g, luts, subs, groups, pair_cap);
+    const int t = threadIdx.x, f = st.f, ty1u = st.ty1u;
 
     const int phases = kThreads / groups;
     const int grp = t % groups, phase = t / groups;
     const int x0 = (blockIdx.z * groups + grp) * kInterpPx;
     if (phase < phases && x0 < g.width) {
+        const int p0 = st.p0, npairs = st.npairs, y_lo = st.y_lo, y_hi = st.y_hi;
+        // column weights, row trim and first row: duplicated in the five bodies, see interp_stage
         float xa[kInterpPx], xa1[kInterpPx];
         f32x2 xw[kInterpPx];                                   // {xa1, xa} pairs for the packed float-table body
         int poff[kInterpPx];
@@ -467,13 +498,10 @@ __device__ __forceinline__ void clahe_interp_body(const PlaneBatch& p, const Fra
         const uint8_t* src = fr.src_of(f);
         uint8_t* dst = fr.dst_of(f);
         const bool full = x0 + kInterpPx <= g.width;
-        // ty1 is monotone in y: trim the widened range to the rows that really belong to this band, using the
-        // reference's own float expression (at most kBandMargin+1 steps per end)
         auto ty1_of = [&](int y) { return floor_f32_to_int(tile_coord<FMA>(y, g.inv_th)); };
         int ya_lo = y_lo, ya_hi = y_hi;
         while (ya_lo < ya_hi && ty1_of(ya_lo) != ty1u) ++ya_lo;
         while (ya_hi > ya_lo && ty1_of(ya_hi - 1) != ty1u) --ya_hi;
-        // rows of this lane: ya_lo + phase, + phases, ...  (sub-ranges are contiguous per block, phases interleave inside)
         int y = ya_lo + ((phase - (ya_lo - y_lo) % phases) % phases + phases) % phases;
         if (full) {
             // The loop is VALU-issue bound (~290 instructions per 16 pixels: 64 byte->float converts, 144 blend

@@ -126,6 +126,8 @@ __global__ __launch_bounds__(kThreads) void nv12_bgr_clahe_interp_kernel(Nv12Bgr
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t quad[];
     f32x4* quadf = reinterpret_cast<f32x4*>(quad);
+    // A copy of interp_stage<true, false> (clahe.hip.h) without the column-segment window, then of the column weights and the row
+    // trim: calling interp_stage here changed this kernel's table fill loop, so the copy stays; a change there is made here too.
     const int t = threadIdx.x, f = (int)gridDim.y - 1 - (int)blockIdx.y;      // last-to-first, see clahe_interp_kernel
     const int band = blockIdx.x / subs, sub = blockIdx.x - band * subs;
     const int ty1u = band - 1;
@@ -154,7 +156,7 @@ __global__ __launch_bounds__(kThreads) void nv12_bgr_clahe_interp_kernel(Nv12Bgr
     int poff[kInterpPx];
 #pragma unroll
     for (int k = 0; k < kInterpPx; ++k) {
-        const float txf = __fsub_rn(__fmul_rn((float)(x0 + k), g.inv_tw), 0.5f);
+        const float txf = tile_coord<false>(x0 + k, g.inv_tw);
         const int tx1 = floor_f32_to_int(txf);
         const float xa = __fsub_rn(txf, (float)tx1);
         xw[k].x = __fsub_rn(1.0f, xa); xw[k].y = xa;
@@ -165,12 +167,12 @@ __global__ __launch_bounds__(kThreads) void nv12_bgr_clahe_interp_kernel(Nv12Bgr
     const uint8_t* yp = j.y + (long long)f * j.y_frame + x0;
     const uint8_t* uvp = j.uv + (long long)f * j.uv_frame + x0;            // pair k of the group: bytes x0 + 2k, x0 + 2k + 1 of the UV row
     uint8_t* dst = j.out + (long long)f * j.out_frame + (long long)x0 * 3;
-    auto ty1_of = [&](int y) { return floor_f32_to_int(__fsub_rn(__fmul_rn((float)y, g.inv_th), 0.5f)); };
+    auto ty1_of = [&](int y) { return floor_f32_to_int(tile_coord<false>(y, g.inv_th)); };
     int ya_lo = y_lo, ya_hi = y_hi;
     while (ya_lo < ya_hi && ty1_of(ya_lo) != ty1u) ++ya_lo;
     while (ya_hi > ya_lo && ty1_of(ya_hi - 1) != ty1u) --ya_hi;
     auto do_row = [&](int y, const u32x4& yq, const u32x4& uv) {
-        const float tyf = __fsub_rn(__fmul_rn((float)y, g.inv_th), 0.5f);
+        const float tyf = tile_coord<false>(y, g.inv_th);
         const float ya = __fsub_rn(tyf, (float)ty1u), ya1 = __fsub_rn(1.0f, ya);
         const u32x4 yo = clahe_vec16_f32<false>(quadf, yq, poff, xw, ya, ya1);       // the host takes the fallback for ClaheGeom::contract
         decode_store16<ORDER>(dst + (long long)y * j.out_step, yo, uv);

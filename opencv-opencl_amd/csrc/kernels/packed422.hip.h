@@ -301,7 +301,8 @@ __global__ __launch_bounds__(NT) void tile_hist422_frames_kernel(Packed422List l
 }
 
 // ---------------------------------------------------------------------------------------------
-// K6p  bilinear interpolation of the tile LUTs on the luma (clahe_interp_kernel's grid, bands, pair tables and column segments).
+// K6p  bilinear interpolation of the tile LUTs on the luma (clahe_interp_kernel's grid, bands, pair tables and column segments:
+// interp_stage in clahe.hip.h).
 // A lane owns 16 columns = 8 dwords of a row: two 16-byte loads, the 16 luma bytes gathered into four dwords (v_perm_b32), blended by the
 // planar kernel's own clahe_vec16 / clahe_vec16_f32, and scattered back between the chroma bytes (v_perm_b32 again), two 16-byte stores.
 // Rows are only dword aligned, so these are unaligned-capable vector accesses, like the planar kernel's stores.
@@ -327,45 +328,14 @@ __device__ __forceinline__ void clahe_interp422_body(const Packed422& p, const F
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t quad[];   // [(tiles_x + 1)][256] u32 quads, or f32x4 when FT
     f32x4* quadf = reinterpret_cast<f32x4*>(quad);
-    const int t = threadIdx.x, f = (int)gridDim.y - 1 - (int)blockIdx.y;      // frames last-to-first (Infinity Cache)
-    const int band = blockIdx.x / subs, sub = blockIdx.x - band * subs;
-    const int ty1u = band - 1;                                // unclamped ty1 of every row of the band
-    const int ty1 = max(ty1u, 0), ty2 = min(ty1u + 1, g.tiles_y - 1);
-    const uint8_t* lf = luts + (size_t)f * g.tiles_x * g.tiles_y * 256;
-    const uint8_t* l1 = lf + (size_t)ty1 * g.tiles_x * 256;
-    const uint8_t* l2 = lf + (size_t)ty2 * g.tiles_x * 256;
-    int p0 = 0, npairs = g.tiles_x + 1;
-    if (npairs > pair_cap) {                                  // the pairs of this column segment only
-        const int xs = (int)blockIdx.z * groups * kInterpPx;
-        const int xe = min(g.width, xs + groups * kInterpPx) - 1;
-        auto pair_of = [&](int x) { const int q = floor_f32_to_int(tile_coord<FMA>(x, g.inv_tw)) + 1; return q < 0 ? 0 : (q > g.tiles_x ? g.tiles_x : q); };
-        p0 = pair_of(xs);
-        npairs = min(pair_of(max(xe, xs)) - p0 + 1, pair_cap);
-    }
-    for (int i = t; i < npairs * 256; i += kThreads) {
-        const int pr = p0 + (i >> 8), v = i & 255;
-        const int ta = max(pr - 1, 0), tb = min(pr, g.tiles_x - 1);
-        if (FT) {
-            const f32x4 e = {(float)l1[ta * 256 + v], (float)l2[ta * 256 + v], (float)l1[tb * 256 + v], (float)l2[tb * 256 + v]};   // {a, c, b, d}
-            quadf[i] = e;
-        } else {
-            quad[i] = (uint32_t)l1[ta * 256 + v] | ((uint32_t)l1[tb * 256 + v] << 8) |
-                      ((uint32_t)l2[ta * 256 + v] << 16) | ((uint32_t)l2[tb * 256 + v] << 24);
-        }
-    }
-    __syncthreads();
-
-    // rows of this band, exactly as clahe_interp_body decides them
-    const int y_lo_band = (int)max(0LL, ((long long)(2 * band - 1) * g.tile_h) / 2 - kBandMargin);
-    const int y_hi_band = (int)min((long long)g.height, ((long long)(2 * band + 1) * g.tile_h + 1) / 2 + kBandMargin);
-    const int nrows = max(0, y_hi_band - y_lo_band);
-    const int y_lo = y_lo_band + (int)((long long)nrows * sub / subs);
-    const int y_hi = y_lo_band + (int)((long long)nrows * (sub + 1) / subs);
+    const InterpStage st = interp_stage<FT, FMA>(quad, g, luts, subs, groups, pair_cap);
+    const int t = threadIdx.x, f = st.f, ty1u = st.ty1u, p0 = st.p0, npairs = st.npairs, y_lo = st.y_lo, y_hi = st.y_hi;
 
     const int phases = kThreads / groups;
     const int grp = t % groups, phase = t / groups;
     const int x0 = (blockIdx.z * groups + grp) * kInterpPx;
     if (!(phase < phases && x0 < g.width)) return;
+    // column weights, row trim and first row: duplicated in the five bodies, see interp_stage (clahe.hip.h)
     float xa[kInterpPx], xa1[kInterpPx];
     f32x2 xw[kInterpPx];                                       // {xa1, xa} pairs for the packed float-table body
     int poff[kInterpPx];

@@ -169,8 +169,6 @@ __global__ __launch_bounds__(kThreads) void lut_apply422_nv12_frames_kernel(Pack
 // lanes): the lane that owns the EVEN row y of a pair also loads the chroma of row y + 1 (the same 32 bytes its neighbour in phase, or
 // the next band's workgroup, reads for the luma: a cache hit at worst an L2 one) and writes UV row y / 2 in the same launch.  Every row
 // belongs to exactly one band, so every UV row is written exactly once.  With MI_UV_FILL128 there is no second read.
-// The table staging, the band / sub-band row ranges and the column weights below are a COPY of clahe_interp422_body's (no existing
-// kernel is edited for this form, and its ISA stays what it was): a change to either must be made in both.
 // ---------------------------------------------------------------------------------------------
 template <bool FT, bool FMA, int OFF, class Frames>
 __device__ __forceinline__ void clahe_interp422_nv12_body(const Packed422Nv12& p, const Frames& fr, const ClaheGeom g,
@@ -178,45 +176,14 @@ __device__ __forceinline__ void clahe_interp422_nv12_body(const Packed422Nv12& p
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t quad[];   // [(tiles_x + 1)][256] u32 quads, or f32x4 when FT
     f32x4* quadf = reinterpret_cast<f32x4*>(quad);
-    const int t = threadIdx.x, f = (int)gridDim.y - 1 - (int)blockIdx.y;      // frames last-to-first (Infinity Cache)
-    const int band = blockIdx.x / subs, sub = blockIdx.x - band * subs;
-    const int ty1u = band - 1;                                // unclamped ty1 of every row of the band
-    const int ty1 = max(ty1u, 0), ty2 = min(ty1u + 1, g.tiles_y - 1);
-    const uint8_t* lf = luts + (size_t)f * g.tiles_x * g.tiles_y * 256;
-    const uint8_t* l1 = lf + (size_t)ty1 * g.tiles_x * 256;
-    const uint8_t* l2 = lf + (size_t)ty2 * g.tiles_x * 256;
-    int p0 = 0, npairs = g.tiles_x + 1;
-    if (npairs > pair_cap) {                                  // the pairs of this column segment only
-        const int xs = (int)blockIdx.z * groups * kInterpPx;
-        const int xe = min(g.width, xs + groups * kInterpPx) - 1;
-        auto pair_of = [&](int x) { const int q = floor_f32_to_int(tile_coord<FMA>(x, g.inv_tw)) + 1; return q < 0 ? 0 : (q > g.tiles_x ? g.tiles_x : q); };
-        p0 = pair_of(xs);
-        npairs = min(pair_of(max(xe, xs)) - p0 + 1, pair_cap);
-    }
-    for (int i = t; i < npairs * 256; i += kThreads) {
-        const int pr = p0 + (i >> 8), v = i & 255;
-        const int ta = max(pr - 1, 0), tb = min(pr, g.tiles_x - 1);
-        if (FT) {
-            const f32x4 e = {(float)l1[ta * 256 + v], (float)l2[ta * 256 + v], (float)l1[tb * 256 + v], (float)l2[tb * 256 + v]};   // {a, c, b, d}
-            quadf[i] = e;
-        } else {
-            quad[i] = (uint32_t)l1[ta * 256 + v] | ((uint32_t)l1[tb * 256 + v] << 8) |
-                      ((uint32_t)l2[ta * 256 + v] << 16) | ((uint32_t)l2[tb * 256 + v] << 24);
-        }
-    }
-    __syncthreads();
-
-    // rows of this band, exactly as clahe_interp_body decides them
-    const int y_lo_band = (int)max(0LL, ((long long)(2 * band - 1) * g.tile_h) / 2 - kBandMargin);
-    const int y_hi_band = (int)min((long long)g.height, ((long long)(2 * band + 1) * g.tile_h + 1) / 2 + kBandMargin);
-    const int nrows = max(0, y_hi_band - y_lo_band);
-    const int y_lo = y_lo_band + (int)((long long)nrows * sub / subs);
-    const int y_hi = y_lo_band + (int)((long long)nrows * (sub + 1) / subs);
+    const InterpStage st = interp_stage<FT, FMA>(quad, g, luts, subs, groups, pair_cap);
+    const int t = threadIdx.x, f = st.f, ty1u = st.ty1u, p0 = st.p0, npairs = st.npairs, y_lo = st.y_lo, y_hi = st.y_hi;
 
     const int phases = kThreads / groups;
     const int grp = t % groups, phase = t / groups;
     const int x0 = (blockIdx.z * groups + grp) * kInterpPx;
     if (!(phase < phases && x0 < g.width)) return;
+    // column weights, row trim and first row: duplicated in the five bodies, see interp_stage (clahe.hip.h)
     float xa[kInterpPx], xa1[kInterpPx];
     f32x2 xw[kInterpPx];                                       // {xa1, xa} pairs for the packed float-table body
     int poff[kInterpPx];
