@@ -488,6 +488,43 @@ mi_status mi_equalize_hist_nv12_to_bgr(mi_ctx* ctx, const uint8_t* nv12_in, uint
         int width, int height, int order);
 mi_status mi_clahe_nv12_to_bgr(mi_ctx* ctx, const uint8_t* nv12_in, uint8_t* out, size_t out_step,
         int width, int height, int order, double clip_limit, int tiles_x, int tiles_y);
+/* mi_*_nv12_to_bgr_frames_dev: the same conversion on a LIST of device frames, each at its own three addresses -- a hardware decoder's
+ * surface pool in (every NV12 surface its own allocation with a pitched Y and a pitched UV plane, as for mi_*_nv12_frames_dev), a pool of
+ * images out.  Repacking such a pool into a batch costs 3 bytes per pixel moved on top of the 5.5 of the conversion; one batch call per
+ * surface costs a launch sequence per frame.  `frames` is a host array of n_frames entries, read only during the call; the pointers in
+ * it are device pointers on the context's device.
+ * Shape: all frames of one call share width, height, order and the three pitches (bytes between rows); each has its own addresses:
+ *   y  : H rows of W bytes at y_pitch >= W            uv : H/2 rows of W bytes (interleaved U and V) at uv_pitch >= W
+ *   out: H rows of 3*W bytes at out_pitch >= 3*W -- B, G, R per pixel (MI_ORDER_BGR) or R, G, B (MI_ORDER_RGB)
+ * Bytes: per frame exactly what mi_*_nv12_to_bgr_batch_dev writes for the same pixels at the same pitches -- cv::equalizeHist /
+ * CLAHE::apply on Y, then cvtColor(COLOR_YUV2BGR_NV12 / COLOR_YUV2RGB_NV12); the clahe_fp_contract option is honoured, REFLECT_101
+ * padding applies when the tile grid does not divide the frame, the limits on sizes and tile grids are the batch form's, with the
+ * same statuses.
+ * Writes: only the 3*W bytes of each output row are written, not the pitch padding; the input planes are never written.
+ * Alignment: none is required of any address or pitch.  The per-frame alignment decides the access width: when W % 16 == 0 and the
+ * three pitches are multiples of 16, a frame whose three addresses are multiples of 16 moves 16 bytes per access and any other frame
+ * of the same call moves bytes, while its neighbours stay vectorised -- slower, the same bytes out.  equalizeHist always maps the luma
+ * and converts in one kernel.  CLAHE does so when the shape is the batch form's one-pass shape (the tile grid divides the frame, tile
+ * width a multiple of 16, tiles_x <= 14, the three pitches multiples of 16, clahe_fp_contract off) and every address of every frame of
+ * the call is a multiple of 16; otherwise the whole call runs the planar CLAHE into scratch Y planes of the context and converts from
+ * there: the same bytes in one more pass.  Statistics "nv12_bgr_onepass" / "nv12_bgr_twopass" count the calls of the list form too,
+ * one count a call.  Launches are charged to the same profiling slots as the batch form, per chunk of 64 frames of the list.
+ * Overlap: there is no in-place form.  MI_ERR_BAD_ARG when the rows of a frame's image meet the rows of its own Y or UV plane
+ * (compared as address ranges).  The same input planes may appear in several entries (inputs are only read).  Outputs that overlap
+ * each other or ANOTHER frame's planes give undefined results and are not checked.
+ * Errors, MI_ERR_BAD_ARG: a null ctx, a null `frames` with n_frames > 0, a null y / uv / out in any entry, a negative size, an odd
+ * width or an odd height (refused even when another size is 0, as in the batch form), a pitch below its row (y_pitch < W,
+ * uv_pitch < W, out_pitch < 3*W), an `order` other than the two, tiles <= 0, the overlap above.  Sizes and tile grids the batch form
+ * refuses: the status it gives (MI_ERR_UNSUPPORTED).  width, height or n_frames of 0: MI_OK, nothing written.
+ * Nothing is enqueued unless every frame passes the checks: a bad last entry leaves the first frames' outputs untouched.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of
+ * the same shape as the other device list forms; a captured graph holds the addresses it was captured with. */
+typedef struct mi_nv12_bgr_frame_dev { const void* y; const void* uv; void* out; } mi_nv12_bgr_frame_dev;
+mi_status mi_equalize_hist_nv12_to_bgr_frames_dev(mi_ctx* ctx, const mi_nv12_bgr_frame_dev* frames, int n_frames,
+        int width, int height, size_t y_pitch, size_t uv_pitch, size_t out_pitch, int order, void* stream);
+mi_status mi_clahe_nv12_to_bgr_frames_dev(mi_ctx* ctx, const mi_nv12_bgr_frame_dev* frames, int n_frames,
+        int width, int height, size_t y_pitch, size_t uv_pitch, size_t out_pitch, int order,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
 
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at

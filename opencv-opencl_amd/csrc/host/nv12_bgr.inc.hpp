@@ -70,8 +70,11 @@ Nv12BgrJob nv12_bgr_job(const Nv12BgrArgs& a, int f0, const uint8_t* y, size_t y
     return j;
 }
 
-// LUT apply + decode (luts != nullptr, MI_K_LUT_APPLY) or the decode alone (MI_K_COLOR)
-mi_status launch_nv12_to_bgr(mi_ctx* c, hipStream_t s, const Nv12BgrJob& j, int nf, int order, const uint8_t* luts)
+// LUT apply + decode (luts != nullptr, MI_K_LUT_APPLY) or the decode alone (MI_K_COLOR).  `fl`: a chunk of a frame list (at most
+// kFramesPerLaunch frames, nv12_bgr_frames.inc.hpp): the same grid on the *_frames_kernel entry; `j` then carries the shape, and
+// j.vec what the shape allows.
+mi_status launch_nv12_to_bgr(mi_ctx* c, hipStream_t s, const Nv12BgrJob& j, int nf, int order, const uint8_t* luts,
+                             const Nv12BgrList* fl = nullptr)
 {
     const long long px = (long long)j.width * j.height;
     // bytes per workgroup as the other apply kernels count them (half of what is read and written: 1.5 + 3 B/px); in 16 x 2 groups a
@@ -80,7 +83,13 @@ mi_status launch_nv12_to_bgr(mi_ctx* c, hipStream_t s, const Nv12BgrJob& j, int 
     const long long items = j.vec ? px / 32 : px / 4;
     B = (int)std::max<long long>(1, std::min<long long>(B, (items + kThreads - 1) / kThreads));
     const dim3 grid(B, nf), block(kThreads);
-    if (luts) {
+    if (fl && luts) {
+        if (order == MI_ORDER_RGB) LAUNCH(c, s, MI_K_LUT_APPLY, (nv12_to_bgr_frames_kernel<1, true>), grid, block, 0, *fl, j, luts);
+        else                       LAUNCH(c, s, MI_K_LUT_APPLY, (nv12_to_bgr_frames_kernel<0, true>), grid, block, 0, *fl, j, luts);
+    } else if (fl) {
+        if (order == MI_ORDER_RGB) LAUNCH(c, s, MI_K_COLOR, (nv12_to_bgr_frames_kernel<1, false>), grid, block, 0, *fl, j, luts);
+        else                       LAUNCH(c, s, MI_K_COLOR, (nv12_to_bgr_frames_kernel<0, false>), grid, block, 0, *fl, j, luts);
+    } else if (luts) {
         if (order == MI_ORDER_RGB) LAUNCH(c, s, MI_K_LUT_APPLY, (nv12_to_bgr_kernel<1, true>), grid, block, 0, j, luts);
         else                       LAUNCH(c, s, MI_K_LUT_APPLY, (nv12_to_bgr_kernel<0, true>), grid, block, 0, j, luts);
     } else {
@@ -108,17 +117,48 @@ mi_status equalize_nv12_bgr_dev(mi_ctx* c, hipStream_t s, const Nv12BgrArgs& a)
     return MI_OK;
 }
 
+// The shapes nv12_bgr_clahe_interp_kernel is taken for: no REFLECT_101 padding, 16-pixel groups that never straddle a tile, f32 pair
+// tables that hold the whole grid, separately rounded arithmetic.  The caller adds the alignment: 16-byte aligned rows.
+bool nv12_bgr_onepass_shape(const ClaheGeom& g, int width, int height, int tiles_x, int tiles_y)
+{
+    return !g.contract && width % tiles_x == 0 && height % tiles_y == 0 && g.tile_w % 16 == 0 && tiles_x + 1 <= kMaxPairsLdsF32 &&
+           tiles_x * tiles_y <= kMaxGridY && width / kInterpPx <= kThreads * kMaxGridY;
+}
+
+// CLAHE blend + decode of nf frames whose tile LUTs are in `luts`: launch_interp's bands, sub-bands and column segments.  `fl`: as
+// for launch_nv12_to_bgr.
+mi_status launch_nv12_bgr_interp(mi_ctx* c, hipStream_t s, const Nv12BgrJob& j, const ClaheGeom& g, int nf, int order, const uint8_t* luts,
+                                 const Nv12BgrList* fl = nullptr)
+{
+    const int ngroups = j.width / kInterpPx;
+    const int groups = std::min(ngroups, kThreads);
+    const int segs = (ngroups + groups - 1) / groups;
+    const int bands = g.tiles_y + 1;
+    const long long want = ((long long)c->cu_count * 8 + (long long)bands * nf * segs - 1) / ((long long)bands * nf * segs);
+    const int subs = (int)std::max<long long>(1, std::min<long long>({want, (long long)std::max(1, (g.tile_h + 2 * kBandMargin) / 8), 64LL}));
+    const dim3 grid(bands * subs, nf, segs);
+    const size_t lds = (size_t)(g.tiles_x + 1) * 256 * 4 * sizeof(float);
+    if (fl) {
+        if (order == MI_ORDER_RGB)
+            LAUNCH(c, s, MI_K_CLAHE_INTERP, nv12_bgr_clahe_interp_frames_kernel<1>, grid, dim3(kThreads), lds, *fl, j, g, luts, subs, groups);
+        else
+            LAUNCH(c, s, MI_K_CLAHE_INTERP, nv12_bgr_clahe_interp_frames_kernel<0>, grid, dim3(kThreads), lds, *fl, j, g, luts, subs, groups);
+        return MI_OK;
+    }
+    if (order == MI_ORDER_RGB)
+        LAUNCH(c, s, MI_K_CLAHE_INTERP, nv12_bgr_clahe_interp_kernel<1>, grid, dim3(kThreads), lds, j, g, luts, subs, groups);
+    else
+        LAUNCH(c, s, MI_K_CLAHE_INTERP, nv12_bgr_clahe_interp_kernel<0>, grid, dim3(kThreads), lds, j, g, luts, subs, groups);
+    return MI_OK;
+}
+
 mi_status clahe_nv12_bgr_dev(mi_ctx* c, hipStream_t s, const Nv12BgrArgs& a, double clip_limit, int tiles_x, int tiles_y)
 {
     ClaheGeom g;
     mi_status st = clahe_geometry(c, a.width, a.height, clip_limit, tiles_x, tiles_y, &g);
     if (st) return st;
     const int tiles = tiles_x * tiles_y;
-    // the conditions bgr_clahe_interp_kernel is taken under: no REFLECT_101 padding, 16-pixel groups that never straddle a tile,
-    // 16-byte aligned rows, f32 pair tables that hold the whole grid, separately rounded arithmetic
-    const bool onepass = !g.contract && a.width % tiles_x == 0 && a.height % tiles_y == 0 && g.tile_w % 16 == 0 &&
-                         tiles_x + 1 <= kMaxPairsLdsF32 && tiles <= kMaxGridY && a.width / kInterpPx <= kThreads * kMaxGridY &&
-                         nv12_bgr_aligned16(a);
+    const bool onepass = nv12_bgr_onepass_shape(g, a.width, a.height, tiles_x, tiles_y) && nv12_bgr_aligned16(a);
     const PlaneArgs ya = nv12_bgr_y_plane(a);
     if (onepass) {
         for (int f0 = 0; f0 < a.n_frames; f0 += kNv12BgrFramesPerLaunch) {
@@ -126,19 +166,7 @@ mi_status clahe_nv12_bgr_dev(mi_ctx* c, hipStream_t s, const Nv12BgrArgs& a, dou
             if ((st = grow_dev(c, &c->d_luts, &c->luts_bytes, (size_t)nf * tiles * 256))) return st;
             if ((st = launch_tile_luts(c, s, ya, g, f0, nf, c->d_luts))) return st;
             const Nv12BgrJob j = nv12_bgr_job(a, f0, a.y + (size_t)f0 * a.in_frame, a.y_pitch, a.in_frame);
-            // launch_interp's bands, sub-bands and column segments
-            const int ngroups = a.width / kInterpPx;
-            const int groups = std::min(ngroups, kThreads);
-            const int segs = (ngroups + groups - 1) / groups;
-            const int bands = tiles_y + 1;
-            const long long want = ((long long)c->cu_count * 8 + (long long)bands * nf * segs - 1) / ((long long)bands * nf * segs);
-            const int subs = (int)std::max<long long>(1, std::min<long long>({want, (long long)std::max(1, (g.tile_h + 2 * kBandMargin) / 8), 64LL}));
-            const dim3 grid(bands * subs, nf, segs);
-            const size_t lds = (size_t)(tiles_x + 1) * 256 * 4 * sizeof(float);
-            if (a.order == MI_ORDER_RGB)
-                LAUNCH(c, s, MI_K_CLAHE_INTERP, nv12_bgr_clahe_interp_kernel<1>, grid, dim3(kThreads), lds, j, g, (const uint8_t*)c->d_luts, subs, groups);
-            else
-                LAUNCH(c, s, MI_K_CLAHE_INTERP, nv12_bgr_clahe_interp_kernel<0>, grid, dim3(kThreads), lds, j, g, (const uint8_t*)c->d_luts, subs, groups);
+            if ((st = launch_nv12_bgr_interp(c, s, j, g, nf, a.order, c->d_luts))) return st;
         }
         ++c->nv12_bgr_onepass;
         return MI_OK;

@@ -24,6 +24,37 @@ struct Nv12BgrJob {
     int vec;                                  // 1: W % 16 == 0 and every base / pitch / frame stride a multiple of 16 -> 16 x 2 pixel groups
 };
 
+// Where frame f of a launch lives, as StridedFrames / TableFrames (common.hip.h) say it for the planar kernels: the bodies below are
+// templates on one of these two policies.  The batch entries wrap them with the strided one -- the arithmetic they always had, on the
+// kernel's own argument -- the *_frames_kernel entries with the table.
+struct StridedNv12Bgr {
+    const Nv12BgrJob& j;
+    __device__ __forceinline__ const uint8_t* y_of(long long f) const { return j.y + f * j.y_frame; }
+    __device__ __forceinline__ const uint8_t* uv_of(long long f) const { return j.uv + f * j.uv_frame; }
+    __device__ __forceinline__ uint8_t* out_of(long long f) const { return j.out + f * j.out_frame; }
+    __device__ __forceinline__ bool vec(long long) const { return j.vec; }              // decided by the host for the whole launch
+};
+
+// A list of such frames, each at its own three addresses (mi_*_nv12_to_bgr_frames_dev: a decoder's surface pool in, an image pool
+// out).  The {y, uv, out} entries travel BY VALUE in the kernel arguments like FrameList -- 64 x 24 B = 1.5 KiB -- and are read with
+// scalar kernarg loads indexed by the frame's grid coordinate.  The shape (pitches, width, height) is the launch's Nv12BgrJob, whose
+// y / uv / out / *_frame a table launch ignores and whose vec says what the SHAPE allows (W % 16 == 0, the three pitches multiples of
+// 16): whether frame f takes the 16 x 2 groups is then decided by its own three addresses -- per frame, so uniform for a workgroup.
+struct Nv12BgrFrame { const uint8_t* y; const uint8_t* uv; uint8_t* out; };
+struct Nv12BgrList { Nv12BgrFrame f[kFramesPerLaunch]; };
+static_assert(sizeof(Nv12BgrFrame) == 24, "three addresses an entry");
+struct TableNv12Bgr {
+    const Nv12BgrList& l;
+    const Nv12BgrJob& j;
+    __device__ __forceinline__ const uint8_t* y_of(long long f) const { return l.f[f].y; }
+    __device__ __forceinline__ const uint8_t* uv_of(long long f) const { return l.f[f].uv; }
+    __device__ __forceinline__ uint8_t* out_of(long long f) const { return l.f[f].out; }
+    __device__ __forceinline__ bool vec(long long f) const
+    {
+        return j.vec && (((uintptr_t)l.f[f].y | (uintptr_t)l.f[f].uv | (uintptr_t)l.f[f].out) & 15) == 0;
+    }
+};
+
 template <int ORDER>
 __device__ __forceinline__ void store_px16(uint8_t* p, const uint32_t* b, const uint32_t* g, const uint32_t* r)
 {
@@ -52,8 +83,8 @@ __device__ __forceinline__ void decode_store16(uint8_t* p, const u32x4& y, const
 // vec: a lane owns a 16 x 2 pixel group -- two 16-byte Y loads, one 16-byte UV load, six 16-byte stores (as cvt420_kernel<1>);
 // otherwise a 2 x 2 block with byte accesses.  Only the 3*W bytes of each output row are written.
 // ---------------------------------------------------------------------------------------------
-template <int ORDER, bool LUT>
-__global__ __launch_bounds__(kThreads) void nv12_to_bgr_kernel(Nv12BgrJob j, const uint8_t* __restrict__ luts)
+template <int ORDER, bool LUT, class Frames>
+__device__ __forceinline__ void nv12_to_bgr_body(const Nv12BgrJob& j, const Frames& fr, const uint8_t* __restrict__ luts)
 {
     __shared__ uint32_t lut[LUT ? 256 * kCopies : 1];
     const int t = threadIdx.x;
@@ -67,10 +98,10 @@ __global__ __launch_bounds__(kThreads) void nv12_to_bgr_kernel(Nv12BgrJob j, con
         for (int k = 0; k < kCopies; ++k) lut[(t << kCopyShift) + ((k + t) & (kCopies - 1))] = v;
         __syncthreads();
     }
-    const uint8_t* yp = j.y + (long long)f * j.y_frame;
-    const uint8_t* uvp = j.uv + (long long)f * j.uv_frame;
-    uint8_t* op = j.out + (long long)f * j.out_frame;
-    if (j.vec) {
+    const uint8_t* yp = fr.y_of(f);
+    const uint8_t* uvp = fr.uv_of(f);
+    uint8_t* op = fr.out_of(f);
+    if (fr.vec(f)) {
         const int gx_n = j.width >> 4;
         const int groups = gx_n * (j.height >> 1);            // < 2^26 (W*H < 2^31)
         const int stride = (int)gridDim.x * kThreads, dby = stride / gx_n, dgx = stride - dby * gx_n;
@@ -112,6 +143,17 @@ __global__ __launch_bounds__(kThreads) void nv12_to_bgr_kernel(Nv12BgrJob j, con
         bt601_px_bgr(Y10, ruv, guv, buv, b, g, r); d1[B] = (uint8_t)b; d1[1] = (uint8_t)g; d1[R] = (uint8_t)r;
         bt601_px_bgr(Y11, ruv, guv, buv, b, g, r); d1[3 + B] = (uint8_t)b; d1[4] = (uint8_t)g; d1[3 + R] = (uint8_t)r;
     }
+}
+template <int ORDER, bool LUT>
+__global__ __launch_bounds__(kThreads) void nv12_to_bgr_kernel(Nv12BgrJob j, const uint8_t* __restrict__ luts)
+{
+    nv12_to_bgr_body<ORDER, LUT>(j, StridedNv12Bgr{j}, luts);
+}
+// the same on a frame list: both loops are grid-stride, so one grid (sized by the shape alone) serves frames of either kind
+template <int ORDER, bool LUT>
+__global__ __launch_bounds__(kThreads) void nv12_to_bgr_frames_kernel(Nv12BgrList l, Nv12BgrJob j, const uint8_t* __restrict__ luts)
+{
+    nv12_to_bgr_body<ORDER, LUT>(j, TableNv12Bgr{l, j}, luts);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -183,5 +225,77 @@ __global__ __launch_bounds__(kThreads) void nv12_bgr_clahe_interp_kernel(Nv12Bgr
         do_row(y, q, uv);
     }
 }
+// The same kernel on a frame list, and a COPY of it: a body shared through the frame policy, as nv12_to_bgr_body is, was tried and
+// changed the table fill loop of the kernel above the way calling interp_stage had (other address arithmetic in the loop's preheader,
+// whether the whole body or only the rows behind the barrier went through the shared function), so that kernel keeps its
+// text and this one repeats it with frame f's addresses read from the table: a change there is made here too.  No byte path: the host
+// takes this kernel only when every address of every frame of the call is a multiple of 16.
+template <int ORDER>
+__global__ __launch_bounds__(kThreads) void nv12_bgr_clahe_interp_frames_kernel(Nv12BgrList l, Nv12BgrJob j, ClaheGeom g, const uint8_t* __restrict__ luts,
+                                                                               int subs, int groups)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t quad[];
+    f32x4* quadf = reinterpret_cast<f32x4*>(quad);
+    const int t = threadIdx.x, f = (int)gridDim.y - 1 - (int)blockIdx.y;      // last-to-first, see clahe_interp_kernel
+    const int band = blockIdx.x / subs, sub = blockIdx.x - band * subs;
+    const int ty1u = band - 1;
+    const int ty1 = max(ty1u, 0), ty2 = min(ty1u + 1, g.tiles_y - 1);
+    const uint8_t* lf = luts + (size_t)f * g.tiles_x * g.tiles_y * 256;
+    const uint8_t* l1 = lf + (size_t)ty1 * g.tiles_x * 256;
+    const uint8_t* l2 = lf + (size_t)ty2 * g.tiles_x * 256;
+    const int npairs = g.tiles_x + 1;
+    for (int i = t; i < npairs * 256; i += kThreads) {
+        const int pr = i >> 8, v = i & 255;
+        const int ta = max(pr - 1, 0), tb = min(pr, g.tiles_x - 1);
+        const f32x4 e = {(float)l1[ta * 256 + v], (float)l2[ta * 256 + v], (float)l1[tb * 256 + v], (float)l2[tb * 256 + v]};   // {a, c, b, d}
+        quadf[i] = e;
+    }
+    __syncthreads();
+    const int y_lo_band = (int)max(0LL, ((long long)(2 * band - 1) * g.tile_h) / 2 - kBandMargin);
+    const int y_hi_band = (int)min((long long)g.height, ((long long)(2 * band + 1) * g.tile_h + 1) / 2 + kBandMargin);
+    const int nrows = max(0, y_hi_band - y_lo_band);
+    const int y_lo = y_lo_band + (int)((long long)nrows * sub / subs);
+    const int y_hi = y_lo_band + (int)((long long)nrows * (sub + 1) / subs);
+    const int phases = kThreads / groups;
+    const int grp = t % groups, phase = t / groups;
+    const int x0 = (blockIdx.z * groups + grp) * kInterpPx;
+    if (phase >= phases || x0 >= g.width) return;
+    f32x2 xw[kInterpPx];
+    int poff[kInterpPx];
+#pragma unroll
+    for (int k = 0; k < kInterpPx; ++k) {
+        const float txf = tile_coord<false>(x0 + k, g.inv_tw);
+        const int tx1 = floor_f32_to_int(txf);
+        const float xa = __fsub_rn(txf, (float)tx1);
+        xw[k].x = __fsub_rn(1.0f, xa); xw[k].y = xa;
+        int pr = tx1 + 1;
+        pr = pr < 0 ? 0 : (pr > g.tiles_x ? g.tiles_x : pr);
+        poff[k] = pr << 8;
+    }
+    const TableNv12Bgr fr{l, j};
+    const uint8_t* yp = fr.y_of(f) + x0;
+    const uint8_t* uvp = fr.uv_of(f) + x0;
+    uint8_t* dst = fr.out_of(f) + (long long)x0 * 3;
+    auto ty1_of = [&](int y) { return floor_f32_to_int(tile_coord<false>(y, g.inv_th)); };
+    int ya_lo = y_lo, ya_hi = y_hi;
+    while (ya_lo < ya_hi && ty1_of(ya_lo) != ty1u) ++ya_lo;
+    while (ya_hi > ya_lo && ty1_of(ya_hi - 1) != ty1u) --ya_hi;
+    auto do_row = [&](int y, const u32x4& yq, const u32x4& uv) {
+        const float tyf = tile_coord<false>(y, g.inv_th);
+        const float ya = __fsub_rn(tyf, (float)ty1u), ya1 = __fsub_rn(1.0f, ya);
+        const u32x4 yo = clahe_vec16_f32<false>(quadf, yq, poff, xw, ya, ya1);       // the host takes the fallback for ClaheGeom::contract
+        decode_store16<ORDER>(dst + (long long)y * j.out_step, yo, uv);
+    };
+    for (int y = ya_lo + ((phase - (ya_lo - y_lo) % phases) % phases + phases) % phases; y < ya_hi; y += phases) {
+        const u32x4 q = *reinterpret_cast<const u32x4*>(yp + (long long)y * j.y_step);
+        const u32x4 uv = *reinterpret_cast<const u32x4*>(uvp + (long long)(y >> 1) * j.uv_step);
+        do_row(y, q, uv);
+    }
+}
+// nv12_bgr_clahe_interp_frames_kernel(l, j, g, luts, subs, groups) is the longer list of the two; 256: the implicit arguments a code
+// object carries behind the explicit ones
+static_assert(sizeof(Nv12BgrList) + sizeof(Nv12BgrJob) + sizeof(ClaheGeom) + 8 + sizeof(const uint8_t*) + 2 * sizeof(int) + 8 + 256 <= 4096,
+              "the table and the remaining arguments of either *_frames_kernel stay below HIP's 4 KiB of kernel arguments");
+static_assert(sizeof(Nv12BgrList) + sizeof(Nv12BgrJob) + sizeof(const uint8_t*) + 8 + 256 <= 4096, "nv12_to_bgr_frames_kernel's arguments");
 
 }  // namespace mi

@@ -54,6 +54,7 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_packed422_to_nv12_frames_dev", "mi_clahe_packed422_to_nv12_frames_dev",
     "mi_equalize_hist_packed422_to_nv12", "mi_clahe_packed422_to_nv12",
     "mi_equalize_hist_nv12_to_bgr_batch_dev", "mi_clahe_nv12_to_bgr_batch_dev", "mi_equalize_hist_nv12_to_bgr", "mi_clahe_nv12_to_bgr",
+    "mi_equalize_hist_nv12_to_bgr_frames_dev", "mi_clahe_nv12_to_bgr_frames_dev",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -87,6 +88,12 @@ class Packed422Nv12FrameDev(C.Structure):
     """mi_packed422_nv12_frame_dev: one frame of a packed 4:2:2 -> NV12 list, its input and its two output plane addresses (device
     pointers)."""
     _fields_ = [("in_", C.c_void_p), ("y_out", C.c_void_p), ("uv_out", C.c_void_p)]
+
+
+class Nv12BgrFrameDev(C.Structure):
+    """mi_nv12_bgr_frame_dev: one frame of an NV12 -> BGR / RGB list, its two input plane addresses and its image address (device
+    pointers)."""
+    _fields_ = [("y", C.c_void_p), ("uv", C.c_void_p), ("out", C.c_void_p)]
 
 
 class MiError(RuntimeError):
@@ -186,6 +193,8 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_nv12_to_bgr_batch_dev.argtypes = [vp, vp, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_nv12_to_bgr.argtypes = [vp, vp, vp, sz, i, i, i]
     L.mi_clahe_nv12_to_bgr.argtypes = [vp, vp, vp, sz, i, i, i, d, i, i]
+    L.mi_equalize_hist_nv12_to_bgr_frames_dev.argtypes = [vp, C.POINTER(Nv12BgrFrameDev), i, i, i, sz, sz, sz, i, vp]
+    L.mi_clahe_nv12_to_bgr_frames_dev.argtypes = [vp, C.POINTER(Nv12BgrFrameDev), i, i, i, sz, sz, sz, i, d, i, i, vp]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -329,6 +338,24 @@ def _packed422_nv12_list(inputs, y_outputs, uv_outputs, width, in_pitch, y_pitch
     for k in range(len(inputs)):
         arr[k] = Packed422Nv12FrameDev(_dptr(inputs[k]), _dptr(y_outputs[k]), _dptr(uv_outputs[k]))
     return arr, len(inputs), ip, yp, up
+
+
+def _nv12_bgr_list(ys, uvs, outs, width, y_pitch, uv_pitch, out_pitch, what):
+    """ys / uvs / outs: sequences of equal length (torch CUDA tensors or raw device addresses).  Returns the mi_nv12_bgr_frame_dev
+    array, its length and the three pitches (given, else the row stride of the tensors -- H x W planes, H x 3W or H x W x 3 images --
+    else width for the planes and 3 * width for the images)."""
+    ys, uvs, outs = list(ys), list(uvs), list(outs)
+    if not (len(ys) == len(uvs) == len(outs)):
+        raise MiError(1, what, f"{len(ys)} Y planes but {len(uvs)} UV planes and {len(outs)} images")
+    yp = _plane_pitch(ys, y_pitch, int(width), what)
+    up = _plane_pitch(uvs, uv_pitch, int(width), what)
+    # an H x W x 3 image's rows are its first axis: seen as H x 3W for the pitch
+    rows = [o if isinstance(o, int) or o is None or o.dim() != 3 else o[:, :, 0] for o in outs]
+    op = int(out_pitch) if out_pitch is not None else _plane_pitch(rows, None, 3 * int(width), what)
+    arr = (Nv12BgrFrameDev * max(1, len(ys)))()
+    for k in range(len(ys)):
+        arr[k] = Nv12BgrFrameDev(_dptr(ys[k]), _dptr(uvs[k]), _dptr(outs[k]))
+    return arr, len(ys), yp, up, op
 
 
 _live_contexts: "weakref.WeakSet[Context]" = weakref.WeakSet()
@@ -783,6 +810,23 @@ class Context:
         self._chk(self._L.mi_clahe_nv12_to_bgr_batch_dev(self._h, y, yp, uv, up, fi, _dptr(d_out), op, fo, int(width), int(height),
                                                        int(n_frames), int(order), float(clip_limit), int(tiles_x), int(tiles_y), stream),
                   "mi_clahe_nv12_to_bgr_batch_dev")
+
+    def equalize_hist_nv12_to_bgr_frames(self, ys, uvs, outs, width, height, order=ORDER_BGR, y_pitch=None, uv_pitch=None,
+                                         out_pitch=None, stream=0):
+        """mi_equalize_hist_nv12_to_bgr_frames_dev.  ys / uvs: the Y and UV planes, outs: the images, each its own buffer -- lists of
+        torch CUDA tensors or raw device addresses, one entry per frame.  A pitch left at None is the row stride of the 2-D tensors of
+        that list (H x W x 3 images: of their rows), or the tight one (width; 3 * width)."""
+        arr, n, yp, up, op = _nv12_bgr_list(ys, uvs, outs, width, y_pitch, uv_pitch, out_pitch, "equalize_hist_nv12_to_bgr_frames")
+        self._chk(self._L.mi_equalize_hist_nv12_to_bgr_frames_dev(self._h, arr, n, int(width), int(height), yp, up, op, int(order), stream),
+                  "mi_equalize_hist_nv12_to_bgr_frames_dev")
+
+    def clahe_nv12_to_bgr_frames(self, ys, uvs, outs, width, height, order=ORDER_BGR, clip_limit=2.0, tiles_x=8, tiles_y=8,
+                                 y_pitch=None, uv_pitch=None, out_pitch=None, stream=0):
+        """mi_clahe_nv12_to_bgr_frames_dev; arguments as equalize_hist_nv12_to_bgr_frames, plus the CLAHE parameters."""
+        arr, n, yp, up, op = _nv12_bgr_list(ys, uvs, outs, width, y_pitch, uv_pitch, out_pitch, "clahe_nv12_to_bgr_frames")
+        self._chk(self._L.mi_clahe_nv12_to_bgr_frames_dev(self._h, arr, n, int(width), int(height), yp, up, op, int(order),
+                                                        float(clip_limit), int(tiles_x), int(tiles_y), stream),
+                  "mi_clahe_nv12_to_bgr_frames_dev")
 
     def _nv12_bgr_host(self, nv12, width, height, out, name):
         if not isinstance(nv12, np.ndarray) or nv12.dtype != np.uint8 or not nv12.flags.c_contiguous:

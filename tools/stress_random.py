@@ -1,7 +1,8 @@
 """Bounded random differential run, HIP vs oracle, aimed at the code paths a fixed test list visits only at a few points: ROI pitches
 (multiples of 16 and not) with random origins, wide CLAHE grids at sizes where the per-segment float tables apply, large batches of small
 tiles (several tiles per histogram workgroup), 16-bit CLAHE at random value ranges, the 4:2:0 codes at random aligned / unaligned sizes, NV12 in / BGR out
-at random pitched layouts (aligned and not) and tile grids on both sides of its one-pass conditions.
+at random pitched layouts (aligned and not) and tile grids on both sides of its one-pass conditions, as a batch and as a frame list
+(random order, every image at its own offset).
     python tools/stress_random.py [seconds] [seed] [option=value ...]        prints a line every ~15 s, exits non-zero on the first mismatch"""
 import sys, time
 sys.path.insert(0, "opencv-opencl_amd/python"); sys.path.insert(0, ".")
@@ -103,11 +104,25 @@ while time.time() - t0 < budget:
         kw = dict(y_pitch=yp, uv_pitch=up, in_frame=fi, out_pitch=opi, out_frame=fo)
         if op == 0: ctx.equalize_hist_nv12_to_bgr_batch_dev(*a, **kw)
         else: ctx.clahe_nv12_to_bgr_batch_dev(*a, clip, tx, ty, **kw)
-        ctx.synchronize(); out = xfer.to_host(d_out); want = np.full(out.size, 0x5A, np.uint8)
+        ctx.synchronize(); out = xfer.to_host(d_out); want = np.full(out.size, 0x5A, np.uint8); imgs = []
         for f in range(nf):
             bgr = oracle.nv12_to_bgr(oracle.nv12_frame(fr[f], w, h, uv_mode=1, op=op, clip_limit=clip, tiles_x=tx, tiles_y=ty), w, h)
-            want[ooff + f * fo: ooff + f * fo + opi * h].reshape(h, opi)[:, : 3 * w] = (bgr if order == 0 else bgr[:, :, ::-1]).reshape(h, 3 * w)
+            imgs.append((bgr if order == 0 else bgr[:, :, ::-1]).reshape(h, 3 * w))
+            want[ooff + f * fo: ooff + f * fo + opi * h].reshape(h, opi)[:, : 3 * w] = imgs[f]
         if not np.array_equal(out, want): fail("nv12bgr", w, h, nf, op, order, clip, tx, ty, al, yp, up, opi, off, gap, fgap, ooff, ofgap, np.flatnonzero(out != want)[:8])
+        # the list form on the same planes: the frames in a random order, every image at an offset of its own (one in three a random
+        # number of bytes past where the batch would put it: that frame alone takes the byte path; CLAHE then takes the fallback)
+        perm = [int(v) for v in rng.permutation(nf)]; jit = [int(rng.integers(0, 16)) if rng.integers(0, 3) == 0 else 0 for _ in range(nf)]
+        d_out2 = torch.full((ooff + (fo + 16) * nf + 64,), 0x5A, dtype=torch.uint8, device="cuda"); want = np.full(d_out2.numel(), 0x5A, np.uint8)
+        oo = [ooff + f * (fo + 16) + jit[f] for f in range(nf)]
+        la = ([d_in.data_ptr() + off + f * fi for f in perm], [d_in.data_ptr() + off + uv_off + f * fi for f in perm],
+              [d_out2.data_ptr() + oo[f] for f in perm], w, h, order)
+        lkw = dict(y_pitch=yp, uv_pitch=up, out_pitch=opi)
+        if op == 0: ctx.equalize_hist_nv12_to_bgr_frames(*la, **lkw)
+        else: ctx.clahe_nv12_to_bgr_frames(*la, clip, tx, ty, **lkw)
+        ctx.synchronize(); out = xfer.to_host(d_out2)
+        for f in range(nf): want[oo[f]: oo[f] + opi * h].reshape(h, opi)[:, : 3 * w] = imgs[f]
+        if not np.array_equal(out, want): fail("nv12bgr list", w, h, nf, op, order, clip, tx, ty, al, yp, up, opi, off, gap, fgap, ooff, perm, jit, np.flatnonzero(out != want)[:8])
         if not np.array_equal(xfer.to_host(d_in), img): fail("nv12bgr wrote its input", w, h, nf, op)
         n["nv12bgr"] += 1
     else:           # 4:2:0 codes
