@@ -575,10 +575,15 @@ class Context:
                                      int(tiles_x), int(tiles_y)), "mi_clahe_u16")
         return dst
 
-    def clahe16_batch_dev(self, src, dst, width, height, n_frames, clip_limit, tiles_x, tiles_y, stream=0):
-        self._chk(self._L.mi_clahe_u16_batch_dev(self._h, _dptr(src), width * 2, width * 2 * height, _dptr(dst), width * 2,
-                                               width * 2 * height, width, height, n_frames, float(clip_limit), tiles_x, tiles_y, stream),
-                  "mi_clahe_u16_batch_dev")
+    def clahe16_batch_dev(self, src, dst, width, height, n_frames, clip_limit, tiles_x, tiles_y, stream=0, src_step=None,
+                          src_frame=None, dst_step=None, dst_frame=None):
+        """Steps and frame strides in bytes; tight (2*W, step * H) when not given."""
+        ss = width * 2 if src_step is None else src_step
+        ds = width * 2 if dst_step is None else dst_step
+        sf = ss * height if src_frame is None else src_frame
+        df = ds * height if dst_frame is None else dst_frame
+        self._chk(self._L.mi_clahe_u16_batch_dev(self._h, _dptr(src), ss, sf, _dptr(dst), ds, df, width, height, n_frames,
+                                               float(clip_limit), tiles_x, tiles_y, stream), "mi_clahe_u16_batch_dev")
 
     # ---- 16-bit 4:2:0 frames: P010 / P012 / P016 ----
     def clahe_p010(self, frame: np.ndarray, width: int, height: int, uv_mode: int = UV_FILL128, clip_limit: float = 2.0,
@@ -886,15 +891,26 @@ class Context:
                                             int(tiles_x), int(tiles_y)), "mi_bgr_luma_op_u8c3")
         return dst
 
-    def cvt_color_batch_dev(self, src, dst, width, height, n_frames, code, stream=0):
-        self._chk(self._L.mi_cvt_color_u8c3_batch_dev(self._h, _dptr(src), width * 3, width * 3 * height, _dptr(dst), width * 3,
-                                                    width * 3 * height, width, height, n_frames, int(code), stream),
-                  "mi_cvt_color_u8c3_batch_dev")
+    def cvt_color_batch_dev(self, src, dst, width, height, n_frames, code, stream=0, src_step=None, src_frame=None, dst_step=None,
+                            dst_frame=None):
+        """Steps and frame strides in bytes; tight (3*W, step * H) when not given."""
+        ss = width * 3 if src_step is None else src_step
+        ds = width * 3 if dst_step is None else dst_step
+        sf = ss * height if src_frame is None else src_frame
+        df = ds * height if dst_frame is None else dst_frame
+        self._chk(self._L.mi_cvt_color_u8c3_batch_dev(self._h, _dptr(src), ss, sf, _dptr(dst), ds, df, width, height, n_frames,
+                                                    int(code), stream), "mi_cvt_color_u8c3_batch_dev")
 
-    def bgr_luma_op_batch_dev(self, src, dst, width, height, n_frames, op=OP_EQUALIZE, clip_limit=3.0, tiles_x=4, tiles_y=4, stream=0):
-        self._chk(self._L.mi_bgr_luma_op_u8c3_batch_dev(self._h, _dptr(src), width * 3, width * 3 * height, _dptr(dst), width * 3,
-                                                      width * 3 * height, width, height, n_frames, int(op), float(clip_limit),
-                                                      int(tiles_x), int(tiles_y), stream), "mi_bgr_luma_op_u8c3_batch_dev")
+    def bgr_luma_op_batch_dev(self, src, dst, width, height, n_frames, op=OP_EQUALIZE, clip_limit=3.0, tiles_x=4, tiles_y=4, stream=0,
+                              src_step=None, src_frame=None, dst_step=None, dst_frame=None):
+        """Steps and frame strides in bytes; tight (3*W, step * H) when not given."""
+        ss = width * 3 if src_step is None else src_step
+        ds = width * 3 if dst_step is None else dst_step
+        sf = ss * height if src_frame is None else src_frame
+        df = ds * height if dst_frame is None else dst_frame
+        self._chk(self._L.mi_bgr_luma_op_u8c3_batch_dev(self._h, _dptr(src), ss, sf, _dptr(dst), ds, df, width, height, n_frames,
+                                                      int(op), float(clip_limit), int(tiles_x), int(tiles_y), stream),
+                  "mi_bgr_luma_op_u8c3_batch_dev")
 
     def cvt_color_420(self, src: np.ndarray, code: int, dst: np.ndarray | None = None) -> np.ndarray:
         """cv::cvtColor with COLOR_BGR2YUV_I420 (HxWx3 -> (H*3/2)xW) or COLOR_YUV2BGR_NV12 ((H*3/2)xW -> HxWx3)."""
@@ -917,12 +933,17 @@ class Context:
         self._chk(self._L.mi_cvt_color_420_u8(self._h, src.ctypes.data, sstep, dst.ctypes.data, dstep, w, h, int(code)), "mi_cvt_color_420_u8")
         return dst
 
-    def cvt_color_420_batch_dev(self, src, dst, width, height, n_frames, code, stream=0):
-        c3, pl = width * 3, width
+    def cvt_color_420_batch_dev(self, src, dst, width, height, n_frames, code, stream=0, src_step=None, src_frame=None, dst_step=None,
+                                dst_frame=None):
+        """Steps and frame strides in bytes; when not given, tight: the CV_8UC3 side 3*W and step * H, the planar side W and
+        step * H*3/2."""
         enc = code == COLOR_BGR2YUV_I420
-        self._chk(self._L.mi_cvt_color_420_u8_batch_dev(self._h, _dptr(src), c3 if enc else pl, (c3 * height) if enc else pl * height * 3 // 2,
-                                                      _dptr(dst), pl if enc else c3, (pl * height * 3 // 2) if enc else c3 * height,
-                                                      width, height, n_frames, int(code), stream), "mi_cvt_color_420_u8_batch_dev")
+        ss = (width * 3 if enc else width) if src_step is None else src_step
+        ds = (width if enc else width * 3) if dst_step is None else dst_step
+        sf = (ss * height if enc else ss * height * 3 // 2) if src_frame is None else src_frame
+        df = (ds * height * 3 // 2 if enc else ds * height) if dst_frame is None else dst_frame
+        self._chk(self._L.mi_cvt_color_420_u8_batch_dev(self._h, _dptr(src), ss, sf, _dptr(dst), ds, df, width, height, n_frames,
+                                                      int(code), stream), "mi_cvt_color_420_u8_batch_dev")
 
     def nv12_bgr_equalize(self, nv12: np.ndarray, width: int, height: int, out: np.ndarray | None = None) -> np.ndarray:
         """NV12 -> BGR -> equalizeHist on B, G, R -> NV12 (BASELINE.json config 5 read literally)."""
@@ -935,9 +956,12 @@ class Context:
         self._chk(self._L.mi_nv12_bgr_equalize(self._h, nv12.ctypes.data, out.ctypes.data, int(width), int(height)), "mi_nv12_bgr_equalize")
         return out
 
-    def nv12_bgr_equalize_batch_dev(self, src, dst, width, height, n_frames, stream=0, frame_stride=None):
+    def nv12_bgr_equalize_batch_dev(self, src, dst, width, height, n_frames, stream=0, frame_stride=None, in_frame=None, out_frame=None):
+        """Frame strides in bytes: in_frame / out_frame per side, else frame_stride for both, else tight (W*H*3/2)."""
         fs = width * height * 3 // 2 if frame_stride is None else int(frame_stride)
-        self._chk(self._L.mi_nv12_bgr_equalize_batch_dev(self._h, _dptr(src), fs, _dptr(dst), fs, width, height, n_frames, stream),
+        fi = fs if in_frame is None else int(in_frame)
+        fo = fs if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_nv12_bgr_equalize_batch_dev(self._h, _dptr(src), fi, _dptr(dst), fo, width, height, n_frames, stream),
                   "mi_nv12_bgr_equalize_batch_dev")
 
     def synchronize(self, stream=0):
