@@ -526,6 +526,55 @@ mi_status mi_clahe_nv12_to_bgr_frames_dev(mi_ctx* ctx, const mi_nv12_bgr_frame_d
         int width, int height, size_t y_pitch, size_t uv_pitch, size_t out_pitch, int order,
         double clip_limit, int tiles_x, int tiles_y, void* stream);
 
+/* mi_*_bgr_to_nv12*: interleaved 8-bit BGR (or RGB) images in, pitched NV12 frames out with the luma equalized -- renderer, model output
+ * or image reader -> hardware encoder without an I420 intermediate and without an interleave of U and V outside the library.  Per frame
+ * the bytes are what OpenCV 4.4 gives for
+ *     cv::cvtColor(bgr, i420, cv::COLOR_BGR2YUV_I420);                                           (COLOR_RGB2YUV_I420 for MI_ORDER_RGB)
+ *     cv::Mat y = i420(Rect(0, 0, W, H));  cv::equalizeHist(y, y)  /  clahe->apply(y, y);        (Y only)
+ * with the U and the V plane interleaved into an NV12 chroma plane (MI_UV_COPY) or every chroma byte 128 (MI_UV_FILL128).  Chroma comes
+ * from the top-left pixel of each 2 x 2 block, without averaging, as in mi_cvt_color_420_u8 (MI_COLOR_BGR2YUV_I420).  The same
+ * clahe_fp_contract option, the same REFLECT_101 padding when the tile grid does not divide the frame and the same limits on sizes and
+ * tile grids as the planar forms.
+ *   input  : frame f at d_in + f * in_frame_stride, H rows of 3*W bytes at in_pitch >= 3*W: B, G, R per pixel (MI_ORDER_BGR) or R, G, B
+ *            (MI_ORDER_RGB).  The input is never written.
+ *   output : frame f has a Y plane at d_y_out + f * out_frame_stride, H rows of W bytes at y_pitch >= W, and a UV plane at
+ *            d_uv_out + f * out_frame_stride, H/2 rows of W bytes (interleaved U and V) at uv_pitch >= W.  A tight NV12 batch is
+ *            d_uv_out = d_y_out + W*H, both pitches W, out_frame_stride = W*H*3/2; pitched encoder surfaces in one allocation are the
+ *            general case.  Only the W bytes of each output row are written: not the pitch padding, not the gap between the planes,
+ *            not the gaps between frames.
+ * Width and height are even.  No alignment is required of any pointer, pitch or stride: when W % 16 == 0 and all three pointers, all
+ * three pitches and both frame strides are multiples of 16 the conversion moves 16 bytes per access, otherwise bytes -- slower, the
+ * same bytes out.
+ * Two stages per chunk of 256 frames.  Y is not in the input, so stage 1 converts: ONE kernel (charged to MI_K_COLOR) reads the image
+ * once, writes Y and UV into the caller's planes and, for equalizeHist, counts the luma bytes it has just produced.  Stage 2 maps the
+ * luma IN PLACE in the output Y plane with the planar kernels: equalizeHist one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch (no MI_K_HIST
+ * launch; never the fused equalizeHist kernel nor the single-launch histogram + LUT kernel, option two_kernel_max_frames does not
+ * apply); CLAHE exactly what mi_clahe_u8_batch_dev launches for that plane, for every shape it takes -- no one-pass / two-pass split, no
+ * scratch plane.  Bytes moved per pixel: equalizeHist 3 + 1.5 + 1 + 1 = 6.5, CLAHE 4.5 + 3 = 7.5.  Between the stages the output Y plane
+ * holds the unequalized luma.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of the
+ * same shape as the other batched device forms.
+ * mi_equalize_hist_bgr_to_nv12 / mi_clahe_bgr_to_nv12: ONE CV_8UC3 image in host memory at in_step >= 3*W, at any address, in, one tight
+ *   NV12 frame of W*H*3/2 bytes out; synchronous, staged like mi_*_nv12_to_bgr (images in pinned memory that are tight are DMA'd as they
+ *   are, everything else goes through the context's pinned staging).  Whatever the call returns, no copy on in / nv12_out is in flight
+ *   any more when it returns.  W*H beyond what mi_cvt_color_420_u8 accepts: MI_ERR_UNSUPPORTED.
+ * Errors, MI_ERR_BAD_ARG: a null ctx or a null pointer, an odd width or an odd height (refused even when another size is 0, as in the
+ * NV12 -> BGR forms), a negative size, a pitch below its row (in_pitch < 3*W, y_pitch < W, uv_pitch < W), an `order` other than the two,
+ * a bad uv_mode, tiles <= 0, d_y_out == d_in, d_uv_out == d_in or d_y_out == d_uv_out (there is no in-place form).  Any other overlap:
+ * undefined, not checked.  width, height or n_frames of 0: MI_OK, nothing written.  Sizes and tile grids the planar forms refuse: the
+ * status they give (MI_ERR_UNSUPPORTED), nothing written.  Nothing is enqueued unless all checks pass. */
+mi_status mi_equalize_hist_bgr_to_nv12_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        void* d_y_out, size_t y_pitch, void* d_uv_out, size_t uv_pitch, size_t out_frame_stride,
+        int width, int height, int n_frames, int order, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_bgr_to_nv12_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        void* d_y_out, size_t y_pitch, void* d_uv_out, size_t uv_pitch, size_t out_frame_stride,
+        int width, int height, int n_frames, int order, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
+mi_status mi_equalize_hist_bgr_to_nv12(mi_ctx* ctx, const uint8_t* in, size_t in_step, uint8_t* nv12_out,
+        int width, int height, int order, mi_uv_mode uv_mode);
+mi_status mi_clahe_bgr_to_nv12(mi_ctx* ctx, const uint8_t* in, size_t in_step, uint8_t* nv12_out,
+        int width, int height, int order, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
+
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at
  * OpenCVequalHist.cpp:115/:158).  Registering a pool's memory once lets the host-pointer forms DMA straight

@@ -33,6 +33,7 @@
 //   kernels/packed422.hip.h       the pixel-touching stages on packed 4:2:2 frames (YUY2 / UYVY): luma at a 2-byte sample stride
 //   kernels/packed422_nv12.hip.h  the pixel-writing stages of packed 4:2:2 in, NV12 out: Y plane + vertically halved chroma in one pass
 //   kernels/nv12_bgr.hip.h         the pixel-writing stages of NV12 in, interleaved BGR / RGB out: LUT apply + decode, CLAHE blend + decode
+//   kernels/bgr_nv12.hip.h         stage 1 of interleaved BGR / RGB in, NV12 out: convert into pitched planes and count the luma written
 #pragma once
 #include "kernels/common.hip.h"
 #include "kernels/equalize.hip.h"
@@ -46,3 +47,4 @@
 #include "kernels/packed422.hip.h"
 #include "kernels/packed422_nv12.hip.h"
 #include "kernels/nv12_bgr.hip.h"
+#include "kernels/bgr_nv12.hip.h"

@@ -492,6 +492,23 @@ inline void claheNV12ToBGR(const unsigned char* nv12, unsigned char* out, size_t
     detail::check(c, mi_clahe_nv12_to_bgr(c, nv12, out, outStep, width, height, (int)order, clipLimit, tiles.width, tiles.height),
                   "mi_clahe_nv12_to_bgr");
 }
+// The opposite edge: one interleaved CV_8UC3 host image (BGR, or RGB) at inStep >= 3*W in, one tight NV12 frame of W*H*3/2 bytes for an
+// encoder out: cv::cvtColor(COLOR_BGR2YUV_I420) + cv::equalizeHist / CLAHE::apply on the Y plane + the U/V interleave (UV_COPY) or
+// chroma 128 (UV_FILL128) without the I420 frame in between.  Width and height are even.
+inline void equalizeHistBGRToNV12(const unsigned char* in, size_t inStep, unsigned char* nv12Out, int width, int height,
+                                  ChannelOrder order = ORDER_BGR, UVMode uv = UV_COPY)
+{
+    mi_ctx* c = detail::thread_ctx();
+    detail::check(c, mi_equalize_hist_bgr_to_nv12(c, in, inStep, nv12Out, width, height, (int)order, (mi_uv_mode)uv),
+                  "mi_equalize_hist_bgr_to_nv12");
+}
+inline void claheBGRToNV12(const unsigned char* in, size_t inStep, unsigned char* nv12Out, int width, int height, double clipLimit,
+                           Size tiles, ChannelOrder order = ORDER_BGR, UVMode uv = UV_COPY)
+{
+    mi_ctx* c = detail::thread_ctx();
+    detail::check(c, mi_clahe_bgr_to_nv12(c, in, inStep, nv12Out, width, height, (int)order, (mi_uv_mode)uv, clipLimit, tiles.width,
+                                          tiles.height), "mi_clahe_bgr_to_nv12");
+}
 
 // BASELINE.json config 5 read literally: cvtColor(COLOR_YUV2BGR_NV12) -> split -> equalizeHist on B, G and R -> merge ->
 // cvtColor(COLOR_BGR2YUV_I420) + U/V interleave, NV12 in -> NV12 out in one call (no file of the reference does this;

@@ -25,7 +25,7 @@ OP_EQUALIZE, OP_CLAHE, OP_CHANNELS = 0, 1, 2
 PIPE_UV_AUTO, PIPE_UV_HOST, PIPE_UV_DEVICE = 0, 1, 2
 FMT_NV12, FMT_P010 = 0, 1              # MI_FMT_*: P010 = any 16-bit LE 4:2:0 semi-planar frame (P010 / P012 / P016)
 FMT_YUY2, FMT_UYVY = 2, 3              # packed 8-bit 4:2:2: luma at byte 0 (YUY2 / YUYV / YVYU) or byte 1 (UYVY / VYUY) of each 2-byte pixel
-ORDER_BGR, ORDER_RGB = 0, 1            # MI_ORDER_*: channel order of the interleaved output of the NV12 -> BGR forms
+ORDER_BGR, ORDER_RGB = 0, 1            # MI_ORDER_*: channel order of the interleaved side of the NV12 -> BGR and BGR -> NV12 forms
 ERR_BUSY = 6
 
 # every extern "C" symbol include/mi_lumaeq.h declares (tests check the .so exports them all)
@@ -55,6 +55,7 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_packed422_to_nv12", "mi_clahe_packed422_to_nv12",
     "mi_equalize_hist_nv12_to_bgr_batch_dev", "mi_clahe_nv12_to_bgr_batch_dev", "mi_equalize_hist_nv12_to_bgr", "mi_clahe_nv12_to_bgr",
     "mi_equalize_hist_nv12_to_bgr_frames_dev", "mi_clahe_nv12_to_bgr_frames_dev",
+    "mi_equalize_hist_bgr_to_nv12_batch_dev", "mi_clahe_bgr_to_nv12_batch_dev", "mi_equalize_hist_bgr_to_nv12", "mi_clahe_bgr_to_nv12",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -195,6 +196,10 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_nv12_to_bgr.argtypes = [vp, vp, vp, sz, i, i, i, d, i, i]
     L.mi_equalize_hist_nv12_to_bgr_frames_dev.argtypes = [vp, C.POINTER(Nv12BgrFrameDev), i, i, i, sz, sz, sz, i, vp]
     L.mi_clahe_nv12_to_bgr_frames_dev.argtypes = [vp, C.POINTER(Nv12BgrFrameDev), i, i, i, sz, sz, sz, i, d, i, i, vp]
+    L.mi_equalize_hist_bgr_to_nv12_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, vp, sz, sz, i, i, i, i, i, vp]
+    L.mi_clahe_bgr_to_nv12_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, vp, sz, sz, i, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_bgr_to_nv12.argtypes = [vp, vp, sz, vp, i, i, i, i]
+    L.mi_clahe_bgr_to_nv12.argtypes = [vp, vp, sz, vp, i, i, i, i, d, i, i]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -860,6 +865,56 @@ class Context:
         out, step = self._nv12_bgr_host(nv12, int(width), int(height), out, "clahe_nv12_to_bgr")
         self._chk(self._L.mi_clahe_nv12_to_bgr(self._h, nv12.ctypes.data, out.ctypes.data, step, int(width), int(height), int(order),
                                              float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_nv12_to_bgr")
+        return out
+
+    # ---- interleaved BGR / RGB in, NV12 out: convert and count in one pass, then map the luma in place ----
+    def equalize_hist_bgr_to_nv12_batch_dev(self, d_in, d_y_out, d_uv_out, width, height, n_frames, order=ORDER_BGR, uv_mode=UV_COPY,
+                                            in_pitch=None, in_frame=None, y_pitch=None, uv_pitch=None, out_frame=None, stream=0):
+        """mi_equalize_hist_bgr_to_nv12_batch_dev: n_frames interleaved BGR / RGB images in, NV12 frames out (torch tensors or raw
+        addresses).  Tight layouts are the defaults: in_pitch 3*W, in_frame in_pitch * H, y_pitch = uv_pitch = W, out_frame =
+        y_pitch * H + uv_pitch * H/2; d_uv_out None puts the UV plane directly behind the Y plane (one tight NV12 batch in d_y_out)."""
+        ip = 3 * int(width) if in_pitch is None else int(in_pitch)
+        fi = ip * int(height) if in_frame is None else int(in_frame)
+        y, yp, uv, up, fo = self._nv12_out(d_y_out, d_uv_out, width, height, y_pitch, uv_pitch, out_frame)
+        self._chk(self._L.mi_equalize_hist_bgr_to_nv12_batch_dev(self._h, _dptr(d_in), ip, fi, y, yp, uv, up, fo, int(width), int(height),
+                                                               int(n_frames), int(order), int(uv_mode), stream),
+                  "mi_equalize_hist_bgr_to_nv12_batch_dev")
+
+    def clahe_bgr_to_nv12_batch_dev(self, d_in, d_y_out, d_uv_out, width, height, n_frames, order=ORDER_BGR, uv_mode=UV_COPY,
+                                    clip_limit=2.0, tiles_x=8, tiles_y=8, in_pitch=None, in_frame=None, y_pitch=None, uv_pitch=None,
+                                    out_frame=None, stream=0):
+        """mi_clahe_bgr_to_nv12_batch_dev; arguments as equalize_hist_bgr_to_nv12_batch_dev, plus the CLAHE parameters."""
+        ip = 3 * int(width) if in_pitch is None else int(in_pitch)
+        fi = ip * int(height) if in_frame is None else int(in_frame)
+        y, yp, uv, up, fo = self._nv12_out(d_y_out, d_uv_out, width, height, y_pitch, uv_pitch, out_frame)
+        self._chk(self._L.mi_clahe_bgr_to_nv12_batch_dev(self._h, _dptr(d_in), ip, fi, y, yp, uv, up, fo, int(width), int(height),
+                                                       int(n_frames), int(order), int(uv_mode), float(clip_limit), int(tiles_x),
+                                                       int(tiles_y), stream), "mi_clahe_bgr_to_nv12_batch_dev")
+
+    def _bgr_nv12_host(self, img, out, name):
+        img = self._host3(img, name)
+        h, w = img.shape[:2]
+        if out is None:
+            out = np.empty(w * h * 3 // 2, np.uint8)
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous or out.size != w * h * 3 // 2:
+            raise MiError(1, name, "out must be a contiguous uint8 array of width*height*3/2 bytes")
+        return img, h, w, (int(img.strides[0]) if h > 1 else max(int(img.strides[0]), 3 * w)), out
+
+    def equalize_hist_bgr_to_nv12(self, img: np.ndarray, order: int = ORDER_BGR, uv_mode: int = UV_COPY,
+                                  out: np.ndarray | None = None) -> np.ndarray:
+        """mi_equalize_hist_bgr_to_nv12 on a host image: an H x W x 3 uint8 array in (a view with padded rows included), the tight NV12
+        frame of W*H*3/2 bytes out -- `out` when given, else a new array."""
+        img, h, w, step, out = self._bgr_nv12_host(img, out, "equalize_hist_bgr_to_nv12")
+        self._chk(self._L.mi_equalize_hist_bgr_to_nv12(self._h, img.ctypes.data, step, out.ctypes.data, w, h, int(order), int(uv_mode)),
+                  "mi_equalize_hist_bgr_to_nv12")
+        return out
+
+    def clahe_bgr_to_nv12(self, img: np.ndarray, order: int = ORDER_BGR, uv_mode: int = UV_COPY, clip_limit: float = 2.0,
+                          tiles_x: int = 8, tiles_y: int = 8, out: np.ndarray | None = None) -> np.ndarray:
+        """mi_clahe_bgr_to_nv12; arguments as equalize_hist_bgr_to_nv12, plus the CLAHE parameters."""
+        img, h, w, step, out = self._bgr_nv12_host(img, out, "clahe_bgr_to_nv12")
+        self._chk(self._L.mi_clahe_bgr_to_nv12(self._h, img.ctypes.data, step, out.ctypes.data, w, h, int(order), int(uv_mode),
+                                             float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_bgr_to_nv12")
         return out
 
     # ---- colour-domain neighbours (N3) ----
