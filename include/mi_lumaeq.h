@@ -574,6 +574,45 @@ mi_status mi_equalize_hist_bgr_to_nv12(mi_ctx* ctx, const uint8_t* in, size_t in
         int width, int height, int order, mi_uv_mode uv_mode);
 mi_status mi_clahe_bgr_to_nv12(mi_ctx* ctx, const uint8_t* in, size_t in_step, uint8_t* nv12_out,
         int width, int height, int order, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
+/* mi_*_bgr_to_nv12_frames_dev: the same conversion on a LIST of device frames, each at its own three addresses -- a pool of images in
+ * (one tensor or buffer per frame, as renderers, models and image readers hand them over), a hardware encoder's surface pool out (every
+ * NV12 surface its own allocation with a pitched Y and a pitched UV plane, as for mi_*_nv12_frames_dev).  Repacking such pools into a
+ * batch and copying the planes out costs 3 + 1.5 bytes per pixel moved on top of the 6.5 / 7.5 of the conversion; one batch call per
+ * surface costs a launch sequence per frame.  `frames` is a host array of n_frames entries, read only during the call; the pointers in
+ * it are device pointers on the context's device.
+ * Shape: all frames of one call share width, height, order, uv_mode and the three pitches (bytes between rows); each has its own
+ * addresses:
+ *   in : H rows of 3*W bytes at in_pitch >= 3*W -- B, G, R per pixel (MI_ORDER_BGR) or R, G, B (MI_ORDER_RGB)
+ *   y  : H rows of W bytes at y_pitch >= W            uv : H/2 rows of W bytes (interleaved U and V) at uv_pitch >= W
+ * Bytes: per frame exactly what mi_*_bgr_to_nv12_batch_dev writes for the same pixels at the same pitches -- cvtColor(COLOR_BGR2YUV_I420
+ * / COLOR_RGB2YUV_I420) with U and V interleaved (MI_UV_COPY) or every chroma byte 128 (MI_UV_FILL128), then cv::equalizeHist /
+ * CLAHE::apply on Y; the clahe_fp_contract option is honoured, REFLECT_101 padding applies when the tile grid does not divide the
+ * frame, the limits on sizes and tile grids are the batch form's, with the same statuses.
+ * Writes: only the W bytes of each output row are written, not the pitch padding; the images are never written.
+ * Alignment: none is required of any address or pitch.  The per-frame alignment decides the access width of the conversion: when
+ * W % 16 == 0 and the three pitches are multiples of 16, a frame whose three addresses are multiples of 16 moves 16 bytes per access
+ * and any other frame of the same call moves bytes, while its neighbours stay vectorised -- slower, the same bytes out.
+ * Two stages per chunk of 64 frames of the list, as in the batch form: ONE conversion kernel (MI_K_COLOR) reads the chunk's images once,
+ * writes Y and UV and, for equalizeHist, counts the luma it has produced; then the luma is mapped IN PLACE in the Y planes:
+ * equalizeHist one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch (no MI_K_HIST launch; never the fused equalizeHist kernel nor the
+ * single-launch histogram + LUT kernel), CLAHE exactly what mi_clahe_nv12_frames_dev launches in place on the same Y planes.  Launches
+ * are charged to the same profiling slots as the batch form.  Between the stages the Y planes hold the unequalized luma.
+ * Overlap: there is no in-place form.  MI_ERR_BAD_ARG when the rows of a frame's image meet the rows of its own Y or UV plane, or the
+ * rows of its Y plane those of its own UV plane (compared as address ranges).  The same image may appear in several entries (inputs are
+ * only read).  Outputs that overlap each other or ANOTHER frame's planes or image give undefined results and are not checked.
+ * Errors, MI_ERR_BAD_ARG: a null ctx, a null `frames` with n_frames > 0, a null in / y / uv in any entry, a negative size, an odd
+ * width or an odd height (refused even when another size is 0, as in the batch form), a pitch below its row (in_pitch < 3*W,
+ * y_pitch < W, uv_pitch < W), an `order` other than the two, a bad uv_mode, tiles <= 0, the overlap above.  Sizes and tile grids the
+ * batch form refuses: the status it gives (MI_ERR_UNSUPPORTED).  width, height or n_frames of 0: MI_OK, nothing written.
+ * Nothing is enqueued unless every frame passes the checks: a bad last entry leaves the first frames' outputs untouched.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of
+ * the same shape as the other device list forms; a captured graph holds the addresses it was captured with. */
+typedef struct mi_bgr_nv12_frame_dev { const void* in; void* y; void* uv; } mi_bgr_nv12_frame_dev;
+mi_status mi_equalize_hist_bgr_to_nv12_frames_dev(mi_ctx* ctx, const mi_bgr_nv12_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t y_pitch, size_t uv_pitch, int order, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_bgr_to_nv12_frames_dev(mi_ctx* ctx, const mi_bgr_nv12_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t y_pitch, size_t uv_pitch, int order, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
 
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at

@@ -50,7 +50,11 @@ mi_status check_bgr_nv12(mi_ctx* c, const BgrNv12Args& a, bool is_clahe, int til
 }
 
 // Stage 1 on frames f0 .. f0 + nf of the call (MI_K_COLOR).  hist: count the luma into c->d_partial, *nparts_out workgroups a frame.
-mi_status launch_bgr_to_nv12(mi_ctx* c, hipStream_t s, const BgrNv12Args& a, int f0, int nf, bool hist, int* nparts_out)
+// With a frame table (fl: one chunk of at most kFramesPerLaunch frames, bgr_nv12_frames.inc.hpp): the same grid on the
+// *_frames_kernel entry; `a` then carries the shape, its base pointers (stand-ins for the vec rule) and frame strides are not used by
+// the kernel, and j.vec says what the shape allows -- a byte-path frame of such a launch simply takes more grid-stride steps.
+mi_status launch_bgr_to_nv12(mi_ctx* c, hipStream_t s, const BgrNv12Args& a, int f0, int nf, bool hist, int* nparts_out,
+                             const BgrNv12List* fl = nullptr)
 {
     BgrNv12Job j{};
     j.in = a.in + (size_t)f0 * a.in_frame; j.y = a.y + (size_t)f0 * a.out_frame; j.uv = a.uv + (size_t)f0 * a.out_frame;
@@ -72,8 +76,10 @@ mi_status launch_bgr_to_nv12(mi_ctx* c, hipStream_t s, const BgrNv12Args& a, int
     const bool rgb = a.order == MI_ORDER_RGB, cp = a.uv_mode == MI_UV_COPY;
 #define MI_BGR_NV12_LAUNCH(O, U)                                                                                                     \
     do {                                                                                                                             \
-        if (hist) LAUNCH(c, s, MI_K_COLOR, (bgr_to_nv12_hist_kernel<O, U, true>), grid, block, 0, j, c->d_partial);                    \
-        else      LAUNCH(c, s, MI_K_COLOR, (bgr_to_nv12_hist_kernel<O, U, false>), grid, block, 0, j, (uint32_t*)nullptr);             \
+        if (fl && hist) LAUNCH(c, s, MI_K_COLOR, (bgr_to_nv12_hist_frames_kernel<O, U, true>), grid, block, 0, j, *fl, c->d_partial);   \
+        else if (fl)    LAUNCH(c, s, MI_K_COLOR, (bgr_to_nv12_hist_frames_kernel<O, U, false>), grid, block, 0, j, *fl, (uint32_t*)nullptr); \
+        else if (hist)  LAUNCH(c, s, MI_K_COLOR, (bgr_to_nv12_hist_kernel<O, U, true>), grid, block, 0, j, c->d_partial);              \
+        else            LAUNCH(c, s, MI_K_COLOR, (bgr_to_nv12_hist_kernel<O, U, false>), grid, block, 0, j, (uint32_t*)nullptr);       \
     } while (0)
     if (rgb && cp) MI_BGR_NV12_LAUNCH(1, 1);
     else if (rgb)  MI_BGR_NV12_LAUNCH(1, 0);

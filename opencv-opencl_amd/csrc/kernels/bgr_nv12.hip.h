@@ -26,6 +26,37 @@ struct BgrNv12Job {
     int vec;                                  // 1: W % 16 == 0 and every base / pitch / frame stride a multiple of 16 -> 16 x 2 pixel groups
 };
 
+// Where frame f of a launch lives, as StridedNv12Bgr / TableNv12Bgr (nv12_bgr.hip.h) say it for the opposite direction: the body below
+// is a template on one of these two policies.  The batch entry wraps it with the strided one -- the arithmetic it always had, on the
+// kernel's own argument -- the *_frames_kernel entry with the table.
+struct StridedBgrNv12 {
+    const BgrNv12Job& j;
+    __device__ __forceinline__ const uint8_t* in_of(long long f) const { return j.in + f * j.in_frame; }
+    __device__ __forceinline__ uint8_t* y_of(long long f) const { return j.y + f * j.out_frame; }
+    __device__ __forceinline__ uint8_t* uv_of(long long f) const { return j.uv + f * j.out_frame; }
+    __device__ __forceinline__ bool vec(long long) const { return j.vec; }              // decided by the host for the whole launch
+};
+
+// A list of such frames, each at its own three addresses (mi_*_bgr_to_nv12_frames_dev: a pool of images in, an encoder's surface pool
+// out).  The {in, y, uv} entries travel BY VALUE in the kernel arguments like FrameList -- 64 x 24 B = 1.5 KiB -- and are read with
+// scalar kernarg loads indexed by the frame's grid coordinate.  The shape (pitches, width, height) is the launch's BgrNv12Job, whose
+// in / y / uv / *_frame a table launch ignores and whose vec says what the SHAPE allows (W % 16 == 0, the three pitches multiples of
+// 16): whether frame f takes the 16 x 2 groups is then decided by its own three addresses -- per frame, so uniform for a workgroup.
+struct BgrNv12Frame { const uint8_t* in; uint8_t* y; uint8_t* uv; };
+struct BgrNv12List { BgrNv12Frame f[kFramesPerLaunch]; };
+static_assert(sizeof(BgrNv12Frame) == 24, "three addresses an entry");
+struct TableBgrNv12 {
+    const BgrNv12List& l;
+    const BgrNv12Job& j;
+    __device__ __forceinline__ const uint8_t* in_of(long long f) const { return l.f[f].in; }
+    __device__ __forceinline__ uint8_t* y_of(long long f) const { return l.f[f].y; }
+    __device__ __forceinline__ uint8_t* uv_of(long long f) const { return l.f[f].uv; }
+    __device__ __forceinline__ bool vec(long long f) const
+    {
+        return j.vec && (((uintptr_t)l.f[f].in | (uintptr_t)l.f[f].y | (uintptr_t)l.f[f].uv) & 15) == 0;
+    }
+};
+
 // ---------------------------------------------------------------------------------------------
 // Stage 1.  grid = (B, n_frames), 256 threads.  With HIST: partial[(f * B + part) * 256 + bin], the layout of hist_partial_kernel,
 // which equalize_lut_kernel reads.
@@ -39,8 +70,8 @@ struct BgrNv12Job {
 // halve the tables zeroed and folded; that has not been measured here, and 256 threads keep the grid rule, the byte basis (4.5 B/px
 // moved) and the loop shapes of nv12_to_bgr_kernel and cvt420_kernel, so one derivation of the loop bounds serves all three.
 // ---------------------------------------------------------------------------------------------
-template <int ORDER, int UVMODE, bool HIST>
-__global__ __launch_bounds__(kThreads) void bgr_to_nv12_hist_kernel(BgrNv12Job j, uint32_t* __restrict__ partial)
+template <int ORDER, int UVMODE, bool HIST, class Frames>
+__device__ __forceinline__ void bgr_to_nv12_hist_body(const BgrNv12Job& j, const Frames& fr, uint32_t* __restrict__ partial)
 {
     __shared__ uint32_t h[HIST ? 256 * kCopies : 1];
     const int t = threadIdx.x, f = blockIdx.y;
@@ -49,11 +80,11 @@ __global__ __launch_bounds__(kThreads) void bgr_to_nv12_hist_kernel(BgrNv12Job j
         __syncthreads();
     }
     const uint32_t copy = t & (kCopies - 1);
-    const uint8_t* ip = j.in + (long long)f * j.in_frame;
-    uint8_t* yp = j.y + (long long)f * j.out_frame;
-    uint8_t* uvp = j.uv + (long long)f * j.out_frame;
+    const uint8_t* ip = fr.in_of(f);
+    uint8_t* yp = fr.y_of(f);
+    uint8_t* uvp = fr.uv_of(f);
     constexpr uint32_t kFill = 0x80808080u;
-    if (j.vec) {
+    if (fr.vec(f)) {
         const int gx_n = j.width >> 4;
         const int groups = gx_n * (j.height >> 1);            // < 2^26 (W*H < 2^31)
         const int stride = (int)gridDim.x * kThreads, dby = stride / gx_n, dgx = stride - dby * gx_n;
@@ -116,6 +147,21 @@ __global__ __launch_bounds__(kThreads) void bgr_to_nv12_hist_kernel(BgrNv12Job j
         partial[((size_t)f * gridDim.x + blockIdx.x) * 256 + t] = lds_hist_bin(h, t);      // kThreads == 256 bins
     }
 }
-static_assert(kThreads == 256, "bgr_to_nv12_hist_kernel writes one bin per thread");
+template <int ORDER, int UVMODE, bool HIST>
+__global__ __launch_bounds__(kThreads) void bgr_to_nv12_hist_kernel(BgrNv12Job j, uint32_t* __restrict__ partial)
+{
+    bgr_to_nv12_hist_body<ORDER, UVMODE, HIST>(j, StridedBgrNv12{j}, partial);
+}
+// the same on a frame list: both loops are grid-stride, so one grid (sized by the shape alone) serves frames of either kind; the
+// partials are those of the chunk's frames in list order
+template <int ORDER, int UVMODE, bool HIST>
+__global__ __launch_bounds__(kThreads) void bgr_to_nv12_hist_frames_kernel(BgrNv12Job j, BgrNv12List l, uint32_t* __restrict__ partial)
+{
+    bgr_to_nv12_hist_body<ORDER, UVMODE, HIST>(j, TableBgrNv12{l, j}, partial);
+}
+static_assert(kThreads == 256, "bgr_to_nv12_hist_body writes one bin per thread");
+// 256: the implicit arguments a code object carries behind the explicit ones
+static_assert(sizeof(BgrNv12Job) + sizeof(BgrNv12List) + sizeof(uint32_t*) + 256 <= 4096,
+              "the table and the remaining arguments of bgr_to_nv12_hist_frames_kernel stay below HIP's 4 KiB of kernel arguments");
 
 }  // namespace mi

@@ -56,6 +56,7 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_nv12_to_bgr_batch_dev", "mi_clahe_nv12_to_bgr_batch_dev", "mi_equalize_hist_nv12_to_bgr", "mi_clahe_nv12_to_bgr",
     "mi_equalize_hist_nv12_to_bgr_frames_dev", "mi_clahe_nv12_to_bgr_frames_dev",
     "mi_equalize_hist_bgr_to_nv12_batch_dev", "mi_clahe_bgr_to_nv12_batch_dev", "mi_equalize_hist_bgr_to_nv12", "mi_clahe_bgr_to_nv12",
+    "mi_equalize_hist_bgr_to_nv12_frames_dev", "mi_clahe_bgr_to_nv12_frames_dev",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -95,6 +96,12 @@ class Nv12BgrFrameDev(C.Structure):
     """mi_nv12_bgr_frame_dev: one frame of an NV12 -> BGR / RGB list, its two input plane addresses and its image address (device
     pointers)."""
     _fields_ = [("y", C.c_void_p), ("uv", C.c_void_p), ("out", C.c_void_p)]
+
+
+class BgrNv12FrameDev(C.Structure):
+    """mi_bgr_nv12_frame_dev: one frame of a BGR / RGB -> NV12 list, its image address and its two output plane addresses (device
+    pointers)."""
+    _fields_ = [("in_", C.c_void_p), ("y", C.c_void_p), ("uv", C.c_void_p)]
 
 
 class MiError(RuntimeError):
@@ -200,6 +207,8 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_bgr_to_nv12_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, vp, sz, sz, i, i, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_bgr_to_nv12.argtypes = [vp, vp, sz, vp, i, i, i, i]
     L.mi_clahe_bgr_to_nv12.argtypes = [vp, vp, sz, vp, i, i, i, i, d, i, i]
+    L.mi_equalize_hist_bgr_to_nv12_frames_dev.argtypes = [vp, C.POINTER(BgrNv12FrameDev), i, i, i, sz, sz, sz, i, i, vp]
+    L.mi_clahe_bgr_to_nv12_frames_dev.argtypes = [vp, C.POINTER(BgrNv12FrameDev), i, i, i, sz, sz, sz, i, i, d, i, i, vp]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -361,6 +370,24 @@ def _nv12_bgr_list(ys, uvs, outs, width, y_pitch, uv_pitch, out_pitch, what):
     for k in range(len(ys)):
         arr[k] = Nv12BgrFrameDev(_dptr(ys[k]), _dptr(uvs[k]), _dptr(outs[k]))
     return arr, len(ys), yp, up, op
+
+
+def _bgr_nv12_list(ins, ys, uvs, width, in_pitch, y_pitch, uv_pitch, what):
+    """ins / ys / uvs: sequences of equal length (torch CUDA tensors or raw device addresses).  Returns the mi_bgr_nv12_frame_dev
+    array, its length and the three pitches (given, else the row stride of the tensors -- H x 3W or H x W x 3 images, H x W planes --
+    else 3 * width for the images and width for the planes)."""
+    ins, ys, uvs = list(ins), list(ys), list(uvs)
+    if not (len(ins) == len(ys) == len(uvs)):
+        raise MiError(1, what, f"{len(ins)} images but {len(ys)} Y planes and {len(uvs)} UV planes")
+    # an H x W x 3 image's rows are its first axis: seen as H x 3W for the pitch
+    rows = [o if isinstance(o, int) or o is None or o.dim() != 3 else o[:, :, 0] for o in ins]
+    ip = int(in_pitch) if in_pitch is not None else _plane_pitch(rows, None, 3 * int(width), what)
+    yp = _plane_pitch(ys, y_pitch, int(width), what)
+    up = _plane_pitch(uvs, uv_pitch, int(width), what)
+    arr = (BgrNv12FrameDev * max(1, len(ins)))()
+    for k in range(len(ins)):
+        arr[k] = BgrNv12FrameDev(_dptr(ins[k]), _dptr(ys[k]), _dptr(uvs[k]))
+    return arr, len(ins), ip, yp, up
 
 
 _live_contexts: "weakref.WeakSet[Context]" = weakref.WeakSet()
@@ -890,6 +917,23 @@ class Context:
         self._chk(self._L.mi_clahe_bgr_to_nv12_batch_dev(self._h, _dptr(d_in), ip, fi, y, yp, uv, up, fo, int(width), int(height),
                                                        int(n_frames), int(order), int(uv_mode), float(clip_limit), int(tiles_x),
                                                        int(tiles_y), stream), "mi_clahe_bgr_to_nv12_batch_dev")
+
+    def equalize_hist_bgr_to_nv12_frames(self, ins, ys, uvs, width, height, order=ORDER_BGR, uv_mode=UV_COPY, in_pitch=None, y_pitch=None,
+                                         uv_pitch=None, stream=0):
+        """mi_equalize_hist_bgr_to_nv12_frames_dev.  ins: the images, ys / uvs: the Y and UV planes, each its own buffer -- lists of
+        torch CUDA tensors or raw device addresses, one entry per frame.  A pitch left at None is the row stride of the 2-D tensors of
+        that list (H x W x 3 images: of their rows), or the tight one (3 * width; width)."""
+        arr, n, ip, yp, up = _bgr_nv12_list(ins, ys, uvs, width, in_pitch, y_pitch, uv_pitch, "equalize_hist_bgr_to_nv12_frames")
+        self._chk(self._L.mi_equalize_hist_bgr_to_nv12_frames_dev(self._h, arr, n, int(width), int(height), ip, yp, up, int(order),
+                                                                int(uv_mode), stream), "mi_equalize_hist_bgr_to_nv12_frames_dev")
+
+    def clahe_bgr_to_nv12_frames(self, ins, ys, uvs, width, height, order=ORDER_BGR, uv_mode=UV_COPY, clip_limit=2.0, tiles_x=8,
+                                 tiles_y=8, in_pitch=None, y_pitch=None, uv_pitch=None, stream=0):
+        """mi_clahe_bgr_to_nv12_frames_dev; arguments as equalize_hist_bgr_to_nv12_frames, plus the CLAHE parameters."""
+        arr, n, ip, yp, up = _bgr_nv12_list(ins, ys, uvs, width, in_pitch, y_pitch, uv_pitch, "clahe_bgr_to_nv12_frames")
+        self._chk(self._L.mi_clahe_bgr_to_nv12_frames_dev(self._h, arr, n, int(width), int(height), ip, yp, up, int(order), int(uv_mode),
+                                                        float(clip_limit), int(tiles_x), int(tiles_y), stream),
+                  "mi_clahe_bgr_to_nv12_frames_dev")
 
     def _bgr_nv12_host(self, img, out, name):
         img = self._host3(img, name)
