@@ -614,6 +614,67 @@ mi_status mi_clahe_bgr_to_nv12_frames_dev(mi_ctx* ctx, const mi_bgr_nv12_frame_d
         int width, int height, size_t in_pitch, size_t y_pitch, size_t uv_pitch, int order, mi_uv_mode uv_mode,
         double clip_limit, int tiles_x, int tiles_y, void* stream);
 
+/* mi_*_yuv420*: equalizeHist / CLAHE on the luma of 8-bit 4:2:0 frames whose two sides each say where their planes lie and whether
+ * their chroma is interleaved (NV12: one plane of U, V pairs) or planar (I420 / YV12: a U plane and a V plane).  One form gives
+ * I420 / YV12 -> I420 / YV12 (pitched planes, separately allocated planes, in place), I420 / YV12 -> NV12 (software decoder -> hardware
+ * encoder surface), NV12 -> I420 / YV12 (hardware decoder or camera -> software encoder) and NV12 -> NV12, without plane copies or an
+ * interleave of U and V outside the library.  c0 is always the U (Cb) plane and c1 the V (Cr) plane: YV12 needs no name of its own, a
+ * YV12 caller passes the address of the SECOND chroma plane of its frame as c0 and that of the first as c1.  NV21 is not supported.
+ * Both descriptors are read only during the call.  The planes of `in` are never written, except where a plane is processed in place.
+ * Luma: for frame f the output Y plane is byte for byte what mi_equalize_hist_u8_batch_dev / mi_clahe_u8_batch_dev write for the plane
+ *   (in->y, in->y_pitch, in->frame_stride) -> (out->y, out->y_pitch, out->frame_stride): the same kernels chosen the same way for the
+ *   batch (the fused equalizeHist kernel included, where it applies), the same clahe_fp_contract and two_kernel_max_frames options, the
+ *   same REFLECT_101 padding when the tile grid does not divide the frame, the same limits on sizes and tile grids, the same statuses.
+ * Chroma, MI_UV_COPY: every chroma sample is carried over unchanged into the output's layout.  planar -> interleaved:
+ *   uv[r][2i] = U[r][i], uv[r][2i+1] = V[r][i]; interleaved -> planar: the inverse; same layout: a row copy.
+ * Chroma, MI_UV_FILL128: every chroma byte of the output is 128.  in->c0 / in->c1 are not read and may be NULL; in->c_pitch and
+ *   in->chroma's planes take no part in the checks below (in->chroma itself must still be one of the two values).
+ * Writes: only the W bytes (Y, interleaved UV) or W/2 bytes (planar U, V) of each output row are written: not the pitch padding, not
+ *   the gaps between planes, not the gaps between frames.
+ * Width and height are even.  No alignment is required of any pointer, pitch or stride.  A layout change moves 16 bytes per access
+ *   when W % 32 == 0 and all chroma pointers, both c_pitch and both frame_stride are multiples of 16 (the Y side plays no part), and
+ *   one U, V sample pair per access with byte loads and stores otherwise -- slower, the same bytes out.  A same-layout move and a fill
+ *   have no rule: every row is written with aligned 16-byte stores and at most 15 + 15 byte stores at its ends, wherever it lies.
+ * In place: a plane may be processed in place when it is EXACTLY the same plane on both sides: the same address, the same pitch, the
+ *   same frame_stride and, for a chroma plane, the same layout.  In-place chroma with MI_UV_COPY moves nothing; with MI_UV_FILL128 it
+ *   writes 128.  Y may be in place while the chroma is converted into other memory, and the other way round.
+ * Launches: the luma is what the planar form launches for the whole batch; the chroma is ONE launch of its own per chunk of 256 frames,
+ *   charged to MI_K_LUT_APPLY like the chroma kernels of the NV12 and P010 forms (no launch at all when every chroma plane is copied in
+ *   place).  mi_ctx_get_stat "yuv420_chroma_vec" / "yuv420_chroma_bytes" count the calls whose chroma launch moved 16 bytes per access
+ *   (every same-layout move and fill, and the layout changes the rule above admits) / changed the layout with byte accesses; a call that
+ *   launches no chroma kernel counts in neither.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of the
+ *   same shape as the other batched device forms.
+ * mi_equalize_hist_yuv420 / mi_clahe_yuv420: ONE frame with `in` / `out` holding HOST pointers, at any address and any pitch;
+ *   frame_stride is ignored.  Synchronous, staged like mi_*_packed422_to_nv12: planes in pinned memory that are tight are DMA'd as they
+ *   are, everything else goes through the context's pinned staging; on the device the frame is tight at the kernels' own pitches.
+ *   Whatever the call returns, no copy on the caller's memory is in flight any more when it returns.  W*H beyond what
+ *   mi_cvt_color_420_u8 accepts: MI_ERR_UNSUPPORTED.
+ * Errors, MI_ERR_BAD_ARG: a null ctx, `in` or `out`; a null y; a null out->c0; a null out->c1 on a PLANAR output; a null input chroma
+ *   pointer that MI_UV_COPY needs; a `chroma` other than the two values; a bad uv_mode; a negative size; an odd width or an odd height
+ *   (refused even when another size is 0, as in the sibling forms); y_pitch < W; a c_pitch below its row (W interleaved, W/2 planar);
+ *   tiles <= 0; two output plane pointers of the call that are equal; an output plane pointer equal to an input plane pointer other than
+ *   that exact in-place case (a c1 of an INTERLEAVED side is ignored throughout).  Any other overlap: undefined, not checked.  width,
+ *   height or n_frames of 0: MI_OK, nothing written.  Sizes and tile grids the planar forms refuse: the status they give
+ *   (MI_ERR_UNSUPPORTED), nothing written.  Nothing is enqueued unless all checks pass. */
+enum { MI_CHROMA_INTERLEAVED = 0, MI_CHROMA_PLANAR = 1 };
+typedef struct mi_yuv420_planes {
+    void*  y;   size_t y_pitch;        /* H rows of W bytes */
+    void*  c0;  void*  c1;             /* INTERLEAVED: c0 = UV plane, H/2 rows of W bytes (U first), c1 ignored (may be NULL)
+                                          PLANAR:      c0 = U plane, c1 = V plane, each H/2 rows of W/2 bytes            */
+    size_t c_pitch;                    /* bytes between chroma rows (both planes of a PLANAR side share it) */
+    size_t frame_stride;               /* frame f: every plane pointer + f * frame_stride (ignored by the host forms) */
+    int    chroma;                     /* MI_CHROMA_* */
+} mi_yuv420_planes;                    /* 56 bytes on LP64 */
+mi_status mi_equalize_hist_yuv420_batch_dev(mi_ctx* ctx, const mi_yuv420_planes* in, const mi_yuv420_planes* out,
+        int width, int height, int n_frames, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_yuv420_batch_dev(mi_ctx* ctx, const mi_yuv420_planes* in, const mi_yuv420_planes* out,
+        int width, int height, int n_frames, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y, void* stream);
+mi_status mi_equalize_hist_yuv420(mi_ctx* ctx, const mi_yuv420_planes* in, const mi_yuv420_planes* out,
+        int width, int height, mi_uv_mode uv_mode);
+mi_status mi_clahe_yuv420(mi_ctx* ctx, const mi_yuv420_planes* in, const mi_yuv420_planes* out,
+        int width, int height, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
+
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at
  * OpenCVequalHist.cpp:115/:158).  Registering a pool's memory once lets the host-pointer forms DMA straight

@@ -346,7 +346,8 @@ mi_status mi_ctx_synchronize(mi_ctx* c, void* stream)
 // "fused_last_policy" (cache-policy code of the last fused launch this context made, see equalize_fused_kernel; all ones before the first),
 // "fused_stream_min_bytes" (bytes a launch loads and stores from which fused_cache_policy = 0 chooses the streaming policy),
 // "nv12_bgr_onepass" / "nv12_bgr_twopass" (mi_*_nv12_to_bgr* calls whose pixels were mapped and converted in one kernel / that ran the
-// planar CLAHE into scratch and the conversion after it).
+// planar CLAHE into scratch and the conversion after it), "yuv420_chroma_vec" / "yuv420_chroma_bytes" (mi_*_yuv420* calls whose chroma
+// launch moved 16 bytes per access / changed the layout with byte accesses; a call that launched no chroma kernel counts in neither).
 mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
 {
     ENTER(c);
@@ -372,6 +373,8 @@ mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
         }
     if (!strcmp(name, "nv12_bgr_onepass")) { *out = c->nv12_bgr_onepass; return MI_OK; }
     if (!strcmp(name, "nv12_bgr_twopass")) { *out = c->nv12_bgr_twopass; return MI_OK; }
+    if (!strcmp(name, "yuv420_chroma_vec")) { *out = c->yuv420_chroma_vec; return MI_OK; }
+    if (!strcmp(name, "yuv420_chroma_bytes")) { *out = c->yuv420_chroma_bytes; return MI_OK; }
     return fail(c, MI_ERR_BAD_ARG, "unknown stat");
 }
 

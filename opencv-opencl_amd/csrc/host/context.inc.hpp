@@ -160,6 +160,8 @@ struct mi_ctx {
     size_t sample_pos[MI_K_COUNT] = {};
     unsigned long long nv12_bgr_onepass = 0, nv12_bgr_twopass = 0;      // statistics "nv12_bgr_onepass" / "nv12_bgr_twopass": mi_*_nv12_to_bgr* calls whose pixels
                                                                         // were mapped and converted in one kernel / that took the planar CLAHE + decode fallback
+    unsigned long long yuv420_chroma_vec = 0, yuv420_chroma_bytes = 0;  // statistics "yuv420_chroma_vec" / "yuv420_chroma_bytes": mi_*_yuv420* calls whose chroma
+                                                                        // launch moved 16 bytes per access / changed the layout sample pair by sample pair
 };
 
 namespace {

@@ -510,6 +510,50 @@ inline void claheBGRToNV12(const unsigned char* in, size_t inStep, unsigned char
                                           tiles.height), "mi_clahe_bgr_to_nv12");
 }
 
+// One 8-bit 4:2:0 host frame whose planes lie where the view says: interleaved chroma (NV12) or planar (I420, YV12), tight or pitched,
+// in one allocation or three.  cv::equalizeHist / CLAHE::apply on the Y plane, the chroma carried into the output view's layout
+// (UV_COPY) or set to 128 (UV_FILL128): a software decoder's I420 frame -> an NV12 encoder surface, or the other way round, without
+// plane copies or an interleave outside the library.  c0 is always the U plane and c1 the V plane.  Width and height are even; a plane
+// may be processed in place when it is exactly the same plane in both views.
+struct YUV420View {
+    unsigned char* y = nullptr;  size_t yPitch = 0;
+    unsigned char* c0 = nullptr; unsigned char* c1 = nullptr;      // interleaved: c0 = UV plane, c1 unused; planar: c0 = U, c1 = V
+    size_t cPitch = 0;
+    bool planar = false;
+    // tight frames of width * height * 3 / 2 bytes at `p`
+    static YUV420View nv12(unsigned char* p, int w, int h)
+    {
+        YUV420View v; v.y = p; v.yPitch = (size_t)w; v.c0 = p + (size_t)w * h; v.cPitch = (size_t)w; return v;
+    }
+    static YUV420View i420(unsigned char* p, int w, int h)
+    {
+        YUV420View v; v.y = p; v.yPitch = (size_t)w; v.c0 = p + (size_t)w * h; v.c1 = v.c0 + (size_t)(w / 2) * (h / 2);
+        v.cPitch = (size_t)(w / 2); v.planar = true; return v;
+    }
+    static YUV420View yv12(unsigned char* p, int w, int h)
+    {
+        YUV420View v = i420(p, w, h); unsigned char* t = v.c0; v.c0 = v.c1; v.c1 = t; return v;
+    }
+    mi_yuv420_planes planes() const
+    {
+        mi_yuv420_planes d; d.y = y; d.y_pitch = yPitch; d.c0 = c0; d.c1 = c1; d.c_pitch = cPitch; d.frame_stride = 0;
+        d.chroma = planar ? MI_CHROMA_PLANAR : MI_CHROMA_INTERLEAVED; return d;
+    }
+};
+inline void equalizeHistYUV420(const YUV420View& in, const YUV420View& out, int width, int height, int uvMode)
+{
+    mi_ctx* c = detail::thread_ctx();
+    const mi_yuv420_planes a = in.planes(), b = out.planes();
+    detail::check(c, mi_equalize_hist_yuv420(c, &a, &b, width, height, (mi_uv_mode)uvMode), "mi_equalize_hist_yuv420");
+}
+inline void claheYUV420(const YUV420View& in, const YUV420View& out, int width, int height, int uvMode, double clipLimit, Size tiles)
+{
+    mi_ctx* c = detail::thread_ctx();
+    const mi_yuv420_planes a = in.planes(), b = out.planes();
+    detail::check(c, mi_clahe_yuv420(c, &a, &b, width, height, (mi_uv_mode)uvMode, clipLimit, tiles.width, tiles.height),
+                  "mi_clahe_yuv420");
+}
+
 // BASELINE.json config 5 read literally: cvtColor(COLOR_YUV2BGR_NV12) -> split -> equalizeHist on B, G and R -> merge ->
 // cvtColor(COLOR_BGR2YUV_I420) + U/V interleave, NV12 in -> NV12 out in one call (no file of the reference does this;
 // ColoropenCVCwqualHist.cpp itself is equalizeHistNV12(..., UV_COPY)).  Width and height must be even.

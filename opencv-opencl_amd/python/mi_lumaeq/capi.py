@@ -26,6 +26,7 @@ PIPE_UV_AUTO, PIPE_UV_HOST, PIPE_UV_DEVICE = 0, 1, 2
 FMT_NV12, FMT_P010 = 0, 1              # MI_FMT_*: P010 = any 16-bit LE 4:2:0 semi-planar frame (P010 / P012 / P016)
 FMT_YUY2, FMT_UYVY = 2, 3              # packed 8-bit 4:2:2: luma at byte 0 (YUY2 / YUYV / YVYU) or byte 1 (UYVY / VYUY) of each 2-byte pixel
 ORDER_BGR, ORDER_RGB = 0, 1            # MI_ORDER_*: channel order of the interleaved side of the NV12 -> BGR and BGR -> NV12 forms
+CHROMA_INTERLEAVED, CHROMA_PLANAR = 0, 1     # MI_CHROMA_*: the chroma of one side of the mi_*_yuv420* forms -- one plane of U, V pairs (NV12) or a U and a V plane (I420 / YV12)
 ERR_BUSY = 6
 
 # every extern "C" symbol include/mi_lumaeq.h declares (tests check the .so exports them all)
@@ -57,6 +58,7 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_nv12_to_bgr_frames_dev", "mi_clahe_nv12_to_bgr_frames_dev",
     "mi_equalize_hist_bgr_to_nv12_batch_dev", "mi_clahe_bgr_to_nv12_batch_dev", "mi_equalize_hist_bgr_to_nv12", "mi_clahe_bgr_to_nv12",
     "mi_equalize_hist_bgr_to_nv12_frames_dev", "mi_clahe_bgr_to_nv12_frames_dev",
+    "mi_equalize_hist_yuv420_batch_dev", "mi_clahe_yuv420_batch_dev", "mi_equalize_hist_yuv420", "mi_clahe_yuv420",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -102,6 +104,32 @@ class BgrNv12FrameDev(C.Structure):
     """mi_bgr_nv12_frame_dev: one frame of a BGR / RGB -> NV12 list, its image address and its two output plane addresses (device
     pointers)."""
     _fields_ = [("in_", C.c_void_p), ("y", C.c_void_p), ("uv", C.c_void_p)]
+
+
+class Yuv420Planes(C.Structure):
+    """mi_yuv420_planes: where the planes of one side of a mi_*_yuv420* call lie (device pointers for the batched forms, host pointers for
+    the host forms).  c0 is always the U plane and c1 the V plane; an INTERLEAVED side has its UV plane in c0.  nv12() / i420() / yv12()
+    describe tight frames of W*H*3/2 bytes starting at `base` (a raw address or a torch CUDA tensor)."""
+    _fields_ = [("y", C.c_void_p), ("y_pitch", C.c_size_t), ("c0", C.c_void_p), ("c1", C.c_void_p), ("c_pitch", C.c_size_t),
+                ("frame_stride", C.c_size_t), ("chroma", C.c_int)]
+
+    @classmethod
+    def nv12(cls, base, width, height):
+        b, w, h = _dptr(base), int(width), int(height)
+        return cls(b, w, b + w * h, None, w, w * h * 3 // 2, CHROMA_INTERLEAVED)
+
+    @classmethod
+    def i420(cls, base, width, height):
+        b, w, h = _dptr(base), int(width), int(height)
+        return cls(b, w, b + w * h, b + w * h + (w // 2) * (h // 2), w // 2, w * h * 3 // 2, CHROMA_PLANAR)
+
+    @classmethod
+    def yv12(cls, base, width, height):
+        b, w, h = _dptr(base), int(width), int(height)
+        return cls(b, w, b + w * h + (w // 2) * (h // 2), b + w * h, w // 2, w * h * 3 // 2, CHROMA_PLANAR)
+
+
+_YUV420_FMTS = {"nv12": Yuv420Planes.nv12, "i420": Yuv420Planes.i420, "yv12": Yuv420Planes.yv12}
 
 
 class MiError(RuntimeError):
@@ -209,6 +237,11 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_bgr_to_nv12.argtypes = [vp, vp, sz, vp, i, i, i, i, d, i, i]
     L.mi_equalize_hist_bgr_to_nv12_frames_dev.argtypes = [vp, C.POINTER(BgrNv12FrameDev), i, i, i, sz, sz, sz, i, i, vp]
     L.mi_clahe_bgr_to_nv12_frames_dev.argtypes = [vp, C.POINTER(BgrNv12FrameDev), i, i, i, sz, sz, sz, i, i, d, i, i, vp]
+    yp = C.POINTER(Yuv420Planes)
+    L.mi_equalize_hist_yuv420_batch_dev.argtypes = [vp, yp, yp, i, i, i, i, vp]
+    L.mi_clahe_yuv420_batch_dev.argtypes = [vp, yp, yp, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_yuv420.argtypes = [vp, yp, yp, i, i, i]
+    L.mi_clahe_yuv420.argtypes = [vp, yp, yp, i, i, i, d, i, i]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -959,6 +992,49 @@ class Context:
         img, h, w, step, out = self._bgr_nv12_host(img, out, "clahe_bgr_to_nv12")
         self._chk(self._L.mi_clahe_bgr_to_nv12(self._h, img.ctypes.data, step, out.ctypes.data, w, h, int(order), int(uv_mode),
                                              float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_bgr_to_nv12")
+        return out
+
+    # ---- 4:2:0 frames whose sides say where their planes lie: I420 / YV12 / NV12 in, any of them out ----
+    def equalize_hist_yuv420_batch_dev(self, src, dst, width, height, n_frames, uv_mode=UV_COPY, stream=0):
+        """mi_equalize_hist_yuv420_batch_dev.  src / dst: Yuv420Planes holding device addresses (Yuv420Planes.nv12 / .i420 / .yv12 for
+        tight batches, the fields themselves for pitched or separately allocated planes)."""
+        self._chk(self._L.mi_equalize_hist_yuv420_batch_dev(self._h, C.byref(src), C.byref(dst), int(width), int(height), int(n_frames),
+                                                          int(uv_mode), stream), "mi_equalize_hist_yuv420_batch_dev")
+
+    def clahe_yuv420_batch_dev(self, src, dst, width, height, n_frames, uv_mode=UV_COPY, clip_limit=2.0, tiles_x=8, tiles_y=8, stream=0):
+        """mi_clahe_yuv420_batch_dev; arguments as equalize_hist_yuv420_batch_dev, plus the CLAHE parameters."""
+        self._chk(self._L.mi_clahe_yuv420_batch_dev(self._h, C.byref(src), C.byref(dst), int(width), int(height), int(n_frames),
+                                                  int(uv_mode), float(clip_limit), int(tiles_x), int(tiles_y), stream),
+                  "mi_clahe_yuv420_batch_dev")
+
+    @staticmethod
+    def _yuv420_host(frame, width, height, src_fmt, dst_fmt, out, name):
+        n = int(width) * int(height) * 3 // 2
+        if src_fmt not in _YUV420_FMTS or dst_fmt not in _YUV420_FMTS:
+            raise MiError(1, name, 'src_fmt / dst_fmt must be "nv12", "i420" or "yv12"')
+        if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or not frame.flags.c_contiguous or frame.size != n:
+            raise MiError(1, name, "frame must be a contiguous uint8 array of width*height*3/2 bytes")
+        if out is None:
+            out = np.empty(n, np.uint8)
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous or out.size != n:
+            raise MiError(1, name, "out must be a contiguous uint8 array of width*height*3/2 bytes")
+        return _YUV420_FMTS[src_fmt](frame.ctypes.data, width, height), _YUV420_FMTS[dst_fmt](out.ctypes.data, width, height), out
+
+    def equalize_hist_yuv420(self, frame: np.ndarray, width: int, height: int, src_fmt: str, dst_fmt: str, uv_mode: int = UV_COPY,
+                             out: np.ndarray | None = None) -> np.ndarray:
+        """mi_equalize_hist_yuv420 on a tight host frame of W*H*3/2 bytes: src_fmt / dst_fmt in {"nv12", "i420", "yv12"} say how the
+        chroma of `frame` and of the result lies; the result is `out` when given, else a new array."""
+        a, b, out = self._yuv420_host(frame, width, height, src_fmt, dst_fmt, out, "equalize_hist_yuv420")
+        self._chk(self._L.mi_equalize_hist_yuv420(self._h, C.byref(a), C.byref(b), int(width), int(height), int(uv_mode)),
+                  "mi_equalize_hist_yuv420")
+        return out
+
+    def clahe_yuv420(self, frame: np.ndarray, width: int, height: int, src_fmt: str, dst_fmt: str, uv_mode: int = UV_COPY,
+                     clip_limit: float = 2.0, tiles_x: int = 8, tiles_y: int = 8, out: np.ndarray | None = None) -> np.ndarray:
+        """mi_clahe_yuv420; arguments as equalize_hist_yuv420, plus the CLAHE parameters."""
+        a, b, out = self._yuv420_host(frame, width, height, src_fmt, dst_fmt, out, "clahe_yuv420")
+        self._chk(self._L.mi_clahe_yuv420(self._h, C.byref(a), C.byref(b), int(width), int(height), int(uv_mode), float(clip_limit),
+                                        int(tiles_x), int(tiles_y)), "mi_clahe_yuv420")
         return out
 
     # ---- colour-domain neighbours (N3) ----
