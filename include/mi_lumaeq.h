@@ -674,6 +674,62 @@ mi_status mi_equalize_hist_yuv420(mi_ctx* ctx, const mi_yuv420_planes* in, const
         int width, int height, mi_uv_mode uv_mode);
 mi_status mi_clahe_yuv420(mi_ctx* ctx, const mi_yuv420_planes* in, const mi_yuv420_planes* out,
         int width, int height, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
+/* mi_*_yuv420_frames_dev: the same on a LIST of device frames, each plane at its own address -- a software decoder's frame pool (every
+ * frame three separately allocated, pitched planes: data[0..2], linesize[0..2]) in, a hardware encoder's surface pool (every NV12
+ * surface its own allocation) out, or any other pairing of the two layouts.  The batch form needs the whole batch in one allocation at
+ * a constant frame stride; one n_frames = 1 batch call per frame costs a launch sequence per frame, and repacking a pool into a batch
+ * moves every byte twice more.  `frames` is a host array of n_frames entries, read only during the call; the pointers in it are device
+ * pointers on the context's device.
+ * Shape: all frames of one call share width, height, uv_mode, the two layouts and the four pitches (bytes between rows: y_in_pitch and
+ *   y_out_pitch >= W; c_in_pitch and c_out_pitch >= W for an INTERLEAVED side, >= W/2 for a PLANAR one, both planes of a planar side
+ *   sharing theirs); each has its own addresses.  There are no per-frame pitches.
+ * Chroma layout: in_chroma / out_chroma are MI_CHROMA_INTERLEAVED or MI_CHROMA_PLANAR.  c0 is always the U plane and c1 the V plane: a
+ *   YV12 caller exchanges the two addresses.  The c1 of an INTERLEAVED side is ignored and may be NULL.  With MI_UV_FILL128 the input
+ *   chroma pointers and c_in_pitch are ignored (in_chroma must still be one of the two values).
+ * Bytes: for every frame the output planes are byte for byte what mi_*_yuv420_batch_dev writes for that frame alone with n_frames = 1
+ *   at the same pitches: cv::equalizeHist / CLAHE::apply on Y -- the clahe_fp_contract option is honoured, REFLECT_101 padding applies
+ *   when the tile grid does not divide the frame -- and every chroma sample carried over into the output's layout (MI_UV_COPY) or every
+ *   chroma byte 128 (MI_UV_FILL128).
+ * Writes: only the W bytes (Y, interleaved UV) or W/2 bytes (planar U, V) of each output row are written, not the pitch padding; the
+ *   input planes are never written, except where a plane is processed in place.
+ * Alignment: none is required of any address or pitch.  The per-frame alignment decides the access width of a layout change: when
+ *   W % 32 == 0 and both c_pitch are multiples of 16 -- the batch form's rule without the frame-stride term -- a frame whose own chroma
+ *   pointers are multiples of 16 moves 16 bytes per access, and any other frame of the same call moves one U, V sample pair per access
+ *   while its neighbours stay vectorised -- slower, the same bytes out.  The Y side plays no part; a same-layout move and a fill have
+ *   no rule.
+ * In place, per frame: a plane is processed in place when it is EXACTLY the same plane on both sides of its entry: the same address,
+ *   the same pitch and, for a chroma plane, the same layout.  In-place chroma with MI_UV_COPY moves nothing; with MI_UV_FILL128 it
+ *   writes 128.  One list may mix in-place and out-of-place frames; Y may be in place while the chroma is not, and the other way round.
+ * Launches, per chunk of 64 frames of the list: the luma is what mi_*_nv12_frames_dev launches for the same Y planes (the planar
+ *   kernels' frame-list entries; never the fused equalizeHist kernel), then ONE launch of the chroma kernel's list entry, charged to
+ *   MI_K_LUT_APPLY like the batch form's -- none for a chunk in which every frame copies all of its chroma in place.  Launches are
+ *   charged to the same profiling slots as the batch form.  mi_ctx_get_stat "yuv420_list_frames_vec" / "yuv420_list_frames_bytes" count
+ *   the FRAMES (not calls) of list calls that changed the layout under MI_UV_COPY with 16-byte / with byte accesses;
+ *   "yuv420_chroma_vec" / "yuv420_chroma_bytes" are not touched by list calls.
+ * Overlap: MI_ERR_BAD_ARG for two equal output plane pointers within a frame, and for an output plane pointer equal to an input plane
+ *   pointer of the same frame other than the exact in-place case.  The checks are pointer equality, not address ranges, on purpose: a
+ *   layout with the U and V rows side by side in one pitched plane (c1 = c0 + W/2, c_pitch = W) is legal here, as it is in the batch
+ *   form.  Any other overlap -- within a frame, between outputs, with ANOTHER frame's planes -- is undefined and not checked.  The same
+ *   input planes may appear in several entries (inputs are only read).
+ * Errors, MI_ERR_BAD_ARG: a null ctx; a null `frames` with n_frames > 0; in any entry a null y_in / y_out, a null c0_out, a null c1_out
+ *   on a PLANAR output, a null input chroma pointer that MI_UV_COPY needs; an in_chroma / out_chroma other than the two values; a bad
+ *   uv_mode; a negative size; an odd width or an odd height (refused even when another size is 0, as in the batch form); a y pitch < W;
+ *   a c pitch below its row; tiles <= 0; the overlap above.  Sizes and tile grids the planar forms refuse: the status they give
+ *   (MI_ERR_UNSUPPORTED).  width, height or n_frames of 0: MI_OK, nothing written.  Nothing is enqueued unless every frame passes the
+ *   checks: a bad last entry leaves the first frames' outputs untouched.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of
+ *   the same shape as the other device list forms; a captured graph holds the addresses it was captured with. */
+typedef struct mi_yuv420_frame_dev {
+    const void* y_in;  const void* c0_in;  const void* c1_in;
+    void*       y_out; void*       c0_out; void*       c1_out;
+} mi_yuv420_frame_dev;                       /* 48 bytes on LP64 */
+mi_status mi_equalize_hist_yuv420_frames_dev(mi_ctx* ctx, const mi_yuv420_frame_dev* frames, int n_frames,
+        int width, int height, size_t y_in_pitch, size_t c_in_pitch, int in_chroma,
+        size_t y_out_pitch, size_t c_out_pitch, int out_chroma, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_yuv420_frames_dev(mi_ctx* ctx, const mi_yuv420_frame_dev* frames, int n_frames,
+        int width, int height, size_t y_in_pitch, size_t c_in_pitch, int in_chroma,
+        size_t y_out_pitch, size_t c_out_pitch, int out_chroma, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
 
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at

@@ -347,7 +347,9 @@ mi_status mi_ctx_synchronize(mi_ctx* c, void* stream)
 // "fused_stream_min_bytes" (bytes a launch loads and stores from which fused_cache_policy = 0 chooses the streaming policy),
 // "nv12_bgr_onepass" / "nv12_bgr_twopass" (mi_*_nv12_to_bgr* calls whose pixels were mapped and converted in one kernel / that ran the
 // planar CLAHE into scratch and the conversion after it), "yuv420_chroma_vec" / "yuv420_chroma_bytes" (mi_*_yuv420* calls whose chroma
-// launch moved 16 bytes per access / changed the layout with byte accesses; a call that launched no chroma kernel counts in neither).
+// launch moved 16 bytes per access / changed the layout with byte accesses; a call that launched no chroma kernel counts in neither),
+// "yuv420_list_frames_vec" / "yuv420_list_frames_bytes" (FRAMES of mi_*_yuv420_frames_dev calls that changed the layout under MI_UV_COPY
+// with 16-byte / with byte accesses, each by its own addresses; list calls do not touch the two per-call counters before them).
 mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
 {
     ENTER(c);
@@ -375,6 +377,8 @@ mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
     if (!strcmp(name, "nv12_bgr_twopass")) { *out = c->nv12_bgr_twopass; return MI_OK; }
     if (!strcmp(name, "yuv420_chroma_vec")) { *out = c->yuv420_chroma_vec; return MI_OK; }
     if (!strcmp(name, "yuv420_chroma_bytes")) { *out = c->yuv420_chroma_bytes; return MI_OK; }
+    if (!strcmp(name, "yuv420_list_frames_vec")) { *out = c->yuv420_list_frames_vec; return MI_OK; }
+    if (!strcmp(name, "yuv420_list_frames_bytes")) { *out = c->yuv420_list_frames_bytes; return MI_OK; }
     return fail(c, MI_ERR_BAD_ARG, "unknown stat");
 }
 

@@ -162,6 +162,8 @@ struct mi_ctx {
                                                                         // were mapped and converted in one kernel / that took the planar CLAHE + decode fallback
     unsigned long long yuv420_chroma_vec = 0, yuv420_chroma_bytes = 0;  // statistics "yuv420_chroma_vec" / "yuv420_chroma_bytes": mi_*_yuv420* calls whose chroma
                                                                         // launch moved 16 bytes per access / changed the layout sample pair by sample pair
+    unsigned long long yuv420_list_frames_vec = 0, yuv420_list_frames_bytes = 0;   // statistics "yuv420_list_frames_vec" / "yuv420_list_frames_bytes": FRAMES of
+                                                                        // mi_*_yuv420_frames_dev calls whose layout change took the 16-byte / the byte path
 };
 
 namespace {

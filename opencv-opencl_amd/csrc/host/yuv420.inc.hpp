@@ -1,5 +1,5 @@
 // yuv420.inc.hpp -- 8-bit 4:2:0 frames whose sides say where their planes lie (mi_*_yuv420*): I420 / YV12 / NV12 in, any of them out:
-// checks, chunking, the two device entry points and the two host forms, extern "C"
+// checks, chunking, the two device entry points and the two host forms, extern "C"  (the frame-list form: yuv420_frames.inc.hpp)
 // Included by ../mi_lumaeq.hip behind bgr_nv12_frames.inc.hpp (one translation unit; not a stand-alone header).
 //
 // software decoder (three planes, linesize[3]) -> equalize -> hardware encoder surface (NV12), or the other way round, without plane
@@ -23,20 +23,29 @@ inline size_t yuv420_chroma_row(const mi_yuv420_planes& p, int width)
     return p.chroma == MI_CHROMA_PLANAR ? (size_t)width / 2 : (size_t)width;
 }
 
-// Everything is checked before anything is enqueued.  *work = false: MI_OK with nothing to do.  host: one frame, frame_stride ignored.
-mi_status check_yuv420(mi_ctx* c, const mi_yuv420_planes* in, const mi_yuv420_planes* out, int width, int height, int n_frames,
-                       mi_uv_mode uv_mode, bool host, bool is_clahe, int tiles_x, int tiles_y, bool* work)
+// check_yuv420 in its three parts, in the order it applies them; the list form (yuv420_frames.inc.hpp) applies the first and the last
+// once per call and the middle one per frame.
+// 1. What does not depend on where the planes lie.  *any = false: MI_OK with nothing to do.
+mi_status check_yuv420_call(mi_ctx* c, int in_chroma, int out_chroma, int width, int height, int n_frames, mi_uv_mode uv_mode,
+                            bool is_clahe, int tiles_x, int tiles_y, bool* any)
 {
-    *work = false;
-    if (!in || !out) return fail(c, MI_ERR_BAD_ARG, "null plane descriptor");
-    for (const mi_yuv420_planes* p : {in, out})
-        if (p->chroma != MI_CHROMA_INTERLEAVED && p->chroma != MI_CHROMA_PLANAR)
+    *any = false;
+    for (const int chroma : {in_chroma, out_chroma})
+        if (chroma != MI_CHROMA_INTERLEAVED && chroma != MI_CHROMA_PLANAR)
             return fail(c, MI_ERR_BAD_ARG, "chroma must be MI_CHROMA_INTERLEAVED or MI_CHROMA_PLANAR");
     if (uv_mode != MI_UV_FILL128 && uv_mode != MI_UV_COPY) return fail(c, MI_ERR_BAD_ARG, "bad uv_mode");
     if (width < 0 || height < 0 || n_frames < 0) return fail(c, MI_ERR_BAD_ARG, "negative size");
     if ((width & 1) || (height & 1)) return fail(c, MI_ERR_BAD_ARG, "4:2:0 frames have an even width and an even height");
     if (is_clahe && (tiles_x <= 0 || tiles_y <= 0)) return fail(c, MI_ERR_BAD_ARG, "tile grid must be >= 1x1");
-    if (width == 0 || height == 0 || n_frames == 0) return MI_OK;
+    *any = width != 0 && height != 0 && n_frames != 0;
+    return MI_OK;
+}
+
+// 2. The planes of one frame (of every frame of a batch): pointers, pitches, the planes that may not share an address.
+// same_stride: both sides step from frame to frame alike (host frames, list entries: there is no frame stride).
+mi_status check_yuv420_planes(mi_ctx* c, const mi_yuv420_planes* in, const mi_yuv420_planes* out, int width, mi_uv_mode uv_mode,
+                              bool same_stride)
+{
     const bool copy = uv_mode == MI_UV_COPY, in_planar = in->chroma == MI_CHROMA_PLANAR, out_planar = out->chroma == MI_CHROMA_PLANAR;
     if (!in->y || !out->y) return fail(c, MI_ERR_BAD_ARG, "null Y plane pointer");
     if (!out->c0 || (out_planar && !out->c1)) return fail(c, MI_ERR_BAD_ARG, "null output chroma plane pointer");
@@ -48,7 +57,6 @@ mi_status check_yuv420(mi_ctx* c, const mi_yuv420_planes* in, const mi_yuv420_pl
     const void* ip[3] = {in->y, copy ? in->c0 : nullptr, copy && in_planar ? in->c1 : nullptr};
     const void* op[3] = {out->y, out->c0, out_planar ? out->c1 : nullptr};
     if (op[0] == op[1] || (op[2] && (op[2] == op[0] || op[2] == op[1]))) return fail(c, MI_ERR_BAD_ARG, "two output planes at one address");
-    const bool same_stride = host || in->frame_stride == out->frame_stride;
     for (int o = 0; o < 3; ++o)
         for (int i = 0; i < 3; ++i) {
             if (!op[o] || op[o] != ip[i]) continue;
@@ -57,7 +65,12 @@ mi_status check_yuv420(mi_ctx* c, const mi_yuv420_planes* in, const mi_yuv420_pl
                               (o == 0 ? in->y_pitch == out->y_pitch : in->chroma == out->chroma && in->c_pitch == out->c_pitch);
             if (!same) return fail(c, MI_ERR_BAD_ARG, "an output plane at the address of an input plane that is not exactly the same plane");
         }
-    // the planar forms' limits (check_plane), with their status
+    return MI_OK;
+}
+
+// 3. The planar forms' limits (check_plane), with their status.
+mi_status check_yuv420_limits(mi_ctx* c, int width, int height, bool is_clahe, int tiles_x, int tiles_y)
+{
     if ((long long)width * height > 0x7fffffffLL) return fail(c, MI_ERR_UNSUPPORTED, "width*height must be < 2^31 (OpenCV: int total)");
     if (width > (1 << 24) || height > (1 << 24)) return fail(c, MI_ERR_UNSUPPORTED, "width/height must be <= 2^24");
     if (is_clahe) {
@@ -66,6 +79,20 @@ mi_status check_yuv420(mi_ctx* c, const mi_yuv420_planes* in, const mi_yuv420_pl
         if (tiles_x * tiles_y > kMaxGridY) return fail(c, MI_ERR_UNSUPPORTED, "more than 65535 tiles per frame");
         if (tiles_x + 1 > kMaxPairsLds && height > kMaxGridY) return fail(c, MI_ERR_UNSUPPORTED, "height > 65535 with tiles_x > 62");
     }
+    return MI_OK;
+}
+
+// Everything is checked before anything is enqueued.  *work = false: MI_OK with nothing to do.  host: one frame, frame_stride ignored.
+mi_status check_yuv420(mi_ctx* c, const mi_yuv420_planes* in, const mi_yuv420_planes* out, int width, int height, int n_frames,
+                       mi_uv_mode uv_mode, bool host, bool is_clahe, int tiles_x, int tiles_y, bool* work)
+{
+    *work = false;
+    if (!in || !out) return fail(c, MI_ERR_BAD_ARG, "null plane descriptor");
+    bool any = false;
+    mi_status st = check_yuv420_call(c, in->chroma, out->chroma, width, height, n_frames, uv_mode, is_clahe, tiles_x, tiles_y, &any);
+    if (st || !any) return st;
+    if ((st = check_yuv420_planes(c, in, out, width, uv_mode, host || in->frame_stride == out->frame_stride))) return st;
+    if ((st = check_yuv420_limits(c, width, height, is_clahe, tiles_x, tiles_y))) return st;
     *work = true;
     return MI_OK;
 }

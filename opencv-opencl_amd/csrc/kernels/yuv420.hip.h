@@ -122,25 +122,86 @@ __device__ __forceinline__ void yuv420_plane(const uint8_t* src, long long src_s
     else uv_rows(src, src_step, dst, dst_step, row_bytes, rows, mode, part, nparts);
 }
 
-// grid = (B, frames of the chunk), 256 threads, no LDS.  Every branch below is uniform for the launch (it depends on the job alone).
-__global__ __launch_bounds__(kThreads) void yuv420_chroma_kernel(Yuv420Job j)
+// Whether ONE frame of a layout change moves 16 bytes per access: `shape16` says what the call's shape allows (W % 32 == 0 and both
+// c_pitch multiples of 16), the rest is the frame's own four chroma addresses (the c1 of an interleaved side is handed over as null).
+// The host counts frames with it (host/yuv420_frames.inc.hpp) and the table policy below branches on it: one function, one answer.
+__host__ __device__ __forceinline__ bool yuv420_frame_vec(int shape16, const void* c0_in, const void* c1_in, const void* c0_out,
+                                                          const void* c1_out)
+{
+    return shape16 && (((uintptr_t)c0_in | (uintptr_t)c1_in | (uintptr_t)c0_out | (uintptr_t)c1_out) & 15) == 0;
+}
+
+// Where the chroma of frame f of a launch lives and which path it takes, as StridedBgrNv12 / TableBgrNv12 (bgr_nv12.hip.h) say it for
+// their kernel: the body below is a template on one of these two policies.  The batch entry wraps it with the strided one -- the
+// arithmetic it always had, on the kernel's own argument, every decision the host's for the whole launch.
+struct StridedYuv420 {
+    const Yuv420Job& j;
+    __device__ __forceinline__ uint8_t* in0(long long f) const { return j.in.c0 + f * j.in.frame; }
+    __device__ __forceinline__ uint8_t* in1(long long f) const { return j.in.c1 + f * j.in.frame; }
+    __device__ __forceinline__ uint8_t* out0(long long f) const { return j.out.c0 + f * j.out.frame; }
+    __device__ __forceinline__ uint8_t* out1(long long f) const { return j.out.c1 + f * j.out.frame; }
+    __device__ __forceinline__ int vec(long long) const { return j.vec; }
+    __device__ __forceinline__ int skip0(long long) const { return j.skip0; }
+    __device__ __forceinline__ int skip1(long long) const { return j.skip1; }
+};
+
+// A list of such frames, each with its own chroma addresses (mi_*_yuv420_frames_dev: a software decoder's frame pool, an encoder's
+// surface pool).  The entries travel BY VALUE in the kernel arguments like FrameList -- 64 x 32 B = 2 KiB, read with scalar kernarg
+// loads indexed by the frame's grid coordinate; the Y addresses are not in it (the luma kernels have their own FrameList).  The shape
+// (pitches, width, rows, mode, layouts, flat) is the launch's Yuv420Job, whose addresses and frame strides a table launch ignores, whose
+// vec says what the SHAPE allows and whose skip0 / skip1 are unused: whether frame f moves 16 bytes per access and which of its planes
+// are in place (the same address on both sides: nothing to move under MI_UV_COPY) is decided by its own entry -- per frame, so uniform
+// for a workgroup.  With MI_UV_FILL128 the host hands over null input addresses: no plane is skipped.
+struct Yuv420Frame { uint8_t* c0_in; uint8_t* c1_in; uint8_t* c0_out; uint8_t* c1_out; };      // c0_in / c1_in are only read
+struct Yuv420List { Yuv420Frame f[kFramesPerLaunch]; };
+static_assert(sizeof(Yuv420Frame) == 32, "four addresses an entry");
+struct TableYuv420 {
+    const Yuv420List& l;
+    const Yuv420Job& j;
+    __device__ __forceinline__ uint8_t* in0(long long f) const { return l.f[f].c0_in; }
+    __device__ __forceinline__ uint8_t* in1(long long f) const { return l.f[f].c1_in; }
+    __device__ __forceinline__ uint8_t* out0(long long f) const { return l.f[f].c0_out; }
+    __device__ __forceinline__ uint8_t* out1(long long f) const { return l.f[f].c1_out; }
+    __device__ __forceinline__ int vec(long long f) const
+    {
+        return yuv420_frame_vec(j.vec, l.f[f].c0_in, l.f[f].c1_in, l.f[f].c0_out, l.f[f].c1_out);
+    }
+    __device__ __forceinline__ int skip0(long long f) const { return l.f[f].c0_in == l.f[f].c0_out; }
+    __device__ __forceinline__ int skip1(long long f) const { return l.f[f].c1_in == l.f[f].c1_out; }
+};
+
+// grid = (B, frames of the chunk), 256 threads, no LDS.  Every branch below is uniform for a workgroup: it depends on the job and, with
+// the table policy, on the frame's entry.
+template <class Frames>
+__device__ __forceinline__ void yuv420_chroma_body(const Yuv420Job& j, const Frames& fr)
 {
     const long long f = blockIdx.y;
     const int part = blockIdx.x, nparts = gridDim.x;
-    uint8_t* o0 = j.out.c0 + f * j.out.frame;
-    uint8_t* o1 = j.out.planar ? j.out.c1 + f * j.out.frame : nullptr;
+    uint8_t* o0 = fr.out0(f);
+    uint8_t* o1 = j.out.planar ? fr.out1(f) : nullptr;
     if (j.mode == 0 || j.in.planar == j.out.planar) {               // fill the output's planes, or move rows between equal layouts
-        const uint8_t* i0 = j.mode ? j.in.c0 + f * j.in.frame : nullptr;
-        const uint8_t* i1 = j.mode && j.in.planar ? j.in.c1 + f * j.in.frame : nullptr;
+        const uint8_t* i0 = j.mode ? fr.in0(f) : nullptr;
+        const uint8_t* i1 = j.mode && j.in.planar ? fr.in1(f) : nullptr;
         const long long row_bytes = j.out.planar ? j.width >> 1 : j.width;
-        if (!j.skip0) yuv420_plane(i0, j.in.step, o0, j.out.step, row_bytes, j.rows, j.mode, j.flat, part, nparts);
-        if (j.out.planar && !j.skip1) yuv420_plane(i1, j.in.step, o1, j.out.step, row_bytes, j.rows, j.mode, j.flat, part, nparts);
+        if (!fr.skip0(f)) yuv420_plane(i0, j.in.step, o0, j.out.step, row_bytes, j.rows, j.mode, j.flat, part, nparts);
+        if (j.out.planar && !fr.skip1(f)) yuv420_plane(i1, j.in.step, o1, j.out.step, row_bytes, j.rows, j.mode, j.flat, part, nparts);
     } else if (j.out.planar) {
-        yuv420_relayout<true>(j.in.c0 + f * j.in.frame, j.in.step, o0, o1, j.out.step, j.width, j.rows, j.vec, part, nparts);
+        yuv420_relayout<true>(fr.in0(f), j.in.step, o0, o1, j.out.step, j.width, j.rows, fr.vec(f), part, nparts);
     } else {
-        yuv420_relayout<false>(o0, j.out.step, j.in.c0 + f * j.in.frame, j.in.c1 + f * j.in.frame, j.in.step, j.width, j.rows, j.vec,
-                               part, nparts);
+        yuv420_relayout<false>(o0, j.out.step, fr.in0(f), fr.in1(f), j.in.step, j.width, j.rows, fr.vec(f), part, nparts);
     }
 }
+__global__ __launch_bounds__(kThreads) void yuv420_chroma_kernel(Yuv420Job j)
+{
+    yuv420_chroma_body(j, StridedYuv420{j});
+}
+// the same on a frame list: every walk is grid-stride, so one grid (sized by the shape alone) serves frames of either path
+__global__ __launch_bounds__(kThreads) void yuv420_chroma_frames_kernel(Yuv420Job j, Yuv420List l)
+{
+    yuv420_chroma_body(j, TableYuv420{l, j});
+}
+// 256: the implicit arguments a code object carries behind the explicit ones
+static_assert(sizeof(Yuv420Job) + sizeof(Yuv420List) + 256 <= 4096,
+              "the table and the job of yuv420_chroma_frames_kernel stay below HIP's 4 KiB of kernel arguments");
 
 }  // namespace mi

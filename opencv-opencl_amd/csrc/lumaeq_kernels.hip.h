@@ -34,7 +34,8 @@
 //   kernels/packed422_nv12.hip.h  the pixel-writing stages of packed 4:2:2 in, NV12 out: Y plane + vertically halved chroma in one pass
 //   kernels/nv12_bgr.hip.h         the pixel-writing stages of NV12 in, interleaved BGR / RGB out: LUT apply + decode, CLAHE blend + decode
 //   kernels/bgr_nv12.hip.h         stage 1 of interleaved BGR / RGB in, NV12 out: convert into pitched planes and count the luma written
-//   kernels/yuv420.hip.h           the chroma of 4:2:0 frames between planar (I420 / YV12) and interleaved (NV12) layouts: copy, relayout or fill
+//   kernels/yuv420.hip.h           the chroma of 4:2:0 frames between planar (I420 / YV12) and interleaved (NV12) layouts: copy, relayout or fill,
+//                                  on a batch at a frame stride or on a list of per-frame plane addresses
 #pragma once
 #include "kernels/common.hip.h"
 #include "kernels/equalize.hip.h"

@@ -59,6 +59,7 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_bgr_to_nv12_batch_dev", "mi_clahe_bgr_to_nv12_batch_dev", "mi_equalize_hist_bgr_to_nv12", "mi_clahe_bgr_to_nv12",
     "mi_equalize_hist_bgr_to_nv12_frames_dev", "mi_clahe_bgr_to_nv12_frames_dev",
     "mi_equalize_hist_yuv420_batch_dev", "mi_clahe_yuv420_batch_dev", "mi_equalize_hist_yuv420", "mi_clahe_yuv420",
+    "mi_equalize_hist_yuv420_frames_dev", "mi_clahe_yuv420_frames_dev",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -127,6 +128,19 @@ class Yuv420Planes(C.Structure):
     def yv12(cls, base, width, height):
         b, w, h = _dptr(base), int(width), int(height)
         return cls(b, w, b + w * h + (w // 2) * (h // 2), b + w * h, w // 2, w * h * 3 // 2, CHROMA_PLANAR)
+
+
+class Yuv420FrameDev(C.Structure):
+    """mi_yuv420_frame_dev: one frame of a mi_*_yuv420_frames_dev list, the addresses of its planes on both sides (device pointers).
+    c0 is always the U plane and c1 the V plane (a YV12 frame exchanges the two); an INTERLEAVED side has its UV plane in c0 and its c1
+    is ignored (None); with UV_FILL128 c0_in / c1_in are ignored."""
+    _fields_ = [("y_in", C.c_void_p), ("c0_in", C.c_void_p), ("c1_in", C.c_void_p),
+                ("y_out", C.c_void_p), ("c0_out", C.c_void_p), ("c1_out", C.c_void_p)]
+
+    @classmethod
+    def of(cls, y_in, c0_in, c1_in, y_out, c0_out, c1_out):
+        """the same from torch CUDA tensors, raw device addresses or None"""
+        return cls(*(None if p is None else _dptr(p) for p in (y_in, c0_in, c1_in, y_out, c0_out, c1_out)))
 
 
 _YUV420_FMTS = {"nv12": Yuv420Planes.nv12, "i420": Yuv420Planes.i420, "yv12": Yuv420Planes.yv12}
@@ -242,6 +256,8 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_yuv420_batch_dev.argtypes = [vp, yp, yp, i, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_yuv420.argtypes = [vp, yp, yp, i, i, i]
     L.mi_clahe_yuv420.argtypes = [vp, yp, yp, i, i, i, d, i, i]
+    L.mi_equalize_hist_yuv420_frames_dev.argtypes = [vp, C.POINTER(Yuv420FrameDev), i, i, i, sz, sz, i, sz, sz, i, i, vp]
+    L.mi_clahe_yuv420_frames_dev.argtypes = [vp, C.POINTER(Yuv420FrameDev), i, i, i, sz, sz, i, sz, sz, i, i, d, i, i, vp]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -1006,6 +1022,34 @@ class Context:
         self._chk(self._L.mi_clahe_yuv420_batch_dev(self._h, C.byref(src), C.byref(dst), int(width), int(height), int(n_frames),
                                                   int(uv_mode), float(clip_limit), int(tiles_x), int(tiles_y), stream),
                   "mi_clahe_yuv420_batch_dev")
+
+    @staticmethod
+    def _yuv420_list(frames):
+        """frames: a sequence of Yuv420FrameDev, or a ctypes array of them.  Returns the array and its length."""
+        if isinstance(frames, C.Array):
+            return frames, len(frames)
+        frames = list(frames)
+        arr = (Yuv420FrameDev * max(1, len(frames)))()
+        for k, f in enumerate(frames):
+            arr[k] = f
+        return arr, len(frames)
+
+    def equalize_hist_yuv420_frames_dev(self, frames, width, height, y_in_pitch, c_in_pitch, in_chroma, y_out_pitch, c_out_pitch,
+                                        out_chroma, uv_mode=UV_COPY, stream=0):
+        """mi_equalize_hist_yuv420_frames_dev.  frames: Yuv420FrameDev entries, one per frame, every plane at its own device address (a
+        decoder's frame pool in, an encoder's surface pool out); one shape, one set of pitches and one layout per side for the call."""
+        arr, n = self._yuv420_list(frames)
+        self._chk(self._L.mi_equalize_hist_yuv420_frames_dev(self._h, arr, n, int(width), int(height), int(y_in_pitch), int(c_in_pitch),
+                                                           int(in_chroma), int(y_out_pitch), int(c_out_pitch), int(out_chroma),
+                                                           int(uv_mode), stream), "mi_equalize_hist_yuv420_frames_dev")
+
+    def clahe_yuv420_frames_dev(self, frames, width, height, y_in_pitch, c_in_pitch, in_chroma, y_out_pitch, c_out_pitch, out_chroma,
+                                uv_mode=UV_COPY, clip_limit=2.0, tiles_x=8, tiles_y=8, stream=0):
+        """mi_clahe_yuv420_frames_dev; arguments as equalize_hist_yuv420_frames_dev, plus the CLAHE parameters."""
+        arr, n = self._yuv420_list(frames)
+        self._chk(self._L.mi_clahe_yuv420_frames_dev(self._h, arr, n, int(width), int(height), int(y_in_pitch), int(c_in_pitch),
+                                                   int(in_chroma), int(y_out_pitch), int(c_out_pitch), int(out_chroma), int(uv_mode),
+                                                   float(clip_limit), int(tiles_x), int(tiles_y), stream), "mi_clahe_yuv420_frames_dev")
 
     @staticmethod
     def _yuv420_host(frame, width, height, src_fmt, dst_fmt, out, name):
