@@ -730,6 +730,62 @@ mi_status mi_clahe_yuv420_frames_dev(mi_ctx* ctx, const mi_yuv420_frame_dev* fra
         int width, int height, size_t y_in_pitch, size_t c_in_pitch, int in_chroma,
         size_t y_out_pitch, size_t c_out_pitch, int out_chroma, mi_uv_mode uv_mode,
         double clip_limit, int tiles_x, int tiles_y, void* stream);
+/* mi_*_yuv420_to_bgr*: 4:2:0 frames described by mi_yuv420_planes in -- planar chroma (I420 / YV12: what a software decoder hands
+ * over, ffmpeg yuv420p, libvpx, dav1d) or interleaved (NV12) -- interleaved 8-bit BGR (or RGB) images out, in the pass that equalizes:
+ * software decoder -> model, display or image writer without an interleave of U and V outside the library and without an NV12
+ * intermediate.  In OpenCV terms cv::equalizeHist / CLAHE::apply on the Y plane, then cv::cvtColor(COLOR_YUV2BGR_I420 / _YV12), the
+ * RGB codes for MI_ORDER_RGB.  Y is read twice (histograms, then map), U and V once, 3 bytes per pixel are written: 5.5 B/px.
+ *   input  : `in` is read only during the call.  Frame f has every plane at pointer + f * in->frame_stride: Y, H rows of W bytes at
+ *            y_pitch >= W; PLANAR: c0 = U and c1 = V, each H/2 rows of W/2 bytes at c_pitch >= W/2; INTERLEAVED: c0 = the UV plane, H/2
+ *            rows of W bytes at c_pitch >= W.  c0 is always U and c1 always V: a YV12 caller passes its second chroma plane as c0.
+ *            The input is never written.
+ *   output : as in the NV12 form: frame f at d_out + f * out_frame_stride, H rows of 3*W bytes at out_pitch >= 3*W, B, G, R per pixel
+ *            (MI_ORDER_BGR) or R, G, B (MI_ORDER_RGB).  Only the 3*W bytes of each output row are written: not the pitch padding, not
+ *            the gap between frames.  There is no in-place form.
+ * Bytes: per frame byte for byte what mi_equalize_hist_nv12_to_bgr_batch_dev / mi_clahe_nv12_to_bgr_batch_dev writes for the same
+ *   pixels with U and V interleaved, and what the two-call composition mi_*_yuv420_batch_dev(I420 -> NV12, MI_UV_COPY) followed by
+ *   mi_cvt_color_420_u8_batch_dev(..., MI_COLOR_YUV2BGR_NV12) writes (8.5 B/px and a tight NV12 batch in between): the same
+ *   clahe_fp_contract option, the same REFLECT_101 padding when the tile grid does not divide the frame, the planar forms' own limits on
+ *   sizes and tile grids with their statuses.  Never the fused equalizeHist kernel nor the single-launch histogram + LUT kernel, as in
+ *   the NV12 form.
+ * in->chroma == MI_CHROMA_INTERLEAVED: the call IS the NV12 form's (d_y = in->y, d_uv = in->c0, uv_pitch = in->c_pitch,
+ *   in_frame_stride = in->frame_stride; in->c1 ignored): the same kernels, the same alignment rule (multiples of 16 throughout), the
+ *   same "nv12_bgr_onepass" / "nv12_bgr_twopass" counters; none of the counters below moves.
+ * Alignment (MI_CHROMA_PLANAR): none is required of any pointer, pitch or stride.  A call moves 16 x 2 pixel groups per lane when
+ *   W % 16 == 0; in->y, in->y_pitch, in->frame_stride, d_out, out_pitch and out_frame_stride are multiples of 16; and in->c0, in->c1
+ *   and in->c_pitch are multiples of 8 (not 16: a lane makes two 16-byte Y loads, one 8-byte U load, one 8-byte V load and six 16-byte
+ *   stores).  Otherwise it processes 2 x 2 pixel blocks with byte accesses -- slower, the same bytes out.  CLAHE maps and converts in
+ *   one kernel when that rule holds and the shape is the NV12 form's one-pass shape (the tile grid divides the frame, tile width a
+ *   multiple of 16, tiles_x <= 14, clahe_fp_contract off); any other call runs the planar CLAHE into scratch Y planes of the context
+ *   and then the conversion alone: the same bytes in one more pass.
+ * Counters (mi_ctx_get_stat), PLANAR-input calls only: "yuv420_bgr_onepass" / "yuv420_bgr_twopass", one count per call (equalizeHist
+ *   always counts as one-pass, as in the NV12 form); "yuv420_bgr_vec" / "yuv420_bgr_bytes", one count per call by the walk the
+ *   pixel-writing kernel took.  Every planar call with work to do moves exactly one counter of each pair; a call that returns an error
+ *   or has a zero size moves none.
+ * Launches run in chunks of 256 frames and are charged to the existing profiling slots by role, as the NV12 form's.  Stream rules,
+ *   MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of the same shape
+ *   as the other batched device forms.
+ * mi_equalize_hist_yuv420_to_bgr / mi_clahe_yuv420_to_bgr: ONE frame with `in` holding HOST pointers at any address and pitch
+ *   (frame_stride is ignored), a CV_8UC3 image at out_step >= 3*W out.  Synchronous; the planes are staged like mi_*_yuv420's (planes
+ *   in pinned memory that are tight are DMA'd as they are, everything else goes through the context's pinned staging) and the image
+ *   comes back like mi_*_nv12_to_bgr's.  On the device the frame is tight with every plane at a 16-byte aligned offset, so a
+ *   W % 16 == 0 frame takes the 16 x 2 groups.  Whatever the call returns, no copy on the caller's memory is in flight any more when
+ *   it returns.  W*H beyond what mi_*_nv12_to_bgr accepts: MI_ERR_UNSUPPORTED.
+ * Errors, MI_ERR_BAD_ARG: a null ctx or `in`; a `chroma` other than the two values; an `order` other than the two; a negative size; an
+ *   odd width or an odd height (refused even when another size is 0, as in the sibling forms); tiles <= 0; a null in->y, in->c0 or
+ *   d_out; a null in->c1 on a PLANAR input; y_pitch < W; a c_pitch below its row (W interleaved, W/2 planar); out_pitch < 3*W; d_out
+ *   equal to any input plane pointer of the call.  Any other overlap: undefined, not checked.  width, height or n_frames of 0: MI_OK,
+ *   nothing written.  Sizes and tile grids the planar forms refuse: the status they give (MI_ERR_UNSUPPORTED), nothing written.
+ *   Nothing is enqueued unless every check passes. */
+mi_status mi_equalize_hist_yuv420_to_bgr_batch_dev(mi_ctx* ctx, const mi_yuv420_planes* in, void* d_out, size_t out_pitch,
+        size_t out_frame_stride, int width, int height, int n_frames, int order, void* stream);
+mi_status mi_clahe_yuv420_to_bgr_batch_dev(mi_ctx* ctx, const mi_yuv420_planes* in, void* d_out, size_t out_pitch,
+        size_t out_frame_stride, int width, int height, int n_frames, int order,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
+mi_status mi_equalize_hist_yuv420_to_bgr(mi_ctx* ctx, const mi_yuv420_planes* in, uint8_t* out, size_t out_step,
+        int width, int height, int order);
+mi_status mi_clahe_yuv420_to_bgr(mi_ctx* ctx, const mi_yuv420_planes* in, uint8_t* out, size_t out_step,
+        int width, int height, int order, double clip_limit, int tiles_x, int tiles_y);
 
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at

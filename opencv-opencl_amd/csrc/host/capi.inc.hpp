@@ -349,7 +349,10 @@ mi_status mi_ctx_synchronize(mi_ctx* c, void* stream)
 // planar CLAHE into scratch and the conversion after it), "yuv420_chroma_vec" / "yuv420_chroma_bytes" (mi_*_yuv420* calls whose chroma
 // launch moved 16 bytes per access / changed the layout with byte accesses; a call that launched no chroma kernel counts in neither),
 // "yuv420_list_frames_vec" / "yuv420_list_frames_bytes" (FRAMES of mi_*_yuv420_frames_dev calls that changed the layout under MI_UV_COPY
-// with 16-byte / with byte accesses, each by its own addresses; list calls do not touch the two per-call counters before them).
+// with 16-byte / with byte accesses, each by its own addresses; list calls do not touch the two per-call counters before them),
+// "yuv420_bgr_onepass" / "yuv420_bgr_twopass" and "yuv420_bgr_vec" / "yuv420_bgr_bytes" (PLANAR-input mi_*_yuv420_to_bgr* calls: mapped and
+// converted in one kernel / planar CLAHE into scratch first; pixel-writing kernel on 16 x 2 pixel groups / on 2 x 2 blocks with byte
+// accesses.  Every such call with work to do moves one counter of each pair; an INTERLEAVED input counts in the nv12_bgr_* pair).
 mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
 {
     ENTER(c);
@@ -379,6 +382,10 @@ mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
     if (!strcmp(name, "yuv420_chroma_bytes")) { *out = c->yuv420_chroma_bytes; return MI_OK; }
     if (!strcmp(name, "yuv420_list_frames_vec")) { *out = c->yuv420_list_frames_vec; return MI_OK; }
     if (!strcmp(name, "yuv420_list_frames_bytes")) { *out = c->yuv420_list_frames_bytes; return MI_OK; }
+    if (!strcmp(name, "yuv420_bgr_onepass")) { *out = c->yuv420_bgr_onepass; return MI_OK; }
+    if (!strcmp(name, "yuv420_bgr_twopass")) { *out = c->yuv420_bgr_twopass; return MI_OK; }
+    if (!strcmp(name, "yuv420_bgr_vec")) { *out = c->yuv420_bgr_vec; return MI_OK; }
+    if (!strcmp(name, "yuv420_bgr_bytes")) { *out = c->yuv420_bgr_bytes; return MI_OK; }
     return fail(c, MI_ERR_BAD_ARG, "unknown stat");
 }
 

@@ -164,6 +164,10 @@ struct mi_ctx {
                                                                         // launch moved 16 bytes per access / changed the layout sample pair by sample pair
     unsigned long long yuv420_list_frames_vec = 0, yuv420_list_frames_bytes = 0;   // statistics "yuv420_list_frames_vec" / "yuv420_list_frames_bytes": FRAMES of
                                                                         // mi_*_yuv420_frames_dev calls whose layout change took the 16-byte / the byte path
+    unsigned long long yuv420_bgr_onepass = 0, yuv420_bgr_twopass = 0;  // statistics "yuv420_bgr_onepass" / "yuv420_bgr_twopass": PLANAR-input mi_*_yuv420_to_bgr*
+                                                                        // calls, as the nv12_bgr_* pair counts the NV12 form's
+    unsigned long long yuv420_bgr_vec = 0, yuv420_bgr_bytes = 0;        // statistics "yuv420_bgr_vec" / "yuv420_bgr_bytes": the same calls by the walk their
+                                                                        // pixel-writing kernel took (16 x 2 pixel groups / 2 x 2 blocks with byte accesses)
 };
 
 namespace {

@@ -36,6 +36,8 @@
 //   kernels/bgr_nv12.hip.h         stage 1 of interleaved BGR / RGB in, NV12 out: convert into pitched planes and count the luma written
 //   kernels/yuv420.hip.h           the chroma of 4:2:0 frames between planar (I420 / YV12) and interleaved (NV12) layouts: copy, relayout or fill,
 //                                  on a batch at a frame stride or on a list of per-frame plane addresses
+//   kernels/yuv420_bgr.hip.h       the pixel-writing stages of planar 4:2:0 (I420 / YV12) in, interleaved BGR / RGB out: those of nv12_bgr.hip.h
+//                                  with the chroma loaded from two planes and zipped in registers
 #pragma once
 #include "kernels/common.hip.h"
 #include "kernels/equalize.hip.h"
@@ -51,3 +53,4 @@
 #include "kernels/nv12_bgr.hip.h"
 #include "kernels/bgr_nv12.hip.h"
 #include "kernels/yuv420.hip.h"
+#include "kernels/yuv420_bgr.hip.h"

@@ -553,6 +553,24 @@ inline void claheYUV420(const YUV420View& in, const YUV420View& out, int width, 
     detail::check(c, mi_clahe_yuv420(c, &a, &b, width, height, (mi_uv_mode)uvMode, clipLimit, tiles.width, tiles.height),
                   "mi_clahe_yuv420");
 }
+// The same frame views in, an interleaved CV_8UC3 image (BGR, or RGB) out in the pass that equalizes: cv::equalizeHist / CLAHE::apply on
+// the Y plane + cv::cvtColor(COLOR_YUV2BGR_I420 / _YV12 / _NV12) without an interleave of U and V and without the frame in between: a
+// software decoder's three planes -> a model, a display or an image writer.  `out`: H rows of 3*W bytes at outStep >= 3*W.
+inline void equalizeHistYUV420ToBGR(const YUV420View& in, unsigned char* out, size_t outStep, int width, int height,
+                                    ChannelOrder order = ORDER_BGR)
+{
+    mi_ctx* c = detail::thread_ctx();
+    const mi_yuv420_planes a = in.planes();
+    detail::check(c, mi_equalize_hist_yuv420_to_bgr(c, &a, out, outStep, width, height, (int)order), "mi_equalize_hist_yuv420_to_bgr");
+}
+inline void claheYUV420ToBGR(const YUV420View& in, unsigned char* out, size_t outStep, int width, int height, double clipLimit,
+                             Size tiles, ChannelOrder order = ORDER_BGR)
+{
+    mi_ctx* c = detail::thread_ctx();
+    const mi_yuv420_planes a = in.planes();
+    detail::check(c, mi_clahe_yuv420_to_bgr(c, &a, out, outStep, width, height, (int)order, clipLimit, tiles.width, tiles.height),
+                  "mi_clahe_yuv420_to_bgr");
+}
 
 // BASELINE.json config 5 read literally: cvtColor(COLOR_YUV2BGR_NV12) -> split -> equalizeHist on B, G and R -> merge ->
 // cvtColor(COLOR_BGR2YUV_I420) + U/V interleave, NV12 in -> NV12 out in one call (no file of the reference does this;

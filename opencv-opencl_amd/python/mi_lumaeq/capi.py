@@ -60,6 +60,7 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_bgr_to_nv12_frames_dev", "mi_clahe_bgr_to_nv12_frames_dev",
     "mi_equalize_hist_yuv420_batch_dev", "mi_clahe_yuv420_batch_dev", "mi_equalize_hist_yuv420", "mi_clahe_yuv420",
     "mi_equalize_hist_yuv420_frames_dev", "mi_clahe_yuv420_frames_dev",
+    "mi_equalize_hist_yuv420_to_bgr_batch_dev", "mi_clahe_yuv420_to_bgr_batch_dev", "mi_equalize_hist_yuv420_to_bgr", "mi_clahe_yuv420_to_bgr",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -258,6 +259,10 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_yuv420.argtypes = [vp, yp, yp, i, i, i, d, i, i]
     L.mi_equalize_hist_yuv420_frames_dev.argtypes = [vp, C.POINTER(Yuv420FrameDev), i, i, i, sz, sz, i, sz, sz, i, i, vp]
     L.mi_clahe_yuv420_frames_dev.argtypes = [vp, C.POINTER(Yuv420FrameDev), i, i, i, sz, sz, i, sz, sz, i, i, d, i, i, vp]
+    L.mi_equalize_hist_yuv420_to_bgr_batch_dev.argtypes = [vp, yp, vp, sz, sz, i, i, i, i, vp]
+    L.mi_clahe_yuv420_to_bgr_batch_dev.argtypes = [vp, yp, vp, sz, sz, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_yuv420_to_bgr.argtypes = [vp, yp, vp, sz, i, i, i]
+    L.mi_clahe_yuv420_to_bgr.argtypes = [vp, yp, vp, sz, i, i, i, d, i, i]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -1079,6 +1084,50 @@ class Context:
         a, b, out = self._yuv420_host(frame, width, height, src_fmt, dst_fmt, out, "clahe_yuv420")
         self._chk(self._L.mi_clahe_yuv420(self._h, C.byref(a), C.byref(b), int(width), int(height), int(uv_mode), float(clip_limit),
                                         int(tiles_x), int(tiles_y)), "mi_clahe_yuv420")
+        return out
+
+    # ---- 4:2:0 frames (I420 / YV12 planes, or NV12) in, interleaved BGR / RGB out in the pass that maps the luma ----
+    def equalize_hist_yuv420_to_bgr_batch_dev(self, src, d_out, width, height, n_frames, order=ORDER_BGR, out_pitch=None, out_frame=None,
+                                              stream=0):
+        """mi_equalize_hist_yuv420_to_bgr_batch_dev.  src: a Yuv420Planes holding device addresses (Yuv420Planes.i420 / .yv12 / .nv12 for
+        tight batches, the fields themselves for pitched or separately allocated planes); d_out: the images (a torch tensor or a raw
+        address).  The tight output is the default: out_pitch 3*W, out_frame = out_pitch * H."""
+        op = 3 * int(width) if out_pitch is None else int(out_pitch)
+        fo = op * int(height) if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_equalize_hist_yuv420_to_bgr_batch_dev(self._h, C.byref(src), _dptr(d_out), op, fo, int(width), int(height),
+                                                                 int(n_frames), int(order), stream),
+                  "mi_equalize_hist_yuv420_to_bgr_batch_dev")
+
+    def clahe_yuv420_to_bgr_batch_dev(self, src, d_out, width, height, n_frames, order=ORDER_BGR, clip_limit=2.0, tiles_x=8, tiles_y=8,
+                                      out_pitch=None, out_frame=None, stream=0):
+        """mi_clahe_yuv420_to_bgr_batch_dev; arguments as equalize_hist_yuv420_to_bgr_batch_dev, plus the CLAHE parameters."""
+        op = 3 * int(width) if out_pitch is None else int(out_pitch)
+        fo = op * int(height) if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_clahe_yuv420_to_bgr_batch_dev(self._h, C.byref(src), _dptr(d_out), op, fo, int(width), int(height),
+                                                         int(n_frames), int(order), float(clip_limit), int(tiles_x), int(tiles_y), stream),
+                  "mi_clahe_yuv420_to_bgr_batch_dev")
+
+    def _yuv420_bgr_host(self, frame, width, height, src_fmt, out, name):
+        if src_fmt not in _YUV420_FMTS:
+            raise MiError(1, name, 'src_fmt must be "nv12", "i420" or "yv12"')
+        out, step = self._nv12_bgr_host(frame, width, height, out, name)
+        return _YUV420_FMTS[src_fmt](frame.ctypes.data, width, height), out, step
+
+    def equalize_hist_yuv420_to_bgr(self, frame: np.ndarray, width: int, height: int, src_fmt: str, order: int = ORDER_BGR,
+                                    out: np.ndarray | None = None) -> np.ndarray:
+        """mi_equalize_hist_yuv420_to_bgr on a tight host frame of W*H*3/2 bytes whose chroma lies as src_fmt in {"nv12", "i420", "yv12"}
+        says: the H x W x 3 image out -- `out` when given (a view with padded rows included), else a new tight array."""
+        a, out, step = self._yuv420_bgr_host(frame, int(width), int(height), src_fmt, out, "equalize_hist_yuv420_to_bgr")
+        self._chk(self._L.mi_equalize_hist_yuv420_to_bgr(self._h, C.byref(a), out.ctypes.data, step, int(width), int(height), int(order)),
+                  "mi_equalize_hist_yuv420_to_bgr")
+        return out
+
+    def clahe_yuv420_to_bgr(self, frame: np.ndarray, width: int, height: int, src_fmt: str, order: int = ORDER_BGR,
+                            clip_limit: float = 2.0, tiles_x: int = 8, tiles_y: int = 8, out: np.ndarray | None = None) -> np.ndarray:
+        """mi_clahe_yuv420_to_bgr; arguments as equalize_hist_yuv420_to_bgr, plus the CLAHE parameters."""
+        a, out, step = self._yuv420_bgr_host(frame, int(width), int(height), src_fmt, out, "clahe_yuv420_to_bgr")
+        self._chk(self._L.mi_clahe_yuv420_to_bgr(self._h, C.byref(a), out.ctypes.data, step, int(width), int(height), int(order),
+                                               float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_yuv420_to_bgr")
         return out
 
     # ---- colour-domain neighbours (N3) ----

@@ -2,7 +2,8 @@
 (multiples of 16 and not) with random origins, wide CLAHE grids at sizes where the per-segment float tables apply, large batches of small
 tiles (several tiles per histogram workgroup), 16-bit CLAHE at random value ranges, the 4:2:0 codes at random aligned / unaligned sizes, NV12 in / BGR out
 at random pitched layouts (aligned and not) and tile grids on both sides of its one-pass conditions, as a batch and as a frame list
-(random order, every image at its own offset).
+(random order, every image at its own offset), and the same pixels from planar chroma (I420 / YV12 in, BGR out) at chroma layouts that are
+multiples of 8 or of 1.
     python tools/stress_random.py [seconds] [seed] [option=value ...]        prints a line every ~15 s, exits non-zero on the first mismatch"""
 import sys, time
 sys.path.insert(0, "opencv-opencl_amd/python"); sys.path.insert(0, ".")
@@ -14,7 +15,7 @@ rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 ctx = mi_lumaeq.Context(0)
 for kv in sys.argv[3:]:                                          # name=value options for the whole run, e.g. clahe16_wide=2 (mid kernel always launched)
     k_, v_ = kv.split("="); ctx.set_option(k_, int(v_)); print("option", k_, "=", v_, flush=True)
-t0 = last = time.time(); n = {"roi": 0, "grid": 0, "small": 0, "c16": 0, "420": 0, "nv12": 0, "nv12bgr": 0}
+t0 = last = time.time(); n = {"roi": 0, "grid": 0, "small": 0, "c16": 0, "420": 0, "nv12": 0, "nv12bgr": 0, "yuv420bgr": 0}
 def dev(a): return xfer.to_device(np.ascontiguousarray(a))
 def fail(what, *info):
     print("MISMATCH", what, info, flush=True); sys.exit(1)
@@ -125,6 +126,28 @@ while time.time() - t0 < budget:
         if not np.array_equal(out, want): fail("nv12bgr list", w, h, nf, op, order, clip, tx, ty, al, yp, up, opi, off, gap, fgap, ooff, perm, jit, np.flatnonzero(out != want)[:8])
         if not np.array_equal(xfer.to_host(d_in), img): fail("nv12bgr wrote its input", w, h, nf, op)
         n["nv12bgr"] += 1
+        # the same pixels from planar chroma (I420, or YV12: the two planes at exchanged addresses) into the same output layout: chroma
+        # pitches, gaps and offsets multiples of 8 where the NV12 layout had 16 (the 16 x 2 groups still apply), or of 1
+        ca = 8 if al == 16 else 1
+        def cpad(v): return (v + ca - 1) // ca * ca + ca * int(rng.integers(0, 40 // ca + 1))
+        cp, g0, g1 = cpad(w // 2), cpad(0), cpad(0); csz = cp * (h // 2); yv12 = bool(rng.integers(0, 2))
+        a_off = yp * h + g0; b_off = a_off + csz + g1; pfi = b_off + csz; pfi += (-pfi) % al + al * int(rng.integers(0, 3))
+        pimg = np.full(off + pfi * nf + 64, 0x5A, np.uint8)
+        u_off, v_off = (b_off, a_off) if yv12 else (a_off, b_off)
+        for f in range(nf):
+            o = off + f * pfi; uvr = fr[f, w * h:].reshape(h // 2, w)
+            pimg[o: o + yp * h].reshape(h, yp)[:, :w] = fr[f, : w * h].reshape(h, w)
+            pimg[o + u_off: o + u_off + csz].reshape(h // 2, cp)[:, : w // 2] = uvr[:, 0::2]
+            pimg[o + v_off: o + v_off + csz].reshape(h // 2, cp)[:, : w // 2] = uvr[:, 1::2]
+        d_pin = dev(pimg); d_out3 = torch.full((ooff + fo * nf + 64,), 0x5A, dtype=torch.uint8, device="cuda"); b = d_pin.data_ptr() + off
+        pl = mi_lumaeq.Yuv420Planes(b, yp, b + u_off, b + v_off, cp, pfi, mi_lumaeq.CHROMA_PLANAR)
+        pa = (pl, d_out3.data_ptr() + ooff, w, h, nf, order); pkw = dict(out_pitch=opi, out_frame=fo)
+        if op == 0: ctx.equalize_hist_yuv420_to_bgr_batch_dev(*pa, **pkw)
+        else: ctx.clahe_yuv420_to_bgr_batch_dev(*pa, clip, tx, ty, **pkw)
+        ctx.synchronize()
+        if not torch.equal(d_out3, d_out): fail("yuv420bgr", w, h, nf, op, order, clip, tx, ty, al, yp, cp, g0, g1, pfi, yv12, opi, off, ooff)
+        if not np.array_equal(xfer.to_host(d_pin), pimg): fail("yuv420bgr wrote its input", w, h, nf, op)
+        n["yuv420bgr"] += 1
     else:           # 4:2:0 codes
         w, h = int(rng.integers(1, 60)) * (16 if rng.integers(0, 2) else 2), int(rng.integers(1, 40)) * 2
         bgr = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
