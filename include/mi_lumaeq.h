@@ -786,6 +786,59 @@ mi_status mi_equalize_hist_yuv420_to_bgr(mi_ctx* ctx, const mi_yuv420_planes* in
         int width, int height, int order);
 mi_status mi_clahe_yuv420_to_bgr(mi_ctx* ctx, const mi_yuv420_planes* in, uint8_t* out, size_t out_step,
         int width, int height, int order, double clip_limit, int tiles_x, int tiles_y);
+/* mi_*_yuv420_to_bgr_frames_dev: the same conversion on a LIST of device frames, each at its own four addresses -- a software decoder's
+ * frame pool in (every frame three separately allocated, pitched planes: data[0..2], linesize[0..2]), a pool of CV_8UC3 images out.
+ * The batch form needs the whole batch in one allocation at a constant frame stride; one n_frames = 1 batch call per frame costs a
+ * launch sequence per frame, and repacking a pool into a batch and copying the images out moves 1.5 + 3 bytes per pixel more each way.
+ * `frames` is a host array of n_frames entries, read only during the call; the pointers in it are device pointers on the context's
+ * device.
+ * Shape: all frames of one call share width, height, order, chroma and the three pitches (bytes between rows); each has its own
+ *   addresses.  There are no per-frame pitches.
+ *   y  : H rows of W bytes at y_pitch >= W
+ *   c0, c1 (MI_CHROMA_PLANAR): the U and the V plane, each H/2 rows of W/2 bytes at c_pitch >= W/2 (both planes share the pitch).  c0 is
+ *        always U and c1 always V: a YV12 caller exchanges the two addresses.
+ *   out: H rows of 3*W bytes at out_pitch >= 3*W -- B, G, R per pixel (MI_ORDER_BGR) or R, G, B (MI_ORDER_RGB)
+ * Bytes: per frame the output is byte for byte what mi_*_yuv420_to_bgr_batch_dev writes for that frame alone at the same pitches --
+ *   cv::equalizeHist / CLAHE::apply on Y, then cvtColor(COLOR_YUV2BGR_I420 / _YV12, or the RGB codes); the clahe_fp_contract option is
+ *   honoured, REFLECT_101 padding applies when the tile grid does not divide the frame, the limits on sizes and tile grids are the
+ *   batch form's, with the same statuses.
+ * Writes: only the 3*W bytes of each output row are written, not the pitch padding; the input planes are never written.
+ * chroma == MI_CHROMA_INTERLEAVED: the call IS mi_*_nv12_to_bgr_frames_dev on {y, c0, out} with uv_pitch = c_pitch (c0 = the UV plane,
+ *   H/2 rows of W bytes at c_pitch >= W; c1 is ignored and may be NULL): that form's checks, its kernels, its rule of multiples of 16
+ *   throughout and its "nv12_bgr_onepass" / "nv12_bgr_twopass" counters; none of the counters below moves.
+ * Alignment (MI_CHROMA_PLANAR): none is required of any address or pitch.  The per-frame alignment decides the access width: the
+ *   shape allows 16 x 2 pixel groups when W % 16 == 0, y_pitch and out_pitch are multiples of 16 and c_pitch is a multiple of 8 (not
+ *   16: a lane makes two 16-byte Y loads, one 8-byte U load, one 8-byte V load and six 16-byte stores); a frame then takes the groups
+ *   when its y and out are multiples of 16 and its c0 and c1 multiples of 8, and any other frame of the same call processes 2 x 2
+ *   pixel blocks with byte accesses while its neighbours stay vectorised -- slower, the same bytes out.  equalizeHist always maps the
+ *   luma and converts in one kernel.  CLAHE does so when the shape is the batch form's one-pass shape (the tile grid divides the frame,
+ *   tile width a multiple of 16, tiles_x <= 14, clahe_fp_contract off), the shape rule above holds and every frame of the call
+ *   satisfies the address rule; otherwise the whole call runs the planar CLAHE into scratch Y planes of the context and converts from
+ *   there: the same bytes in one more pass.  (In that fallback the Y address the rule sees is the scratch plane's, which is aligned;
+ *   the pitches are still the caller's.)
+ * Counters (mi_ctx_get_stat), PLANAR lists only: "yuv420_bgr_onepass" / "yuv420_bgr_twopass" count the calls of the list form too,
+ *   one count a call (equalizeHist always counts as one-pass).  "yuv420_bgr_list_frames_vec" / "yuv420_bgr_list_frames_bytes" count the
+ *   FRAMES (not calls) of list calls by the walk their pixel-writing kernel took: 16 x 2 groups / 2 x 2 blocks.  "yuv420_bgr_vec" /
+ *   "yuv420_bgr_bytes" are not touched by list calls.  A call that returns an error or has nothing to do moves none.
+ * Launches are charged to the same profiling slots as the batch form, per chunk of 64 frames of the list.
+ * Overlap: there is no in-place form.  MI_ERR_BAD_ARG when the rows of a frame's image meet the rows of its own Y, U or V plane
+ *   (compared as address ranges).  Input planes are not compared with each other: the U and V rows may lie side by side in one pitched
+ *   plane (c1 = c0 + W/2, c_pitch = W).  The same input planes may appear in several entries (inputs are only read).  Outputs that
+ *   overlap each other or ANOTHER frame's planes give undefined results and are not checked.
+ * Errors, MI_ERR_BAD_ARG: a null ctx; a null `frames` with n_frames > 0; a null y, c0 or out in any entry; a null c1 in any entry on a
+ *   PLANAR input; a `chroma` other than the two values; an `order` other than the two; a negative size; an odd width or an odd height
+ *   (refused even when another size is 0, as in the batch form); y_pitch < W; a c_pitch below its row (W interleaved, W/2 planar);
+ *   out_pitch < 3*W; tiles <= 0; the overlap above.  Sizes and tile grids the planar forms refuse: the status they give
+ *   (MI_ERR_UNSUPPORTED).  width, height or n_frames of 0: MI_OK, nothing written.  Nothing is enqueued unless every frame passes the
+ *   checks: a bad last entry leaves the first frames' outputs untouched.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of
+ *   the same shape as the other device list forms; a captured graph holds the addresses it was captured with. */
+typedef struct mi_yuv420_bgr_frame_dev { const void* y; const void* c0; const void* c1; void* out; } mi_yuv420_bgr_frame_dev;  /* 32 bytes on LP64 */
+mi_status mi_equalize_hist_yuv420_to_bgr_frames_dev(mi_ctx* ctx, const mi_yuv420_bgr_frame_dev* frames, int n_frames,
+        int width, int height, size_t y_pitch, size_t c_pitch, int chroma, size_t out_pitch, int order, void* stream);
+mi_status mi_clahe_yuv420_to_bgr_frames_dev(mi_ctx* ctx, const mi_yuv420_bgr_frame_dev* frames, int n_frames,
+        int width, int height, size_t y_pitch, size_t c_pitch, int chroma, size_t out_pitch, int order,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
 
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at

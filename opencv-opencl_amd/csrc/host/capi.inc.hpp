@@ -352,7 +352,10 @@ mi_status mi_ctx_synchronize(mi_ctx* c, void* stream)
 // with 16-byte / with byte accesses, each by its own addresses; list calls do not touch the two per-call counters before them),
 // "yuv420_bgr_onepass" / "yuv420_bgr_twopass" and "yuv420_bgr_vec" / "yuv420_bgr_bytes" (PLANAR-input mi_*_yuv420_to_bgr* calls: mapped and
 // converted in one kernel / planar CLAHE into scratch first; pixel-writing kernel on 16 x 2 pixel groups / on 2 x 2 blocks with byte
-// accesses.  Every such call with work to do moves one counter of each pair; an INTERLEAVED input counts in the nv12_bgr_* pair).
+// accesses.  Every such call with work to do moves one counter of each pair; an INTERLEAVED input counts in the nv12_bgr_* pair),
+// "yuv420_bgr_list_frames_vec" / "yuv420_bgr_list_frames_bytes" (FRAMES of PLANAR mi_*_yuv420_to_bgr_frames_dev calls whose pixels were
+// written on 16 x 2 pixel groups / on 2 x 2 blocks, each by its own addresses; list calls move the onepass / twopass pair once a call
+// and do not touch "yuv420_bgr_vec" / "yuv420_bgr_bytes").
 mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
 {
     ENTER(c);
@@ -386,6 +389,8 @@ mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
     if (!strcmp(name, "yuv420_bgr_twopass")) { *out = c->yuv420_bgr_twopass; return MI_OK; }
     if (!strcmp(name, "yuv420_bgr_vec")) { *out = c->yuv420_bgr_vec; return MI_OK; }
     if (!strcmp(name, "yuv420_bgr_bytes")) { *out = c->yuv420_bgr_bytes; return MI_OK; }
+    if (!strcmp(name, "yuv420_bgr_list_frames_vec")) { *out = c->yuv420_bgr_list_frames_vec; return MI_OK; }
+    if (!strcmp(name, "yuv420_bgr_list_frames_bytes")) { *out = c->yuv420_bgr_list_frames_bytes; return MI_OK; }
     return fail(c, MI_ERR_BAD_ARG, "unknown stat");
 }
 

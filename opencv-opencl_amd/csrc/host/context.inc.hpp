@@ -168,6 +168,8 @@ struct mi_ctx {
                                                                         // calls, as the nv12_bgr_* pair counts the NV12 form's
     unsigned long long yuv420_bgr_vec = 0, yuv420_bgr_bytes = 0;        // statistics "yuv420_bgr_vec" / "yuv420_bgr_bytes": the same calls by the walk their
                                                                         // pixel-writing kernel took (16 x 2 pixel groups / 2 x 2 blocks with byte accesses)
+    unsigned long long yuv420_bgr_list_frames_vec = 0, yuv420_bgr_list_frames_bytes = 0;   // statistics "yuv420_bgr_list_frames_vec" / "yuv420_bgr_list_frames_bytes":
+                                                                        // FRAMES of PLANAR mi_*_yuv420_to_bgr_frames_dev calls by that walk, each by its own addresses
 };
 
 namespace {

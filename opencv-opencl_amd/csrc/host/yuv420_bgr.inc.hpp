@@ -66,15 +66,24 @@ Yuv420BgrJob yuv420_bgr_job(const Yuv420BgrArgs& a, int f0, const uint8_t* y, si
     return j;
 }
 
-// LUT apply + decode (luts != nullptr, MI_K_LUT_APPLY) or the decode alone (MI_K_COLOR): the grid of launch_nv12_to_bgr
-mi_status launch_yuv420_to_bgr(mi_ctx* c, hipStream_t s, const Yuv420BgrJob& j, int nf, int order, const uint8_t* luts)
+// LUT apply + decode (luts != nullptr, MI_K_LUT_APPLY) or the decode alone (MI_K_COLOR): the grid of launch_nv12_to_bgr.  `fl`: a
+// chunk of a frame list (at most kFramesPerLaunch frames, yuv420_bgr_frames.inc.hpp): the same grid on the *_frames_kernel entry; `j`
+// then carries the shape, and j.vec what the shape allows.
+mi_status launch_yuv420_to_bgr(mi_ctx* c, hipStream_t s, const Yuv420BgrJob& j, int nf, int order, const uint8_t* luts,
+                               const Yuv420BgrList* fl = nullptr)
 {
     const long long px = (long long)j.width * j.height;
     int B = blocks_per_frame(c, px * 9 / 4, j.height / 2, nf, 2048);
     const long long items = j.vec ? px / 32 : px / 4;
     B = (int)std::max<long long>(1, std::min<long long>(B, (items + kThreads - 1) / kThreads));
     const dim3 grid(B, nf), block(kThreads);
-    if (luts) {
+    if (fl && luts) {
+        if (order == MI_ORDER_RGB) LAUNCH(c, s, MI_K_LUT_APPLY, (yuv420_to_bgr_frames_kernel<1, true>), grid, block, 0, *fl, j, luts);
+        else                       LAUNCH(c, s, MI_K_LUT_APPLY, (yuv420_to_bgr_frames_kernel<0, true>), grid, block, 0, *fl, j, luts);
+    } else if (fl) {
+        if (order == MI_ORDER_RGB) LAUNCH(c, s, MI_K_COLOR, (yuv420_to_bgr_frames_kernel<1, false>), grid, block, 0, *fl, j, luts);
+        else                       LAUNCH(c, s, MI_K_COLOR, (yuv420_to_bgr_frames_kernel<0, false>), grid, block, 0, *fl, j, luts);
+    } else if (luts) {
         if (order == MI_ORDER_RGB) LAUNCH(c, s, MI_K_LUT_APPLY, (yuv420_to_bgr_kernel<1, true>), grid, block, 0, j, luts);
         else                       LAUNCH(c, s, MI_K_LUT_APPLY, (yuv420_to_bgr_kernel<0, true>), grid, block, 0, j, luts);
     } else {
@@ -84,8 +93,10 @@ mi_status launch_yuv420_to_bgr(mi_ctx* c, hipStream_t s, const Yuv420BgrJob& j, 
     return MI_OK;
 }
 
-// CLAHE blend + decode of nf frames whose tile LUTs are in `luts`: the grid of launch_nv12_bgr_interp
-mi_status launch_yuv420_bgr_interp(mi_ctx* c, hipStream_t s, const Yuv420BgrJob& j, const ClaheGeom& g, int nf, int order, const uint8_t* luts)
+// CLAHE blend + decode of nf frames whose tile LUTs are in `luts`: the grid of launch_nv12_bgr_interp.  `fl`: as for
+// launch_yuv420_to_bgr.
+mi_status launch_yuv420_bgr_interp(mi_ctx* c, hipStream_t s, const Yuv420BgrJob& j, const ClaheGeom& g, int nf, int order, const uint8_t* luts,
+                                   const Yuv420BgrList* fl = nullptr)
 {
     const int ngroups = j.width / kInterpPx;
     const int groups = std::min(ngroups, kThreads);
@@ -95,6 +106,13 @@ mi_status launch_yuv420_bgr_interp(mi_ctx* c, hipStream_t s, const Yuv420BgrJob&
     const int subs = (int)std::max<long long>(1, std::min<long long>({want, (long long)std::max(1, (g.tile_h + 2 * kBandMargin) / 8), 64LL}));
     const dim3 grid(bands * subs, nf, segs);
     const size_t lds = (size_t)(g.tiles_x + 1) * 256 * 4 * sizeof(float);
+    if (fl) {
+        if (order == MI_ORDER_RGB)
+            LAUNCH(c, s, MI_K_CLAHE_INTERP, yuv420_bgr_clahe_interp_frames_kernel<1>, grid, dim3(kThreads), lds, *fl, j, g, luts, subs, groups);
+        else
+            LAUNCH(c, s, MI_K_CLAHE_INTERP, yuv420_bgr_clahe_interp_frames_kernel<0>, grid, dim3(kThreads), lds, *fl, j, g, luts, subs, groups);
+        return MI_OK;
+    }
     if (order == MI_ORDER_RGB)
         LAUNCH(c, s, MI_K_CLAHE_INTERP, yuv420_bgr_clahe_interp_kernel<1>, grid, dim3(kThreads), lds, j, g, luts, subs, groups);
     else

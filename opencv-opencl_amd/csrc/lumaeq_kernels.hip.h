@@ -37,7 +37,8 @@
 //   kernels/yuv420.hip.h           the chroma of 4:2:0 frames between planar (I420 / YV12) and interleaved (NV12) layouts: copy, relayout or fill,
 //                                  on a batch at a frame stride or on a list of per-frame plane addresses
 //   kernels/yuv420_bgr.hip.h       the pixel-writing stages of planar 4:2:0 (I420 / YV12) in, interleaved BGR / RGB out: those of nv12_bgr.hip.h
-//                                  with the chroma loaded from two planes and zipped in registers
+//                                  with the chroma loaded from two planes and zipped in registers; their *_frames_kernel entries on a
+//                                  list of {y, u, v, out} addresses
 #pragma once
 #include "kernels/common.hip.h"
 #include "kernels/equalize.hip.h"

@@ -54,5 +54,6 @@ using namespace mi;
 #include "host/yuv420.inc.hpp"         // 4:2:0 frames whose sides say where their planes lie: I420 / YV12 / NV12 in, any of them out
 #include "host/yuv420_frames.inc.hpp"  // ... as a list of separately allocated, pitched planes (a decoder's frame pool in, an encoder's surface pool out)
 #include "host/yuv420_bgr.inc.hpp"     // planar 4:2:0 (I420 / YV12) or NV12 frames in, interleaved BGR / RGB out in the pass that maps the luma (software decoder -> model)
+#include "host/yuv420_bgr_frames.inc.hpp"   // ... as a list of separately allocated, pitched planes (a decoder's frame pool in, an image pool out)
 #include "host/pipe.inc.hpp"
 #include "host/diff.inc.hpp"

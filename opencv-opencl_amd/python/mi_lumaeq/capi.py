@@ -61,6 +61,7 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_yuv420_batch_dev", "mi_clahe_yuv420_batch_dev", "mi_equalize_hist_yuv420", "mi_clahe_yuv420",
     "mi_equalize_hist_yuv420_frames_dev", "mi_clahe_yuv420_frames_dev",
     "mi_equalize_hist_yuv420_to_bgr_batch_dev", "mi_clahe_yuv420_to_bgr_batch_dev", "mi_equalize_hist_yuv420_to_bgr", "mi_clahe_yuv420_to_bgr",
+    "mi_equalize_hist_yuv420_to_bgr_frames_dev", "mi_clahe_yuv420_to_bgr_frames_dev",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -142,6 +143,18 @@ class Yuv420FrameDev(C.Structure):
     def of(cls, y_in, c0_in, c1_in, y_out, c0_out, c1_out):
         """the same from torch CUDA tensors, raw device addresses or None"""
         return cls(*(None if p is None else _dptr(p) for p in (y_in, c0_in, c1_in, y_out, c0_out, c1_out)))
+
+
+class Yuv420BgrFrameDev(C.Structure):
+    """mi_yuv420_bgr_frame_dev: one frame of a mi_*_yuv420_to_bgr_frames_dev list, its three input plane addresses and its image address
+    (device pointers).  c0 is always the U plane and c1 the V plane (a YV12 frame exchanges the two); an INTERLEAVED list has its UV
+    plane in c0 and its c1 is ignored (None)."""
+    _fields_ = [("y", C.c_void_p), ("c0", C.c_void_p), ("c1", C.c_void_p), ("out", C.c_void_p)]
+
+    @classmethod
+    def of(cls, y, c0, c1, out):
+        """the same from torch CUDA tensors, raw device addresses or None"""
+        return cls(*(None if p is None else _dptr(p) for p in (y, c0, c1, out)))
 
 
 _YUV420_FMTS = {"nv12": Yuv420Planes.nv12, "i420": Yuv420Planes.i420, "yv12": Yuv420Planes.yv12}
@@ -261,6 +274,8 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_yuv420_frames_dev.argtypes = [vp, C.POINTER(Yuv420FrameDev), i, i, i, sz, sz, i, sz, sz, i, i, d, i, i, vp]
     L.mi_equalize_hist_yuv420_to_bgr_batch_dev.argtypes = [vp, yp, vp, sz, sz, i, i, i, i, vp]
     L.mi_clahe_yuv420_to_bgr_batch_dev.argtypes = [vp, yp, vp, sz, sz, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_yuv420_to_bgr_frames_dev.argtypes = [vp, C.POINTER(Yuv420BgrFrameDev), i, i, i, sz, sz, i, sz, i, vp]
+    L.mi_clahe_yuv420_to_bgr_frames_dev.argtypes = [vp, C.POINTER(Yuv420BgrFrameDev), i, i, i, sz, sz, i, sz, i, d, i, i, vp]
     L.mi_equalize_hist_yuv420_to_bgr.argtypes = [vp, yp, vp, sz, i, i, i]
     L.mi_clahe_yuv420_to_bgr.argtypes = [vp, yp, vp, sz, i, i, i, d, i, i]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
@@ -1106,6 +1121,37 @@ class Context:
         self._chk(self._L.mi_clahe_yuv420_to_bgr_batch_dev(self._h, C.byref(src), _dptr(d_out), op, fo, int(width), int(height),
                                                          int(n_frames), int(order), float(clip_limit), int(tiles_x), int(tiles_y), stream),
                   "mi_clahe_yuv420_to_bgr_batch_dev")
+
+    @staticmethod
+    def _yuv420_bgr_list(frames):
+        """frames: a sequence of Yuv420BgrFrameDev, or a ctypes array of them.  Returns the array and its length."""
+        if isinstance(frames, C.Array):
+            return frames, len(frames)
+        frames = list(frames)
+        arr = (Yuv420BgrFrameDev * max(1, len(frames)))()
+        for k, f in enumerate(frames):
+            arr[k] = f
+        return arr, len(frames)
+
+    def equalize_hist_yuv420_to_bgr_frames_dev(self, frames, width, height, y_pitch, c_pitch, chroma, order=ORDER_BGR, out_pitch=None,
+                                               stream=0):
+        """mi_equalize_hist_yuv420_to_bgr_frames_dev.  frames: Yuv420BgrFrameDev entries, one per frame, every plane and every image at
+        its own device address (a software decoder's frame pool in, an image pool out); one shape, one set of pitches and one chroma
+        layout for the call.  The tight image is the default: out_pitch 3*W."""
+        arr, n = self._yuv420_bgr_list(frames)
+        op = 3 * int(width) if out_pitch is None else int(out_pitch)
+        self._chk(self._L.mi_equalize_hist_yuv420_to_bgr_frames_dev(self._h, arr, n, int(width), int(height), int(y_pitch), int(c_pitch),
+                                                                  int(chroma), op, int(order), stream),
+                  "mi_equalize_hist_yuv420_to_bgr_frames_dev")
+
+    def clahe_yuv420_to_bgr_frames_dev(self, frames, width, height, y_pitch, c_pitch, chroma, order=ORDER_BGR, clip_limit=2.0, tiles_x=8,
+                                       tiles_y=8, out_pitch=None, stream=0):
+        """mi_clahe_yuv420_to_bgr_frames_dev; arguments as equalize_hist_yuv420_to_bgr_frames_dev, plus the CLAHE parameters."""
+        arr, n = self._yuv420_bgr_list(frames)
+        op = 3 * int(width) if out_pitch is None else int(out_pitch)
+        self._chk(self._L.mi_clahe_yuv420_to_bgr_frames_dev(self._h, arr, n, int(width), int(height), int(y_pitch), int(c_pitch),
+                                                          int(chroma), op, int(order), float(clip_limit), int(tiles_x), int(tiles_y),
+                                                          stream), "mi_clahe_yuv420_to_bgr_frames_dev")
 
     def _yuv420_bgr_host(self, frame, width, height, src_fmt, out, name):
         if src_fmt not in _YUV420_FMTS:

@@ -3,7 +3,7 @@
 tiles (several tiles per histogram workgroup), 16-bit CLAHE at random value ranges, the 4:2:0 codes at random aligned / unaligned sizes, NV12 in / BGR out
 at random pitched layouts (aligned and not) and tile grids on both sides of its one-pass conditions, as a batch and as a frame list
 (random order, every image at its own offset), and the same pixels from planar chroma (I420 / YV12 in, BGR out) at chroma layouts that are
-multiples of 8 or of 1.
+multiples of 8 or of 1, as a batch and as a frame list against the batch form's bytes.
     python tools/stress_random.py [seconds] [seed] [option=value ...]        prints a line every ~15 s, exits non-zero on the first mismatch"""
 import sys, time
 sys.path.insert(0, "opencv-opencl_amd/python"); sys.path.insert(0, ".")
@@ -15,7 +15,7 @@ rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 ctx = mi_lumaeq.Context(0)
 for kv in sys.argv[3:]:                                          # name=value options for the whole run, e.g. clahe16_wide=2 (mid kernel always launched)
     k_, v_ = kv.split("="); ctx.set_option(k_, int(v_)); print("option", k_, "=", v_, flush=True)
-t0 = last = time.time(); n = {"roi": 0, "grid": 0, "small": 0, "c16": 0, "420": 0, "nv12": 0, "nv12bgr": 0, "yuv420bgr": 0}
+t0 = last = time.time(); n = {"roi": 0, "grid": 0, "small": 0, "c16": 0, "420": 0, "nv12": 0, "nv12bgr": 0, "yuv420bgr": 0, "yuv420bgrlist": 0}
 def dev(a): return xfer.to_device(np.ascontiguousarray(a))
 def fail(what, *info):
     print("MISMATCH", what, info, flush=True); sys.exit(1)
@@ -148,6 +148,21 @@ while time.time() - t0 < budget:
         if not torch.equal(d_out3, d_out): fail("yuv420bgr", w, h, nf, op, order, clip, tx, ty, al, yp, cp, g0, g1, pfi, yv12, opi, off, ooff)
         if not np.array_equal(xfer.to_host(d_pin), pimg): fail("yuv420bgr wrote its input", w, h, nf, op)
         n["yuv420bgr"] += 1
+        # the planar list form on the same planes, against the batch form's bytes: the frames in another random order, every image at
+        # an offset of its own (one in three some bytes past a 16-byte boundary: that frame alone takes the byte walk and CLAHE the
+        # fallback), U and V exchanged between c0 and c1 by the layout alone
+        perm = [int(v) for v in rng.permutation(nf)]; jit = [int(rng.integers(0, 16)) if rng.integers(0, 3) == 0 else 0 for _ in range(nf)]
+        oo = [ooff + f * (fo + 16) + jit[f] for f in range(nf)]
+        d_out4 = torch.full((ooff + (fo + 16) * nf + 64,), 0x5A, dtype=torch.uint8, device="cuda"); want = np.full(d_out4.numel(), 0x5A, np.uint8)
+        ents = [mi_lumaeq.Yuv420BgrFrameDev(b + f * pfi, b + u_off + f * pfi, b + v_off + f * pfi, d_out4.data_ptr() + oo[f]) for f in perm]
+        fa = (ents, w, h, yp, cp, mi_lumaeq.CHROMA_PLANAR, order); fkw = dict(out_pitch=opi)
+        if op == 0: ctx.equalize_hist_yuv420_to_bgr_frames_dev(*fa, **fkw)
+        else: ctx.clahe_yuv420_to_bgr_frames_dev(*fa, clip, tx, ty, **fkw)
+        ctx.synchronize(); out = xfer.to_host(d_out4); bat = xfer.to_host(d_out3)
+        for f in range(nf): want[oo[f]: oo[f] + opi * h].reshape(h, opi)[:, : 3 * w] = bat[ooff + f * fo: ooff + f * fo + opi * h].reshape(h, opi)[:, : 3 * w]
+        if not np.array_equal(out, want): fail("yuv420bgr list", w, h, nf, op, order, clip, tx, ty, al, yp, cp, g0, g1, pfi, yv12, opi, off, ooff, perm, jit, np.flatnonzero(out != want)[:8])
+        if not np.array_equal(xfer.to_host(d_pin), pimg): fail("yuv420bgr list wrote its input", w, h, nf, op)
+        n["yuv420bgrlist"] += 1
     else:           # 4:2:0 codes
         w, h = int(rng.integers(1, 60)) * (16 if rng.integers(0, 2) else 2), int(rng.integers(1, 40)) * 2
         bgr = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
