@@ -839,6 +839,66 @@ mi_status mi_equalize_hist_yuv420_to_bgr_frames_dev(mi_ctx* ctx, const mi_yuv420
 mi_status mi_clahe_yuv420_to_bgr_frames_dev(mi_ctx* ctx, const mi_yuv420_bgr_frame_dev* frames, int n_frames,
         int width, int height, size_t y_pitch, size_t c_pitch, int chroma, size_t out_pitch, int order,
         double clip_limit, int tiles_x, int tiles_y, void* stream);
+/* mi_*_bgr_to_yuv420*: interleaved 8-bit BGR (or RGB) images in, 4:2:0 frames described by mi_yuv420_planes out with the luma equalized
+ * -- planar chroma (I420 / YV12: the three pitched planes a software encoder takes, data[0..2] / linesize[0..2]: x264, libvpx, SVT-AV1)
+ * or interleaved (NV12) -- renderer, model output or image reader -> encoder without an NV12 intermediate and without plane copies
+ * outside the library.  Per frame the bytes are what OpenCV 4.4 gives for
+ *     cv::cvtColor(bgr, i420, cv::COLOR_BGR2YUV_I420);                                           (COLOR_RGB2YUV_I420 for MI_ORDER_RGB)
+ *     cv::Mat y = i420(Rect(0, 0, W, H));  cv::equalizeHist(y, y)  /  clahe->apply(y, y);        (Y only)
+ * with the U plane going to out->c0 and the V plane to out->c1 (MI_UV_COPY) or every chroma byte 128 (MI_UV_FILL128).  Chroma comes
+ * from the top-left pixel of each 2 x 2 block, without averaging.  The luma is byte for byte the Y plane of mi_*_bgr_to_nv12_batch_dev
+ * for the same pixels; U and V are that call's UV plane de-interleaved and equal the U and V rows of
+ * mi_cvt_color_420_u8_batch_dev(MI_COLOR_BGR2YUV_I420).  c0 is always U and c1 always V: a YV12 caller passes the address of its second
+ * chroma plane as c0.  The same clahe_fp_contract option, the same REFLECT_101 padding when the tile grid does not divide the frame and
+ * the same limits on sizes and tile grids as the planar forms, with the same statuses.
+ *   input  : as in mi_*_bgr_to_nv12_batch_dev: frame f at d_in + f * in_frame_stride, H rows of 3*W bytes at in_pitch >= 3*W: B, G, R per
+ *            pixel (MI_ORDER_BGR) or R, G, B (MI_ORDER_RGB).  The input is never written.
+ *   output : `out` is read only during the call.  Frame f has every plane at its pointer + f * out->frame_stride: Y, H rows of W bytes
+ *            at y_pitch >= W; PLANAR: c0 = U and c1 = V, each H/2 rows of W/2 bytes at c_pitch >= W/2; INTERLEAVED: c0 = the UV plane,
+ *            H/2 rows of W bytes at c_pitch >= W.  Only the W bytes (Y, interleaved UV) or W/2 bytes (planar U, V) of each output row
+ *            are written: not the pitch padding, not the gaps between the planes, not the gaps between frames.
+ * out->chroma == MI_CHROMA_INTERLEAVED: the call IS the NV12 form's (d_y_out = out->y, d_uv_out = out->c0, uv_pitch = out->c_pitch,
+ *   out_frame_stride = out->frame_stride; out->c1 ignored): the same kernels, the same alignment rule (multiples of 16 throughout), the
+ *   same checks; none of the counters below moves.
+ * Alignment (MI_CHROMA_PLANAR): none is required of any pointer, pitch or stride.  A call moves 16 x 2 pixel groups per lane when
+ *   W % 16 == 0; d_in, in_pitch, in_frame_stride, out->y, out->y_pitch and out->frame_stride are multiples of 16; and out->c0, out->c1
+ *   and out->c_pitch are multiples of 8 (not 16: a lane makes six 16-byte loads, two 16-byte Y stores, one 8-byte U store and one
+ *   8-byte V store -- the mirror of the loads of the 4:2:0 -> BGR forms).  Otherwise it processes 2 x 2 pixel blocks with byte accesses
+ *   -- slower, the same bytes out.
+ * Two stages per chunk of 256 frames, as in the NV12 form.  Y is not in the input, so stage 1 converts: ONE kernel (charged to
+ *   MI_K_COLOR) reads the image once, writes Y, U and V into the caller's planes and, for equalizeHist, counts the luma bytes it has
+ *   just produced.  Stage 2 maps the luma IN PLACE in out->y with the planar kernels: equalizeHist one MI_K_EQ_LUT and one
+ *   MI_K_LUT_APPLY launch (no MI_K_HIST launch; never the fused equalizeHist kernel nor the single-launch histogram + LUT kernel, option
+ *   two_kernel_max_frames does not apply); CLAHE exactly what mi_clahe_u8_batch_dev launches for that plane in place.  Bytes moved per
+ *   pixel: equalizeHist 3 + 1.5 + 1 + 1 = 6.5, CLAHE 4.5 + 3 = 7.5.  Between the stages out->y holds the unequalized luma.
+ * Counters (mi_ctx_get_stat), PLANAR-output calls only: "bgr_yuv420_vec" / "bgr_yuv420_bytes", one count per call by the walk the
+ *   conversion kernel took (16 x 2 groups / 2 x 2 blocks).  A call with work to do moves exactly one of them; a call that returns an
+ *   error or has a zero size moves neither.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of the
+ *   same shape as the other batched device forms.
+ * mi_equalize_hist_bgr_to_yuv420 / mi_clahe_bgr_to_yuv420: ONE CV_8UC3 image in host memory at in_step >= 3*W, at any address, in; `out`
+ *   holds HOST pointers at any address and pitch (frame_stride is ignored).  Synchronous; the image is staged in like
+ *   mi_*_bgr_to_nv12's and the planes come back like mi_*_yuv420's (planes in pinned memory that are tight are DMA'd as they are,
+ *   everything else goes through the context's pinned staging).  On the device the frame is tight with every plane at a 16-byte
+ *   aligned offset, so a W % 16 == 0 frame takes the 16 x 2 groups.  Whatever the call returns, no copy on the caller's memory is in
+ *   flight any more when it returns.  W*H beyond what mi_*_bgr_to_nv12 accepts: MI_ERR_UNSUPPORTED.
+ * Errors, MI_ERR_BAD_ARG: a null ctx, d_in or `out`; a null out->y or out->c0; a null out->c1 on a PLANAR output; a `chroma` other than
+ *   the two values; an `order` other than the two; a bad uv_mode; a negative size; an odd width or an odd height (refused even when
+ *   another size is 0, as in the sibling forms); in_pitch < 3*W; y_pitch < W; a c_pitch below its row (W interleaved, W/2 planar);
+ *   tiles <= 0; two output plane pointers of the call that are equal; an output plane pointer equal to d_in (there is no in-place
+ *   form).  Any other overlap: undefined, not checked; U and V rows side by side in one pitched plane (c1 = c0 + W/2, c_pitch = W) are
+ *   legal, as in mi_*_yuv420*.  width, height or n_frames of 0: MI_OK, nothing written (pointers and pitches are not looked at then).
+ *   Sizes and tile grids the planar forms refuse: the status they give (MI_ERR_UNSUPPORTED), nothing written.  Nothing is enqueued
+ *   unless every check passes. */
+mi_status mi_equalize_hist_bgr_to_yuv420_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        const mi_yuv420_planes* out, int width, int height, int n_frames, int order, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_bgr_to_yuv420_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        const mi_yuv420_planes* out, int width, int height, int n_frames, int order, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
+mi_status mi_equalize_hist_bgr_to_yuv420(mi_ctx* ctx, const uint8_t* in, size_t in_step, const mi_yuv420_planes* out,
+        int width, int height, int order, mi_uv_mode uv_mode);
+mi_status mi_clahe_bgr_to_yuv420(mi_ctx* ctx, const uint8_t* in, size_t in_step, const mi_yuv420_planes* out,
+        int width, int height, int order, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
 
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at

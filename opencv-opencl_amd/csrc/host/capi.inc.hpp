@@ -355,7 +355,9 @@ mi_status mi_ctx_synchronize(mi_ctx* c, void* stream)
 // accesses.  Every such call with work to do moves one counter of each pair; an INTERLEAVED input counts in the nv12_bgr_* pair),
 // "yuv420_bgr_list_frames_vec" / "yuv420_bgr_list_frames_bytes" (FRAMES of PLANAR mi_*_yuv420_to_bgr_frames_dev calls whose pixels were
 // written on 16 x 2 pixel groups / on 2 x 2 blocks, each by its own addresses; list calls move the onepass / twopass pair once a call
-// and do not touch "yuv420_bgr_vec" / "yuv420_bgr_bytes").
+// and do not touch "yuv420_bgr_vec" / "yuv420_bgr_bytes"),
+// "bgr_yuv420_vec" / "bgr_yuv420_bytes" (PLANAR-output mi_*_bgr_to_yuv420* calls whose conversion kernel walked 16 x 2 pixel groups / 2 x 2
+// blocks with byte accesses: one count per call with work to do; an INTERLEAVED output is the NV12 form's call and moves neither).
 mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
 {
     ENTER(c);
@@ -391,6 +393,8 @@ mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
     if (!strcmp(name, "yuv420_bgr_bytes")) { *out = c->yuv420_bgr_bytes; return MI_OK; }
     if (!strcmp(name, "yuv420_bgr_list_frames_vec")) { *out = c->yuv420_bgr_list_frames_vec; return MI_OK; }
     if (!strcmp(name, "yuv420_bgr_list_frames_bytes")) { *out = c->yuv420_bgr_list_frames_bytes; return MI_OK; }
+    if (!strcmp(name, "bgr_yuv420_vec")) { *out = c->bgr_yuv420_vec; return MI_OK; }
+    if (!strcmp(name, "bgr_yuv420_bytes")) { *out = c->bgr_yuv420_bytes; return MI_OK; }
     return fail(c, MI_ERR_BAD_ARG, "unknown stat");
 }
 

@@ -571,6 +571,26 @@ inline void claheYUV420ToBGR(const YUV420View& in, unsigned char* out, size_t ou
     detail::check(c, mi_clahe_yuv420_to_bgr(c, &a, out, outStep, width, height, (int)order, clipLimit, tiles.width, tiles.height),
                   "mi_clahe_yuv420_to_bgr");
 }
+// The opposite edge: one interleaved CV_8UC3 host image (BGR, or RGB) at inStep >= 3*W in, the planes of the view out:
+// cv::cvtColor(COLOR_BGR2YUV_I420) + cv::equalizeHist / CLAHE::apply on the Y plane, U into out.c0 and V into out.c1 (UV_COPY) or chroma
+// 128 (UV_FILL128): a renderer's or a model's image -> the three pitched planes a software encoder takes, without an NV12 frame in
+// between and without plane copies.  An interleaved view gives what equalizeHistBGRToNV12 gives, at the view's pitches.
+inline void equalizeHistBGRToYUV420(const unsigned char* in, size_t inStep, const YUV420View& out, int width, int height,
+                                    ChannelOrder order = ORDER_BGR, UVMode uv = UV_COPY)
+{
+    mi_ctx* c = detail::thread_ctx();
+    const mi_yuv420_planes b = out.planes();
+    detail::check(c, mi_equalize_hist_bgr_to_yuv420(c, in, inStep, &b, width, height, (int)order, (mi_uv_mode)uv),
+                  "mi_equalize_hist_bgr_to_yuv420");
+}
+inline void claheBGRToYUV420(const unsigned char* in, size_t inStep, const YUV420View& out, int width, int height, double clipLimit,
+                             Size tiles, ChannelOrder order = ORDER_BGR, UVMode uv = UV_COPY)
+{
+    mi_ctx* c = detail::thread_ctx();
+    const mi_yuv420_planes b = out.planes();
+    detail::check(c, mi_clahe_bgr_to_yuv420(c, in, inStep, &b, width, height, (int)order, (mi_uv_mode)uv, clipLimit, tiles.width,
+                                            tiles.height), "mi_clahe_bgr_to_yuv420");
+}
 
 // BASELINE.json config 5 read literally: cvtColor(COLOR_YUV2BGR_NV12) -> split -> equalizeHist on B, G and R -> merge ->
 // cvtColor(COLOR_BGR2YUV_I420) + U/V interleave, NV12 in -> NV12 out in one call (no file of the reference does this;

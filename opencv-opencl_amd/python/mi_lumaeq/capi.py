@@ -62,6 +62,7 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_yuv420_frames_dev", "mi_clahe_yuv420_frames_dev",
     "mi_equalize_hist_yuv420_to_bgr_batch_dev", "mi_clahe_yuv420_to_bgr_batch_dev", "mi_equalize_hist_yuv420_to_bgr", "mi_clahe_yuv420_to_bgr",
     "mi_equalize_hist_yuv420_to_bgr_frames_dev", "mi_clahe_yuv420_to_bgr_frames_dev",
+    "mi_equalize_hist_bgr_to_yuv420_batch_dev", "mi_clahe_bgr_to_yuv420_batch_dev", "mi_equalize_hist_bgr_to_yuv420", "mi_clahe_bgr_to_yuv420",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -278,6 +279,10 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_yuv420_to_bgr_frames_dev.argtypes = [vp, C.POINTER(Yuv420BgrFrameDev), i, i, i, sz, sz, i, sz, i, d, i, i, vp]
     L.mi_equalize_hist_yuv420_to_bgr.argtypes = [vp, yp, vp, sz, i, i, i]
     L.mi_clahe_yuv420_to_bgr.argtypes = [vp, yp, vp, sz, i, i, i, d, i, i]
+    L.mi_equalize_hist_bgr_to_yuv420_batch_dev.argtypes = [vp, vp, sz, sz, yp, i, i, i, i, i, vp]
+    L.mi_clahe_bgr_to_yuv420_batch_dev.argtypes = [vp, vp, sz, sz, yp, i, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_bgr_to_yuv420.argtypes = [vp, vp, sz, yp, i, i, i, i]
+    L.mi_clahe_bgr_to_yuv420.argtypes = [vp, vp, sz, yp, i, i, i, i, d, i, i]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -1174,6 +1179,50 @@ class Context:
         a, out, step = self._yuv420_bgr_host(frame, int(width), int(height), src_fmt, out, "clahe_yuv420_to_bgr")
         self._chk(self._L.mi_clahe_yuv420_to_bgr(self._h, C.byref(a), out.ctypes.data, step, int(width), int(height), int(order),
                                                float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_yuv420_to_bgr")
+        return out
+
+    # ---- interleaved BGR / RGB in, 4:2:0 frames (I420 / YV12 planes, or NV12) out: convert and count in one pass, then map the luma in place ----
+    def equalize_hist_bgr_to_yuv420_batch_dev(self, d_in, dst, width, height, n_frames, order=ORDER_BGR, uv_mode=UV_COPY, in_pitch=None,
+                                              in_frame=None, stream=0):
+        """mi_equalize_hist_bgr_to_yuv420_batch_dev.  d_in: the images (a torch tensor or a raw address); dst: a Yuv420Planes holding
+        device addresses (Yuv420Planes.i420 / .yv12 / .nv12 for tight batches, the fields themselves for pitched or separately allocated
+        planes).  The tight input is the default: in_pitch 3*W, in_frame = in_pitch * H."""
+        ip = 3 * int(width) if in_pitch is None else int(in_pitch)
+        fi = ip * int(height) if in_frame is None else int(in_frame)
+        self._chk(self._L.mi_equalize_hist_bgr_to_yuv420_batch_dev(self._h, _dptr(d_in), ip, fi, C.byref(dst), int(width), int(height),
+                                                                 int(n_frames), int(order), int(uv_mode), stream),
+                  "mi_equalize_hist_bgr_to_yuv420_batch_dev")
+
+    def clahe_bgr_to_yuv420_batch_dev(self, d_in, dst, width, height, n_frames, order=ORDER_BGR, uv_mode=UV_COPY, clip_limit=2.0,
+                                      tiles_x=8, tiles_y=8, in_pitch=None, in_frame=None, stream=0):
+        """mi_clahe_bgr_to_yuv420_batch_dev; arguments as equalize_hist_bgr_to_yuv420_batch_dev, plus the CLAHE parameters."""
+        ip = 3 * int(width) if in_pitch is None else int(in_pitch)
+        fi = ip * int(height) if in_frame is None else int(in_frame)
+        self._chk(self._L.mi_clahe_bgr_to_yuv420_batch_dev(self._h, _dptr(d_in), ip, fi, C.byref(dst), int(width), int(height),
+                                                         int(n_frames), int(order), int(uv_mode), float(clip_limit), int(tiles_x),
+                                                         int(tiles_y), stream), "mi_clahe_bgr_to_yuv420_batch_dev")
+
+    def _bgr_yuv420_host(self, img, dst_fmt, out, name):
+        if dst_fmt not in _YUV420_FMTS:
+            raise MiError(1, name, 'dst_fmt must be "nv12", "i420" or "yv12"')
+        img, h, w, step, out = self._bgr_nv12_host(img, out, name)
+        return img, h, w, step, out, _YUV420_FMTS[dst_fmt](out.ctypes.data, w, h)
+
+    def equalize_hist_bgr_to_yuv420(self, img: np.ndarray, dst_fmt: str = "i420", order: int = ORDER_BGR, uv_mode: int = UV_COPY,
+                                    out: np.ndarray | None = None) -> np.ndarray:
+        """mi_equalize_hist_bgr_to_yuv420 on a host image: an H x W x 3 uint8 array in (a view with padded rows included), the tight frame
+        of W*H*3/2 bytes out, its chroma laid out as dst_fmt in {"nv12", "i420", "yv12"} says -- `out` when given, else a new array."""
+        img, h, w, step, out, b = self._bgr_yuv420_host(img, dst_fmt, out, "equalize_hist_bgr_to_yuv420")
+        self._chk(self._L.mi_equalize_hist_bgr_to_yuv420(self._h, img.ctypes.data, step, C.byref(b), w, h, int(order), int(uv_mode)),
+                  "mi_equalize_hist_bgr_to_yuv420")
+        return out
+
+    def clahe_bgr_to_yuv420(self, img: np.ndarray, dst_fmt: str = "i420", order: int = ORDER_BGR, uv_mode: int = UV_COPY,
+                            clip_limit: float = 2.0, tiles_x: int = 8, tiles_y: int = 8, out: np.ndarray | None = None) -> np.ndarray:
+        """mi_clahe_bgr_to_yuv420; arguments as equalize_hist_bgr_to_yuv420, plus the CLAHE parameters."""
+        img, h, w, step, out, b = self._bgr_yuv420_host(img, dst_fmt, out, "clahe_bgr_to_yuv420")
+        self._chk(self._L.mi_clahe_bgr_to_yuv420(self._h, img.ctypes.data, step, C.byref(b), w, h, int(order), int(uv_mode),
+                                               float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_bgr_to_yuv420")
         return out
 
     # ---- colour-domain neighbours (N3) ----
