@@ -899,6 +899,61 @@ mi_status mi_equalize_hist_bgr_to_yuv420(mi_ctx* ctx, const uint8_t* in, size_t 
         int width, int height, int order, mi_uv_mode uv_mode);
 mi_status mi_clahe_bgr_to_yuv420(mi_ctx* ctx, const uint8_t* in, size_t in_step, const mi_yuv420_planes* out,
         int width, int height, int order, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
+/* mi_*_bgr_to_yuv420_frames_dev: the same conversion on a LIST of device frames, each at its own four addresses -- a pool of CV_8UC3
+ * images in (a renderer or a model hands over one image per frame), a software encoder's frame pool out (x264, libvpx, SVT-AV1: every
+ * frame three separately allocated, pitched planes, data[0..2] / linesize[0..2]).  The batch form needs both sides in one allocation
+ * each at a constant frame stride; one n_frames = 1 batch call per frame costs a launch sequence per frame with tiny grids, and
+ * repacking both pools into strided scratch and copying the planes out moves 3 + 1.5 bytes per pixel more each way.
+ * `frames` is a host array of n_frames entries, read only during the call; the pointers in it are device pointers on the context's
+ * device.
+ * Shape: all frames of one call share width, height, order, uv_mode, chroma and the three pitches (bytes between rows); each has its
+ *   own addresses.  There are no per-frame pitches.
+ *   in : H rows of 3*W bytes at in_pitch >= 3*W -- B, G, R per pixel (MI_ORDER_BGR) or R, G, B (MI_ORDER_RGB)
+ *   y  : H rows of W bytes at y_pitch >= W
+ *   c0, c1 (MI_CHROMA_PLANAR): the U and the V plane, each H/2 rows of W/2 bytes at c_pitch >= W/2 (both planes share the pitch).  c0 is
+ *        always U and c1 always V: a YV12 caller exchanges the two addresses.
+ * Bytes: per frame the output is byte for byte what mi_*_bgr_to_yuv420_batch_dev writes for that frame alone at the same pitches --
+ *   cvtColor(COLOR_BGR2YUV_I420, or the RGB code), then cv::equalizeHist / CLAHE::apply on Y, U and V of the conversion (MI_UV_COPY) or
+ *   every chroma byte 128 (MI_UV_FILL128); the clahe_fp_contract option is honoured, REFLECT_101 padding applies when the tile grid
+ *   does not divide the frame, the limits on sizes and tile grids are the batch form's, with the same statuses.
+ * Writes: only the W bytes of each Y row and the W/2 bytes of each U and V row are written: not the pitch padding, not the gaps
+ *   between planes or frames.  The images are never written.
+ * chroma == MI_CHROMA_INTERLEAVED: the call IS mi_*_bgr_to_nv12_frames_dev on {in, y, c0} with uv_pitch = c_pitch (c0 = the UV plane,
+ *   H/2 rows of W bytes at c_pitch >= W; c1 is ignored and may be NULL): that form's checks, its kernels and its rule of multiples of
+ *   16 throughout; none of the counters below moves.
+ * Alignment (MI_CHROMA_PLANAR): none is required of any address or pitch.  The per-frame alignment decides the access width: the
+ *   shape allows 16 x 2 pixel groups when W % 16 == 0, in_pitch and y_pitch are multiples of 16 and c_pitch is a multiple of 8; a
+ *   frame then takes the groups when its in and y are multiples of 16 and its c0 and c1 multiples of 8 (8, not 16: a lane makes six
+ *   16-byte loads, two 16-byte Y stores, one 8-byte U store and one 8-byte V store), and any other frame of the same call processes
+ *   2 x 2 pixel blocks with byte accesses while its neighbours stay vectorised -- slower, the same bytes out.
+ * Stages, per chunk of 64 frames of the list (not the batch form's 256): stage 1 is ONE launch charged to MI_K_COLOR that converts
+ *   into the caller's planes and, for equalizeHist, counts the luma bytes it has just produced.  Stage 2 maps the luma IN PLACE on the
+ *   chunk's Y planes: equalizeHist one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch (no MI_K_HIST launch; never the fused equalizeHist
+ *   kernel nor the single-launch histogram + LUT kernel, option two_kernel_max_frames does not apply); CLAHE exactly what
+ *   mi_clahe_nv12_frames_dev launches in place on those Y planes.  Launches are charged to the same profiling slots as the batch form.
+ *   Between the stages a frame's y holds the unequalized luma.
+ * Counters (mi_ctx_get_stat), PLANAR lists only: "bgr_yuv420_list_frames_vec" / "bgr_yuv420_list_frames_bytes" count the FRAMES (not
+ *   calls) of list calls by the walk their stage-1 kernel took: 16 x 2 groups / 2 x 2 blocks.  "bgr_yuv420_vec" / "bgr_yuv420_bytes"
+ *   are not touched by list calls.  A call that returns an error or has nothing to do moves none.
+ * Overlap: there is no in-place form.  MI_ERR_BAD_ARG when the rows of a frame's image meet the rows of its own Y, U or V plane, or
+ *   the rows of its Y plane meet the rows of its own U or V plane (compared as address ranges), and when c0 == c1.  U and V are
+ *   otherwise not compared with each other: the U and V rows may lie side by side in one pitched plane (c1 = c0 + W/2, c_pitch = W),
+ *   as in the batch form.  The same image may appear in several entries (inputs are only read).  Outputs that overlap ANOTHER frame's
+ *   planes give undefined results and are not checked.
+ * Errors, MI_ERR_BAD_ARG: a null ctx; a null `frames` with n_frames > 0; a null in, y or c0 in any entry; a null c1 in any entry on a
+ *   PLANAR list; a `chroma` other than the two values; an `order` other than the two; a bad uv_mode; a negative size; an odd width or
+ *   an odd height (refused even when another size is 0, as in the batch form); in_pitch < 3*W; y_pitch < W; a c_pitch below its row
+ *   (W interleaved, W/2 planar); tiles <= 0; the overlap above.  Sizes and tile grids the planar forms refuse: the status they give
+ *   (MI_ERR_UNSUPPORTED).  width, height or n_frames of 0: MI_OK, nothing written.  Nothing is enqueued unless every frame passes the
+ *   checks: a bad last entry leaves the first frames' outputs untouched.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of
+ *   the same shape as the other device list forms; a captured graph holds the addresses it was captured with. */
+typedef struct mi_bgr_yuv420_frame_dev { const void* in; void* y; void* c0; void* c1; } mi_bgr_yuv420_frame_dev;  /* 32 bytes on LP64 */
+mi_status mi_equalize_hist_bgr_to_yuv420_frames_dev(mi_ctx* ctx, const mi_bgr_yuv420_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t y_pitch, size_t c_pitch, int chroma, int order, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_bgr_to_yuv420_frames_dev(mi_ctx* ctx, const mi_bgr_yuv420_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t y_pitch, size_t c_pitch, int chroma, int order, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
 
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at

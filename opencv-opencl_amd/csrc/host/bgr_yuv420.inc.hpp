@@ -53,7 +53,11 @@ mi_status check_bgr_yuv420(mi_ctx* c, const BgrYuv420Args& a, bool is_clahe, int
 
 // Stage 1 on frames f0 .. f0 + nf of a PLANAR call (MI_K_COLOR).  hist: count the luma into c->d_partial, *nparts_out workgroups a
 // frame.  *vec_out: the walk the kernel takes.  The grid is launch_bgr_to_nv12's: the same byte basis, the same cap.
-mi_status launch_bgr_to_yuv420(mi_ctx* c, hipStream_t s, const BgrYuv420Args& a, int f0, int nf, bool hist, int* nparts_out, bool* vec_out)
+// With a frame table (fl: one chunk of at most kFramesPerLaunch frames, bgr_yuv420_frames.inc.hpp): the same grid on the
+// *_frames_kernel entry; `a` then carries the shape, its base pointers (stand-ins for the vec rule) and frame strides are not used by
+// the kernel, and j.vec (*vec_out) says what the shape allows -- a byte-path frame of such a launch simply takes more grid-stride steps.
+mi_status launch_bgr_to_yuv420(mi_ctx* c, hipStream_t s, const BgrYuv420Args& a, int f0, int nf, bool hist, int* nparts_out, bool* vec_out,
+                               const BgrYuv420List* fl = nullptr)
 {
     BgrYuv420Job j{};
     j.in = a.in + (size_t)f0 * a.in_frame; j.y = a.y + (size_t)f0 * a.out_frame;
@@ -77,8 +81,10 @@ mi_status launch_bgr_to_yuv420(mi_ctx* c, hipStream_t s, const BgrYuv420Args& a,
     const bool rgb = a.order == MI_ORDER_RGB, cp = a.uv_mode == MI_UV_COPY;
 #define MI_BGR_YUV420_LAUNCH(O, U)                                                                                                   \
     do {                                                                                                                             \
-        if (hist) LAUNCH(c, s, MI_K_COLOR, (bgr_to_yuv420_hist_kernel<O, U, true>), grid, block, 0, j, c->d_partial);                 \
-        else      LAUNCH(c, s, MI_K_COLOR, (bgr_to_yuv420_hist_kernel<O, U, false>), grid, block, 0, j, (uint32_t*)nullptr);          \
+        if (fl && hist) LAUNCH(c, s, MI_K_COLOR, (bgr_to_yuv420_hist_frames_kernel<O, U, true>), grid, block, 0, j, *fl, c->d_partial);  \
+        else if (fl)    LAUNCH(c, s, MI_K_COLOR, (bgr_to_yuv420_hist_frames_kernel<O, U, false>), grid, block, 0, j, *fl, (uint32_t*)nullptr); \
+        else if (hist)  LAUNCH(c, s, MI_K_COLOR, (bgr_to_yuv420_hist_kernel<O, U, true>), grid, block, 0, j, c->d_partial);            \
+        else            LAUNCH(c, s, MI_K_COLOR, (bgr_to_yuv420_hist_kernel<O, U, false>), grid, block, 0, j, (uint32_t*)nullptr);     \
     } while (0)
     if (rgb && cp) MI_BGR_YUV420_LAUNCH(1, 1);
     else if (rgb)  MI_BGR_YUV420_LAUNCH(1, 0);

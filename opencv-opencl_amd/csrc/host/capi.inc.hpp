@@ -357,7 +357,10 @@ mi_status mi_ctx_synchronize(mi_ctx* c, void* stream)
 // written on 16 x 2 pixel groups / on 2 x 2 blocks, each by its own addresses; list calls move the onepass / twopass pair once a call
 // and do not touch "yuv420_bgr_vec" / "yuv420_bgr_bytes"),
 // "bgr_yuv420_vec" / "bgr_yuv420_bytes" (PLANAR-output mi_*_bgr_to_yuv420* calls whose conversion kernel walked 16 x 2 pixel groups / 2 x 2
-// blocks with byte accesses: one count per call with work to do; an INTERLEAVED output is the NV12 form's call and moves neither).
+// blocks with byte accesses: one count per call with work to do; an INTERLEAVED output is the NV12 form's call and moves neither),
+// "bgr_yuv420_list_frames_vec" / "bgr_yuv420_list_frames_bytes" (FRAMES of PLANAR mi_*_bgr_to_yuv420_frames_dev calls whose conversion
+// kernel walked 16 x 2 pixel groups / 2 x 2 blocks, each by its own addresses; list calls do not touch "bgr_yuv420_vec" /
+// "bgr_yuv420_bytes", and an INTERLEAVED list is the NV12 list form's call and moves none of the four).
 mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
 {
     ENTER(c);
@@ -395,6 +398,8 @@ mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
     if (!strcmp(name, "yuv420_bgr_list_frames_bytes")) { *out = c->yuv420_bgr_list_frames_bytes; return MI_OK; }
     if (!strcmp(name, "bgr_yuv420_vec")) { *out = c->bgr_yuv420_vec; return MI_OK; }
     if (!strcmp(name, "bgr_yuv420_bytes")) { *out = c->bgr_yuv420_bytes; return MI_OK; }
+    if (!strcmp(name, "bgr_yuv420_list_frames_vec")) { *out = c->bgr_yuv420_list_frames_vec; return MI_OK; }
+    if (!strcmp(name, "bgr_yuv420_list_frames_bytes")) { *out = c->bgr_yuv420_list_frames_bytes; return MI_OK; }
     return fail(c, MI_ERR_BAD_ARG, "unknown stat");
 }
 

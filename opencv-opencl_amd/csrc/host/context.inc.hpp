@@ -172,6 +172,8 @@ struct mi_ctx {
                                                                         // FRAMES of PLANAR mi_*_yuv420_to_bgr_frames_dev calls by that walk, each by its own addresses
     uint64_t bgr_yuv420_vec = 0, bgr_yuv420_bytes = 0;                  // statistics "bgr_yuv420_vec" / "bgr_yuv420_bytes": PLANAR-output mi_*_bgr_to_yuv420* calls by the
                                                                         // walk their conversion kernel took (16 x 2 pixel groups / 2 x 2 blocks with byte accesses)
+    unsigned long long bgr_yuv420_list_frames_vec = 0, bgr_yuv420_list_frames_bytes = 0;   // statistics "bgr_yuv420_list_frames_vec" / "bgr_yuv420_list_frames_bytes":
+                                                                        // FRAMES of PLANAR mi_*_bgr_to_yuv420_frames_dev calls by that walk, each by its own addresses
 };
 
 namespace {

@@ -56,5 +56,6 @@ using namespace mi;
 #include "host/yuv420_bgr.inc.hpp"     // planar 4:2:0 (I420 / YV12) or NV12 frames in, interleaved BGR / RGB out in the pass that maps the luma (software decoder -> model)
 #include "host/yuv420_bgr_frames.inc.hpp"   // ... as a list of separately allocated, pitched planes (a decoder's frame pool in, an image pool out)
 #include "host/bgr_yuv420.inc.hpp"     // interleaved BGR / RGB in, planar 4:2:0 (I420 / YV12) or NV12 out: convert and count, then map the luma in place (renderer / model -> software encoder)
+#include "host/bgr_yuv420_frames.inc.hpp"   // ... as a list of pitched device frames (an image pool in, a software encoder's frame pool out)
 #include "host/pipe.inc.hpp"
 #include "host/diff.inc.hpp"

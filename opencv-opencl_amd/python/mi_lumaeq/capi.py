@@ -63,6 +63,7 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_yuv420_to_bgr_batch_dev", "mi_clahe_yuv420_to_bgr_batch_dev", "mi_equalize_hist_yuv420_to_bgr", "mi_clahe_yuv420_to_bgr",
     "mi_equalize_hist_yuv420_to_bgr_frames_dev", "mi_clahe_yuv420_to_bgr_frames_dev",
     "mi_equalize_hist_bgr_to_yuv420_batch_dev", "mi_clahe_bgr_to_yuv420_batch_dev", "mi_equalize_hist_bgr_to_yuv420", "mi_clahe_bgr_to_yuv420",
+    "mi_equalize_hist_bgr_to_yuv420_frames_dev", "mi_clahe_bgr_to_yuv420_frames_dev",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -156,6 +157,18 @@ class Yuv420BgrFrameDev(C.Structure):
     def of(cls, y, c0, c1, out):
         """the same from torch CUDA tensors, raw device addresses or None"""
         return cls(*(None if p is None else _dptr(p) for p in (y, c0, c1, out)))
+
+
+class BgrYuv420FrameDev(C.Structure):
+    """mi_bgr_yuv420_frame_dev: one frame of a mi_*_bgr_to_yuv420_frames_dev list, its image address and its three output plane
+    addresses (device pointers).  c0 is always the U plane and c1 the V plane (a YV12 frame exchanges the two); an INTERLEAVED list has
+    its UV plane in c0 and its c1 is ignored (None)."""
+    _fields_ = [("in_", C.c_void_p), ("y", C.c_void_p), ("c0", C.c_void_p), ("c1", C.c_void_p)]
+
+    @classmethod
+    def of(cls, in_, y, c0, c1):
+        """the same from torch CUDA tensors, raw device addresses or None"""
+        return cls(*(None if p is None else _dptr(p) for p in (in_, y, c0, c1)))
 
 
 _YUV420_FMTS = {"nv12": Yuv420Planes.nv12, "i420": Yuv420Planes.i420, "yv12": Yuv420Planes.yv12}
@@ -283,6 +296,8 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_bgr_to_yuv420_batch_dev.argtypes = [vp, vp, sz, sz, yp, i, i, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_bgr_to_yuv420.argtypes = [vp, vp, sz, yp, i, i, i, i]
     L.mi_clahe_bgr_to_yuv420.argtypes = [vp, vp, sz, yp, i, i, i, i, d, i, i]
+    L.mi_equalize_hist_bgr_to_yuv420_frames_dev.argtypes = [vp, C.POINTER(BgrYuv420FrameDev), i, i, i, sz, sz, sz, i, i, i, vp]
+    L.mi_clahe_bgr_to_yuv420_frames_dev.argtypes = [vp, C.POINTER(BgrYuv420FrameDev), i, i, i, sz, sz, sz, i, i, i, d, i, i, vp]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -1224,6 +1239,35 @@ class Context:
         self._chk(self._L.mi_clahe_bgr_to_yuv420(self._h, img.ctypes.data, step, C.byref(b), w, h, int(order), int(uv_mode),
                                                float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_bgr_to_yuv420")
         return out
+
+    @staticmethod
+    def _bgr_yuv420_list(frames):
+        """frames: a sequence of BgrYuv420FrameDev, or a ctypes array of them.  Returns the array and its length."""
+        if isinstance(frames, C.Array):
+            return frames, len(frames)
+        frames = list(frames)
+        arr = (BgrYuv420FrameDev * max(1, len(frames)))()
+        for k, f in enumerate(frames):
+            arr[k] = f
+        return arr, len(frames)
+
+    def equalize_hist_bgr_to_yuv420_frames_dev(self, frames, width, height, in_pitch, y_pitch, c_pitch, chroma, order=ORDER_BGR,
+                                               uv_mode=UV_COPY, stream=0):
+        """mi_equalize_hist_bgr_to_yuv420_frames_dev.  frames: BgrYuv420FrameDev entries, one per frame, every image and every plane at
+        its own device address (an image pool in, a software encoder's frame pool out); one shape, one set of pitches and one chroma
+        layout for the call."""
+        arr, n = self._bgr_yuv420_list(frames)
+        self._chk(self._L.mi_equalize_hist_bgr_to_yuv420_frames_dev(self._h, arr, n, int(width), int(height), int(in_pitch), int(y_pitch),
+                                                                  int(c_pitch), int(chroma), int(order), int(uv_mode), stream),
+                  "mi_equalize_hist_bgr_to_yuv420_frames_dev")
+
+    def clahe_bgr_to_yuv420_frames_dev(self, frames, width, height, in_pitch, y_pitch, c_pitch, chroma, order=ORDER_BGR, uv_mode=UV_COPY,
+                                       clip_limit=2.0, tiles_x=8, tiles_y=8, stream=0):
+        """mi_clahe_bgr_to_yuv420_frames_dev; arguments as equalize_hist_bgr_to_yuv420_frames_dev, plus the CLAHE parameters."""
+        arr, n = self._bgr_yuv420_list(frames)
+        self._chk(self._L.mi_clahe_bgr_to_yuv420_frames_dev(self._h, arr, n, int(width), int(height), int(in_pitch), int(y_pitch),
+                                                          int(c_pitch), int(chroma), int(order), int(uv_mode), float(clip_limit),
+                                                          int(tiles_x), int(tiles_y), stream), "mi_clahe_bgr_to_yuv420_frames_dev")
 
     # ---- colour-domain neighbours (N3) ----
     @staticmethod

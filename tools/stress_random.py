@@ -3,7 +3,8 @@
 tiles (several tiles per histogram workgroup), 16-bit CLAHE at random value ranges, the 4:2:0 codes at random aligned / unaligned sizes, NV12 in / BGR out
 at random pitched layouts (aligned and not) and tile grids on both sides of its one-pass conditions, as a batch and as a frame list
 (random order, every image at its own offset), and the same pixels from planar chroma (I420 / YV12 in, BGR out) at chroma layouts that are
-multiples of 8 or of 1, as a batch and as a frame list against the batch form's bytes.
+multiples of 8 or of 1, as a batch and as a frame list against the batch form's bytes, and the way back on a frame list (those images in,
+I420 / YV12 planes out at that layout, every frame at an offset of its own) against the oracle.
     python tools/stress_random.py [seconds] [seed] [option=value ...]        prints a line every ~15 s, exits non-zero on the first mismatch"""
 import sys, time
 sys.path.insert(0, "opencv-opencl_amd/python"); sys.path.insert(0, ".")
@@ -15,7 +16,7 @@ rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 ctx = mi_lumaeq.Context(0)
 for kv in sys.argv[3:]:                                          # name=value options for the whole run, e.g. clahe16_wide=2 (mid kernel always launched)
     k_, v_ = kv.split("="); ctx.set_option(k_, int(v_)); print("option", k_, "=", v_, flush=True)
-t0 = last = time.time(); n = {"roi": 0, "grid": 0, "small": 0, "c16": 0, "420": 0, "nv12": 0, "nv12bgr": 0, "yuv420bgr": 0, "yuv420bgrlist": 0}
+t0 = last = time.time(); n = {"roi": 0, "grid": 0, "small": 0, "c16": 0, "420": 0, "nv12": 0, "nv12bgr": 0, "yuv420bgr": 0, "yuv420bgrlist": 0, "bgryuv420list": 0}
 def dev(a): return xfer.to_device(np.ascontiguousarray(a))
 def fail(what, *info):
     print("MISMATCH", what, info, flush=True); sys.exit(1)
@@ -163,6 +164,28 @@ while time.time() - t0 < budget:
         if not np.array_equal(out, want): fail("yuv420bgr list", w, h, nf, op, order, clip, tx, ty, al, yp, cp, g0, g1, pfi, yv12, opi, off, ooff, perm, jit, np.flatnonzero(out != want)[:8])
         if not np.array_equal(xfer.to_host(d_pin), pimg): fail("yuv420bgr list wrote its input", w, h, nf, op)
         n["yuv420bgrlist"] += 1
+        # the way back on a list: those images, where the list call above left them, in; planar 4:2:0 frames out at the planar layout
+        # above (U and V exchanged between c0 and c1 by the layout alone), the frames in another random order, one in three some bytes
+        # past where its neighbours lie (that frame alone takes the byte walk), against the oracle
+        perm = [int(v) for v in rng.permutation(nf)]; jy = [int(rng.integers(0, 16)) if rng.integers(0, 3) == 0 else 0 for _ in range(nf)]
+        uvm = int(rng.integers(0, 2)); po = [off + f * (pfi + 16) + jy[f] for f in range(nf)]
+        d_out5 = torch.full((off + (pfi + 16) * nf + 64,), 0x5A, dtype=torch.uint8, device="cuda"); want = np.full(d_out5.numel(), 0x5A, np.uint8)
+        for f in range(nf):
+            px = imgs[f].reshape(h, w, 3); px = px if order == 0 else px[:, :, ::-1]
+            eqf = oracle.nv12_frame(oracle.bgr_to_nv12(np.ascontiguousarray(px)), w, h, uv_mode=uvm, op=op, clip_limit=clip, tiles_x=tx, tiles_y=ty)
+            uvr = eqf[w * h:].reshape(h // 2, w)
+            want[po[f]: po[f] + yp * h].reshape(h, yp)[:, :w] = eqf[: w * h].reshape(h, w)
+            want[po[f] + u_off: po[f] + u_off + csz].reshape(h // 2, cp)[:, : w // 2] = uvr[:, 0::2]
+            want[po[f] + v_off: po[f] + v_off + csz].reshape(h // 2, cp)[:, : w // 2] = uvr[:, 1::2]
+        b5 = d_out5.data_ptr()
+        ents = [mi_lumaeq.BgrYuv420FrameDev(d_out4.data_ptr() + oo[f], b5 + po[f], b5 + po[f] + u_off, b5 + po[f] + v_off) for f in perm]
+        ba = (ents, w, h, opi, yp, cp, mi_lumaeq.CHROMA_PLANAR, order, uvm)
+        if op == 0: ctx.equalize_hist_bgr_to_yuv420_frames_dev(*ba)
+        else: ctx.clahe_bgr_to_yuv420_frames_dev(*ba, clip, tx, ty)
+        ctx.synchronize(); got = xfer.to_host(d_out5)
+        if not np.array_equal(got, want): fail("bgryuv420 list", w, h, nf, op, order, uvm, clip, tx, ty, al, opi, yp, cp, g0, g1, pfi, yv12, off, perm, jy, np.flatnonzero(got != want)[:8])
+        if not np.array_equal(xfer.to_host(d_out4), out): fail("bgryuv420 list wrote its input", w, h, nf, op)
+        n["bgryuv420list"] += 1
     else:           # 4:2:0 codes
         w, h = int(rng.integers(1, 60)) * (16 if rng.integers(0, 2) else 2), int(rng.integers(1, 40)) * 2
         bgr = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
