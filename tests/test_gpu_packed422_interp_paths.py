@@ -1,7 +1,10 @@
 """Every rung of the CLAHE interpolation ladder on packed 4:2:2 input (YUY2 / UYVY), through every device form: packed out and NV12
 out, each as a strided batch and as a list of frames.  The host picks the interpolation kernel from (writer, list or batch, float or
 quad tables, clahe_fp_contract, format, LDS or global tables); the four sizes below are the smallest that reach each branch of that
-choice, and the options clahe_float_tables and clahe_fp_contract are set both ways, so that every instantiation runs.
+choice, and the options clahe_float_tables and clahe_fp_contract are set both ways, so that every instantiation runs.  64 x 8 and
+128 x 8 have tiles of 4 x 4 and 2 x 4 pixels: 1 / tile is exact there, FMA and mul + add round alike and both arithmetic modes give the
+same bytes, so those two rungs cannot tell an FMA body from a plain one.  96 x 10 and 192 x 10 (tiles 6 x 5 and 3 x 5) reach the same
+two kernels on shapes where the modes differ; their luma is tests/clahe_u8_rungs.py content, on which the test first shows that they do.
 
     kMaxPairsLdsF32 = 15, kMaxPairsLds = 63, kInterpPx = 16, clahe_seg_pairs = 9 (default); pairs = tiles_x + 1
     64 x 48,   8 x 8:   9 pairs <= 15: one float table; uchar quads when clahe_float_tables = 0
@@ -9,6 +12,8 @@ choice, and the options clahe_float_tables and clahe_fp_contract are set both wa
                         column segments (112 groups in ceil(112 / 42) = 3 segments); quads in one segment when clahe_float_tables = 0
     64 x 8,    16 x 2:  17 pairs > 15, tile_w = 4: (9 - 3) * 4 / 16 = 1 < 40, quads whatever clahe_float_tables says
     128 x 8,   64 x 2:  65 pairs > 63: the global-LUT kernel
+    96 x 10,   16 x 2:  17 pairs > 15, tile_w = 6: (9 - 3) * 6 / 16 = 2 < 40, quads again, on tiles that are no power of two
+    192 x 10,  64 x 2:  65 pairs > 63: the global-LUT kernel again, tile_w = 3
 
 The expected luma is oracle.clahe on the gathered luma in the arithmetic mode of the call (oracle.set_fp_contract); chroma is copied
 (packed out) or the rounding mean of each row pair (NV12 out).  Every plane lies in a sentinel-filled allocation at a padded pitch,
@@ -19,6 +24,7 @@ import torch
 
 import mi_lumaeq
 import oracle
+import clahe_u8_rungs
 from mi_lumaeq import synth, UV_COPY, FMT_YUY2, FMT_UYVY
 
 pytestmark = pytest.mark.gpu
@@ -26,8 +32,10 @@ SENT = 0x5A
 N = 3
 DISTS = ["D1", "D2", "D3"]
 CLIP = 2.0
-# (width, height, tiles_x, tiles_y): plain float tables, column-segment float tables, quad fallback of a wide grid, global LUTs
-SHAPES = [(64, 48, 8, 8), (1792, 8, 16, 2), (64, 8, 16, 2), (128, 8, 64, 2)]
+# (width, height, tiles_x, tiles_y): plain float tables, column-segment float tables, quad fallback of a wide grid, global LUTs;
+# then the last two again on tiles where the arithmetic mode shows
+SHAPES = [(64, 48, 8, 8), (1792, 8, 16, 2), (64, 8, 16, 2), (128, 8, 64, 2), (96, 10, 16, 2), (192, 10, 64, 2)]
+MODE_SHAPES = SHAPES[4:]                                         # luma from clahe_u8_rungs.content, not from D1 / D2 / D3
 FORMS = ["packed_batch", "packed_list", "nv12_batch", "nv12_list"]
 FMTS = [FMT_YUY2, FMT_UYVY]
 # (clahe_float_tables, clahe_fp_contract); the first is the default pair, whose bytes the other pair with fp_contract 0 must repeat
@@ -60,6 +68,21 @@ def uv_mean(c):
 _ref_cache = {}
 
 
+def y_plane(shape, k):
+    """The luma of frame k of a shape."""
+    w, h = shape[:2]
+    return clahe_u8_rungs.content(w, h, 100 + k) if shape in MODE_SHAPES else synth.y_plane(w, h, DISTS[k], 500 + k)
+
+
+def packed_frame(shape, fmt, k):
+    w, h = shape[:2]
+    f = synth.packed422_frame(w, h, fmt, DISTS[k], 500 + k)
+    if shape in MODE_SHAPES:
+        f = f.copy()
+        f[:, fmt - 2:2 * w:2] = y_plane(shape, k)
+    return f
+
+
 def y_ref(shape, k, contract):
     """oracle.clahe on the luma of frame k of a shape (the same plane in both formats), computed once per arithmetic mode."""
     key = (shape, k, contract)
@@ -67,7 +90,7 @@ def y_ref(shape, k, contract):
         w, h, tx, ty = shape
         old = oracle.set_fp_contract(bool(contract))
         try:
-            _ref_cache[key] = oracle.clahe(synth.y_plane(w, h, DISTS[k], 500 + k), CLIP, tx, ty)
+            _ref_cache[key] = oracle.clahe(y_plane(shape, k), CLIP, tx, ty)
         finally:
             oracle.set_fp_contract(old)
     return _ref_cache[key]
@@ -191,11 +214,13 @@ def test_every_rung(c, shape, form):
     oracle's in the call's arithmetic mode, and with clahe_fp_contract = 0 also those of the default tables (the same bytes on
     every path)."""
     w, h = shape[:2]
+    if shape in MODE_SHAPES:                                     # the two arithmetic modes are told apart on this shape
+        assert any(not np.array_equal(y_ref(shape, k, 0), y_ref(shape, k, 1)) for k in range(N)), (shape, "both modes give the same bytes")
     case = Case(form, shape)
     try:
         for fmt in FMTS:
-            frames = [synth.packed422_frame(w, h, fmt, DISTS[k], 500 + k) for k in range(N)]
-            assert all(np.array_equal(luma(f, w, fmt), synth.y_plane(w, h, DISTS[k], 500 + k)) for k, f in enumerate(frames))
+            frames = [packed_frame(shape, fmt, k) for k in range(N)]
+            assert all(np.array_equal(luma(f, w, fmt), y_plane(shape, k)) for k, f in enumerate(frames))
             default = None
             for float_tables, contract in OPTIONS:
                 why = (form, shape, fmt, float_tables, contract)
