@@ -526,6 +526,60 @@ mi_status mi_clahe_nv12_to_bgr_frames_dev(mi_ctx* ctx, const mi_nv12_bgr_frame_d
         int width, int height, size_t y_pitch, size_t uv_pitch, size_t out_pitch, int order,
         double clip_limit, int tiles_x, int tiles_y, void* stream);
 
+/* mi_*_packed422_to_bgr*: packed 4:2:2 frames in (YUY2 / UYVY), interleaved 8-bit BGR (or RGB) images out, in the pass that equalizes --
+ * capture card -> display, image writer or model.  Per frame the result is what OpenCV 4.4 gives for
+ *     cv::extractChannel(frame, y, off);  cv::equalizeHist(y, y)  /  clahe->apply(y, y);  cv::insertChannel(y, frame, off);
+ *     cv::cvtColor(frame, bgr, cv::COLOR_YUV2BGR_YUY2);              (_UYVY for MI_FMT_UYVY; COLOR_YUV2RGB_* for MI_ORDER_RGB)
+ * The packed frame is read twice (histograms, then map) and 3 bytes per pixel are written: 7 bytes per pixel.  The two-call route,
+ * mi_*_packed422_to_nv12_batch_dev followed by mi_cvt_color_420_u8_batch_dev(MI_COLOR_YUV2BGR_NV12), moves 5.5 + 4.5 = 10, needs an NV12
+ * batch in between and gives DIFFERENT pixels: it halves the chroma vertically, this form keeps the chroma of every row.
+ *   input  : exactly what mi_*_packed422_batch_dev takes: frame f at d_in + f * in_frame_stride, H rows of 2*W bytes at in_pitch >= 2*W;
+ *            the pointer, the pitch and the frame stride are multiples of 4; `width` is even, `height` any value >= 1 (neither side
+ *            subsamples vertically: odd heights are legal).  The input is never written.
+ *   format : HERE THE CHROMA ORDER MATTERS, unlike in every other packed form (the comment on MI_FMT_YUY2 above, "the chroma order is
+ *            irrelevant", does not hold for these entry points): MI_FMT_YUY2 means exactly Y0 U Y1 V, MI_FMT_UYVY exactly U Y0 V Y1.  A
+ *            YVYU or VYUY frame passed as one of the two comes out with U and V swapped; those layouts are not supported by this form.
+ *   output : frame f at d_out + f * out_frame_stride, H rows of 3*W bytes at out_pitch >= 3*W: B, G, R per pixel (MI_ORDER_BGR) or
+ *            R, G, B (MI_ORDER_RGB).  Only the 3*W bytes of each output row are written: not the pitch padding, not the gap between
+ *            frames.  No alignment is required of d_out, out_pitch or out_frame_stride -- a tight image with W % 4 == 2 is accepted.
+ *            Speed note: when d_out, out_pitch and out_frame_stride are multiples of 4 the kernels store 16 bytes per access (dwords
+ *            in the ragged last 16-column group of a row), otherwise they take the byte-granular path -- slower, the same bytes out.
+ *   luma   : byte for byte what mi_equalize_hist_u8_batch_dev / mi_clahe_u8_batch_dev return on the gathered W x H luma plane (same
+ *            clahe_fp_contract option, REFLECT_101 padding when the tile grid does not divide the frame, the same fallback for tile
+ *            grids too wide for the LDS pair table as the other packed forms).
+ *   pixels : (x, y) and (x+1, y) of a macropixel are decoded with that macropixel's own U and V, in the arithmetic of
+ *            mi_cvt_color_420_u8 (MI_COLOR_YUV2BGR_NV12): OpenCV 4.4's ITUR_BT_601 integer decode, shift 20.  No vertical sharing, no
+ *            filtering, and no uv_mode parameter (the NV12 -> BGR form has none either).
+ * Every shape runs in one pass: there is no scratch Y plane and no two-pass fallback.  Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the
+ * context's pipe has frames pending and hipGraph capture after one eager call of the same shape as the other batched device forms.
+ * Never the fused equalizeHist kernel nor the single-launch histogram + LUT kernel; launches are charged to the existing profiling
+ * slots by role: MI_K_HIST, MI_K_EQ_LUT, MI_K_LUT_APPLY, MI_K_TILE_HIST, MI_K_TILE_LUT, MI_K_CLAHE_INTERP (equalizeHist on up to one chunk
+ * of frames: one MI_K_HIST, one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch).  There is no frame-list form yet.
+ * mi_equalize_hist_packed422_to_bgr / mi_clahe_packed422_to_bgr: ONE packed host frame in, one image out, synchronous.  The input side
+ *   follows the rules of mi_*_packed422 (`in` and in_pitch multiples of 4, in_pitch >= 2*W; only the 2*W bytes of each row are read),
+ *   the output side those of mi_*_nv12_to_bgr (any address, any out_step >= 3*W; only the 3*W bytes of each row are written).  Tight
+ *   buffers in pinned memory (mi_host_register) are DMA'd as they are, everything else goes through the context's pinned staging.
+ *   Whatever the call returns, no copy on in / out is in flight any more when it returns.  MI_ERR_BAD_ARG when the rows of the image
+ *   meet the rows of the input; W*H beyond what mi_cvt_color_420_u8 accepts: MI_ERR_UNSUPPORTED.
+ * Errors, MI_ERR_BAD_ARG: a null ctx or frame pointer, an odd width (refused even when another size is 0, as in the packed forms), a
+ * negative size, in_pitch < 2*W or out_pitch < 3*W, an input pointer / pitch / frame stride that is not a multiple of 4, a `format` or
+ * an `order` other than the two, tiles <= 0, d_out == d_in (there is no in-place form).  Any other overlap of input and output:
+ * undefined, not checked.  width, height or n_frames of 0: MI_OK, nothing written.  Sizes and tile grids the planar forms refuse: the
+ * status they give (MI_ERR_UNSUPPORTED), nothing written.  Nothing is enqueued unless all checks pass. */
+mi_status mi_equalize_hist_packed422_to_bgr_batch_dev(mi_ctx* ctx,
+        const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        void* d_out, size_t out_pitch, size_t out_frame_stride,
+        int width, int height, int n_frames, int format, int order, void* stream);
+mi_status mi_clahe_packed422_to_bgr_batch_dev(mi_ctx* ctx,
+        const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        void* d_out, size_t out_pitch, size_t out_frame_stride,
+        int width, int height, int n_frames, int format, int order,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
+mi_status mi_equalize_hist_packed422_to_bgr(mi_ctx* ctx, const uint8_t* in, size_t in_pitch, uint8_t* out, size_t out_step,
+        int width, int height, int format, int order);
+mi_status mi_clahe_packed422_to_bgr(mi_ctx* ctx, const uint8_t* in, size_t in_pitch, uint8_t* out, size_t out_step,
+        int width, int height, int format, int order, double clip_limit, int tiles_x, int tiles_y);
+
 /* mi_*_bgr_to_nv12*: interleaved 8-bit BGR (or RGB) images in, pitched NV12 frames out with the luma equalized -- renderer, model output
  * or image reader -> hardware encoder without an I420 intermediate and without an interleave of U and V outside the library.  Per frame
  * the bytes are what OpenCV 4.4 gives for

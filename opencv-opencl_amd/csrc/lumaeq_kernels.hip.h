@@ -40,6 +40,8 @@
 //   kernels/yuv420_bgr.hip.h       the pixel-writing stages of planar 4:2:0 (I420 / YV12) in, interleaved BGR / RGB out: those of nv12_bgr.hip.h
 //                                  with the chroma loaded from two planes and zipped in registers; their *_frames_kernel entries on a
 //                                  list of {y, u, v, out} addresses
+//   kernels/packed422_bgr.hip.h    the pixel-writing stages of packed 4:2:2 in, interleaved BGR / RGB out: LUT apply / CLAHE blend + decode,
+//                                  every row with its own chroma
 #pragma once
 #include "kernels/common.hip.h"
 #include "kernels/equalize.hip.h"
@@ -57,3 +59,4 @@
 #include "kernels/bgr_yuv420.hip.h"
 #include "kernels/yuv420.hip.h"
 #include "kernels/yuv420_bgr.hip.h"
+#include "kernels/packed422_bgr.hip.h"

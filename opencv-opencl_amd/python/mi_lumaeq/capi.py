@@ -54,6 +54,8 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_packed422_to_nv12_batch_dev", "mi_clahe_packed422_to_nv12_batch_dev",
     "mi_equalize_hist_packed422_to_nv12_frames_dev", "mi_clahe_packed422_to_nv12_frames_dev",
     "mi_equalize_hist_packed422_to_nv12", "mi_clahe_packed422_to_nv12",
+    "mi_equalize_hist_packed422_to_bgr_batch_dev", "mi_clahe_packed422_to_bgr_batch_dev",
+    "mi_equalize_hist_packed422_to_bgr", "mi_clahe_packed422_to_bgr",
     "mi_equalize_hist_nv12_to_bgr_batch_dev", "mi_clahe_nv12_to_bgr_batch_dev", "mi_equalize_hist_nv12_to_bgr", "mi_clahe_nv12_to_bgr",
     "mi_equalize_hist_nv12_to_bgr_frames_dev", "mi_clahe_nv12_to_bgr_frames_dev",
     "mi_equalize_hist_bgr_to_nv12_batch_dev", "mi_clahe_bgr_to_nv12_batch_dev", "mi_equalize_hist_bgr_to_nv12", "mi_clahe_bgr_to_nv12",
@@ -267,6 +269,10 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_packed422_to_nv12_frames_dev.argtypes = [vp, C.POINTER(Packed422Nv12FrameDev), i, i, i, sz, sz, sz, i, i, d, i, i, vp]
     L.mi_equalize_hist_packed422_to_nv12.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, i]
     L.mi_clahe_packed422_to_nv12.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, i, d, i, i]
+    L.mi_equalize_hist_packed422_to_bgr_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, vp]
+    L.mi_clahe_packed422_to_bgr_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_packed422_to_bgr.argtypes = [vp, vp, sz, vp, sz, i, i, i, i]
+    L.mi_clahe_packed422_to_bgr.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, d, i, i]
     L.mi_equalize_hist_nv12_to_bgr_batch_dev.argtypes = [vp, vp, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp]
     L.mi_clahe_nv12_to_bgr_batch_dev.argtypes = [vp, vp, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_nv12_to_bgr.argtypes = [vp, vp, vp, sz, i, i, i]
@@ -903,6 +909,59 @@ class Context:
                                                    uv_out.ctypes.data, _step(uv_out), int(width), int(h), int(fmt), int(uv_mode),
                                                    float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_packed422_to_nv12")
         return y_out, uv_out
+
+    # ---- packed 4:2:2 in, interleaved BGR / RGB out in the pass that maps the luma: every row keeps its own chroma ----
+    def equalize_hist_packed422_to_bgr_batch_dev(self, d_in, d_out, width, height, n_frames, fmt=FMT_YUY2, order=ORDER_BGR,
+                                                 in_pitch=None, in_frame=None, out_pitch=None, out_frame=None, stream=0):
+        """mi_equalize_hist_packed422_to_bgr_batch_dev: n_frames packed frames in, interleaved BGR / RGB images out (torch tensors or
+        raw addresses).  fmt says the chroma order too: FMT_YUY2 is Y0 U Y1 V, FMT_UYVY is U Y0 V Y1.  Tight layouts are the defaults:
+        in_pitch 2*W, in_frame in_pitch * H, out_pitch 3*W, out_frame out_pitch * H."""
+        ip = 2 * int(width) if in_pitch is None else int(in_pitch)
+        fi = ip * int(height) if in_frame is None else int(in_frame)
+        op = 3 * int(width) if out_pitch is None else int(out_pitch)
+        fo = op * int(height) if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_equalize_hist_packed422_to_bgr_batch_dev(self._h, _dptr(d_in), ip, fi, _dptr(d_out), op, fo, int(width),
+                                                                    int(height), int(n_frames), int(fmt), int(order), stream),
+                  "mi_equalize_hist_packed422_to_bgr_batch_dev")
+
+    def clahe_packed422_to_bgr_batch_dev(self, d_in, d_out, width, height, n_frames, fmt=FMT_YUY2, order=ORDER_BGR, clip_limit=2.0,
+                                         tiles_x=8, tiles_y=8, in_pitch=None, in_frame=None, out_pitch=None, out_frame=None, stream=0):
+        """mi_clahe_packed422_to_bgr_batch_dev; arguments as equalize_hist_packed422_to_bgr_batch_dev, plus the CLAHE parameters."""
+        ip = 2 * int(width) if in_pitch is None else int(in_pitch)
+        fi = ip * int(height) if in_frame is None else int(in_frame)
+        op = 3 * int(width) if out_pitch is None else int(out_pitch)
+        fo = op * int(height) if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_clahe_packed422_to_bgr_batch_dev(self._h, _dptr(d_in), ip, fi, _dptr(d_out), op, fo, int(width), int(height),
+                                                            int(n_frames), int(fmt), int(order), float(clip_limit), int(tiles_x),
+                                                            int(tiles_y), stream), "mi_clahe_packed422_to_bgr_batch_dev")
+
+    def _packed_bgr_host(self, frame, width, out, name):
+        frame = self._packed_host(frame, width, name)
+        h = frame.shape[0]
+        if out is None:
+            out = np.empty((h, max(int(width), 0), 3), np.uint8)
+        out = self._host3(out, name)
+        if out.shape[:2] != (h, width):
+            raise MiError(1, name, "out must be an H x W x 3 uint8 array (rows may be padded)")
+        return frame, out, (int(out.strides[0]) if h > 1 else max(int(out.strides[0]), 3 * int(width)))
+
+    def equalize_hist_packed422_to_bgr(self, frame: np.ndarray, width: int, fmt: int = FMT_YUY2, order: int = ORDER_BGR,
+                                       out: np.ndarray | None = None) -> np.ndarray:
+        """mi_equalize_hist_packed422_to_bgr on a host frame: an H x pitch-bytes uint8 array (pitch >= 2*W) in, the H x W x 3 image
+        out -- `out` when given (a view with padded rows or at an odd address included), else a new tight array."""
+        frame, out, step = self._packed_bgr_host(frame, int(width), out, "equalize_hist_packed422_to_bgr")
+        self._chk(self._L.mi_equalize_hist_packed422_to_bgr(self._h, frame.ctypes.data, _step(frame), out.ctypes.data, step, int(width),
+                                                          int(frame.shape[0]), int(fmt), int(order)), "mi_equalize_hist_packed422_to_bgr")
+        return out
+
+    def clahe_packed422_to_bgr(self, frame: np.ndarray, width: int, fmt: int = FMT_YUY2, order: int = ORDER_BGR,
+                               clip_limit: float = 2.0, tiles_x: int = 8, tiles_y: int = 8, out: np.ndarray | None = None) -> np.ndarray:
+        """mi_clahe_packed422_to_bgr; arguments as equalize_hist_packed422_to_bgr, plus the CLAHE parameters."""
+        frame, out, step = self._packed_bgr_host(frame, int(width), out, "clahe_packed422_to_bgr")
+        self._chk(self._L.mi_clahe_packed422_to_bgr(self._h, frame.ctypes.data, _step(frame), out.ctypes.data, step, int(width),
+                                                  int(frame.shape[0]), int(fmt), int(order), float(clip_limit), int(tiles_x),
+                                                  int(tiles_y)), "mi_clahe_packed422_to_bgr")
+        return out
 
     # ---- NV12 in, interleaved BGR / RGB out in the pass that maps the luma ----
     @staticmethod
