@@ -554,7 +554,7 @@ mi_status mi_clahe_nv12_to_bgr_frames_dev(mi_ctx* ctx, const mi_nv12_bgr_frame_d
  * context's pipe has frames pending and hipGraph capture after one eager call of the same shape as the other batched device forms.
  * Never the fused equalizeHist kernel nor the single-launch histogram + LUT kernel; launches are charged to the existing profiling
  * slots by role: MI_K_HIST, MI_K_EQ_LUT, MI_K_LUT_APPLY, MI_K_TILE_HIST, MI_K_TILE_LUT, MI_K_CLAHE_INTERP (equalizeHist on up to one chunk
- * of frames: one MI_K_HIST, one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch).  There is no frame-list form yet.
+ * of frames: one MI_K_HIST, one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch).  The frame-list form, mi_*_packed422_to_bgr_frames_dev, follows below.
  * mi_equalize_hist_packed422_to_bgr / mi_clahe_packed422_to_bgr: ONE packed host frame in, one image out, synchronous.  The input side
  *   follows the rules of mi_*_packed422 (`in` and in_pitch multiples of 4, in_pitch >= 2*W; only the 2*W bytes of each row are read),
  *   the output side those of mi_*_nv12_to_bgr (any address, any out_step >= 3*W; only the 3*W bytes of each row are written).  Tight
@@ -579,6 +579,44 @@ mi_status mi_equalize_hist_packed422_to_bgr(mi_ctx* ctx, const uint8_t* in, size
         int width, int height, int format, int order);
 mi_status mi_clahe_packed422_to_bgr(mi_ctx* ctx, const uint8_t* in, size_t in_pitch, uint8_t* out, size_t out_step,
         int width, int height, int format, int order, double clip_limit, int tiles_x, int tiles_y);
+/* mi_*_packed422_to_bgr_frames_dev: the same conversion on a LIST of device frames, each at its own two addresses -- a capture device's
+ * buffer pool in (every YUY2 / UYVY buffer its own pitched allocation, as for mi_*_packed422_frames_dev), a pool of images out (one
+ * tensor or cv::Mat per frame).  Repacking both pools into a batch moves 10 bytes per pixel on top of the 7 of the conversion; one batch
+ * call per buffer costs a launch sequence per frame.  `frames` is a host array of n_frames entries, read only during the call; the
+ * pointers in it are device pointers on the context's device.
+ * Shape: all frames of one call share width, height, format, order and the two pitches (bytes between rows); each has its own addresses:
+ *   in : H rows of 2*W bytes at in_pitch >= 2*W     out: H rows of 3*W bytes at out_pitch >= 3*W -- B, G, R per pixel (MI_ORDER_BGR) or
+ *                                                        R, G, B (MI_ORDER_RGB)
+ * Bytes: per frame exactly what mi_*_packed422_to_bgr_batch_dev writes for the same pixels -- the luma of the planar forms, every row
+ * decoded with its own chroma, MI_FMT_YUY2 exactly Y0 U Y1 V and MI_FMT_UYVY exactly U Y0 V Y1 (the chroma order matters, as above); the
+ * clahe_fp_contract and clahe_float_tables options apply as in the batch form, as do REFLECT_101 padding and the fallback for tile grids
+ * too wide for the LDS pair table.  Every CLAHE shape runs in one pass: there is no scratch Y plane and no two-pass fallback.
+ * Input side: the rules of mi_*_packed422_frames_dev.  Width is even, height any value >= 1; in_pitch is a multiple of 4; every `in` is
+ * a multiple of 4, at its own alignment modulo 16.  The same input may appear in several entries.  The inputs are never written.
+ * Output side: NO alignment rule -- any `out`, odd addresses included, any out_pitch >= 3*W, a tight image with W % 4 == 2 included.
+ * Only the 3*W bytes of each output row are written, not the pitch padding.  The per-frame address decides the store width: when
+ * out_pitch is a multiple of 4, a frame whose `out` is a multiple of 4 stores 16 bytes per access (dwords in the ragged last 16-column
+ * group of a row) and any other frame of the same call stores bytes, while its neighbours stay wide -- slower, the same bytes out.
+ * mi_ctx_get_stat "packed422_bgr_list_frames_wide" / "packed422_bgr_list_frames_bytes" count the FRAMES (not calls) of each kind, for
+ * calls that were enqueued.
+ * Overlap: there is no in-place form.  MI_ERR_BAD_ARG when the rows of a frame's image meet the rows of its own input (compared as
+ * address ranges).  Images that overlap each other or ANOTHER frame's input give undefined results and are not checked.
+ * Launches are charged to the same profiling slots as the batch form, per chunk of 128 frames of the list (equalizeHist: one MI_K_HIST,
+ * one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch per chunk).  Never the fused equalizeHist kernel nor the single-launch histogram + LUT
+ * kernel.  Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call
+ * of the same shape as the other device list forms; a captured graph holds the addresses it was captured with.
+ * Errors, MI_ERR_BAD_ARG: a null ctx, a null `frames` with n_frames > 0, a null in / out in any entry, an `in` that is not a multiple
+ * of 4, an odd width (refused even when another size is 0), a negative size, in_pitch < 2*W or not a multiple of 4, out_pitch < 3*W, a
+ * `format` or an `order` other than the two, tiles <= 0, the overlap above.  Sizes and tile grids the batch form refuses (more than 65535
+ * tiles, a height above 65535 with tiles_x > 62, what the planar forms refuse): the status it gives (MI_ERR_UNSUPPORTED).  width,
+ * height or n_frames of 0: MI_OK, nothing written.  Nothing is enqueued unless every frame passes the checks: a bad last entry leaves
+ * the first frames' images untouched. */
+typedef struct mi_packed422_bgr_frame_dev { const void* in; void* out; } mi_packed422_bgr_frame_dev;   /* 16 bytes on LP64 */
+mi_status mi_equalize_hist_packed422_to_bgr_frames_dev(mi_ctx* ctx, const mi_packed422_bgr_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t out_pitch, int format, int order, void* stream);
+mi_status mi_clahe_packed422_to_bgr_frames_dev(mi_ctx* ctx, const mi_packed422_bgr_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t out_pitch, int format, int order,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
 
 /* mi_*_bgr_to_nv12*: interleaved 8-bit BGR (or RGB) images in, pitched NV12 frames out with the luma equalized -- renderer, model output
  * or image reader -> hardware encoder without an I420 intermediate and without an interleave of U and V outside the library.  Per frame

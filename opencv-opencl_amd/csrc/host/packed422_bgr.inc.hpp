@@ -6,8 +6,7 @@
 // row.  The stage sequences are packed422.inc.hpp's own (one MI_K_HIST, one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch per chunk; tile
 // histograms -> interpolation): same scratch, same chunks, same grids and splits, every shape in one pass.  Only the writer differs:
 // the pixel-writing kernels of kernels/packed422_bgr.hip.h decode the new luma with the row's own chroma and write 3 bytes per pixel.
-// Never the fused kernel and never hist_lut_kernel, as the packed forms.  There is no frame-list form yet: the writer has batch
-// entries only.
+// Never the fused kernel and never hist_lut_kernel, as the packed forms.  The frame-list form is packed422_bgr_frames.inc.hpp's.
 
 namespace {
 
@@ -61,42 +60,29 @@ Packed422Bgr packed422_bgr_batch(const P422BgrArgs& a, int f0)
     return p;
 }
 
-// A writer's kernel that has a batch entry only, and the launch_pair of such a one: the stage sequences of packed422.inc.hpp find it
-// through their writer's K<OFF> (a call that came with a frame list has no kernel to go to).
-template <class KB> struct BatchKernel { KB batch; };
-template <class KB> BatchKernel(KB) -> BatchKernel<KB>;
-struct NoFrameList {};
-
-template <class KB, class... A>
-mi_status launch_pair(mi_ctx* c, hipStream_t s, int kid, const BatchKernel<KB>& k, const NoFrameList* fl, dim3 grid, dim3 block, size_t lds,
-                      const A&... args)
-{
-    if (fl) return fail(c, MI_ERR_UNSUPPORTED, "this writer has no frame-list form");
-    LAUNCH(c, s, kid, k.batch, grid, block, lds, args...);
-    return MI_OK;
-}
-
 // The writer of the stage sequences of packed422.inc.hpp that decodes the new luma with the row's own chroma into B, G, R (ORDER 0)
-// or R, G, B (ORDER 1)
+// or R, G, B (ORDER 1).  Its frame list is the packed forms' own {in, out} table (packed422_bgr_frames.inc.hpp fills it).
 template <int ORDER> struct BgrOut {
     using Args = P422BgrArgs;
     using Block = Packed422Bgr;
-    using List = NoFrameList;
+    using List = Packed422List;
     static const P422Args& input(const Args& a) { return a.in; }
     static Block cut(const Args& a, int f0) { return packed422_bgr_batch(a, f0); }
     static int apply_rows(int height) { return height; }
     template <int OFF> struct K {
-        static constexpr BatchKernel apply{lut_apply422_bgr_kernel<OFF, ORDER>};
-        static constexpr BatchKernel interp_global{clahe_interp422_bgr_global_kernel<OFF, ORDER>};
+        static constexpr KernelPair apply{lut_apply422_bgr_frames_kernel<OFF, ORDER>, lut_apply422_bgr_kernel<OFF, ORDER>};
+        static constexpr KernelPair interp_global{clahe_interp422_bgr_global_frames_kernel<OFF, ORDER>, clahe_interp422_bgr_global_kernel<OFF, ORDER>};
         template <bool FT, bool FMA>
-        static constexpr BatchKernel interp{clahe_interp422_bgr_kernel<FT, FMA, OFF, ORDER>};
+        static constexpr KernelPair interp{clahe_interp422_bgr_frames_kernel<FT, FMA, OFF, ORDER>, clahe_interp422_bgr_kernel<FT, FMA, OFF, ORDER>};
     };
 };
 
-mi_status packed422_bgr_dev(mi_ctx* c, hipStream_t s, const P422BgrArgs& a, int op, double clip_limit, int tiles_x, int tiles_y)
+// fl_in / fl_out: a chunk of a frame list (both or neither, see packed422.inc.hpp)
+mi_status packed422_bgr_dev(mi_ctx* c, hipStream_t s, const P422BgrArgs& a, int op, double clip_limit, int tiles_x, int tiles_y,
+                            const Packed422List* fl_in = nullptr, const Packed422List* fl_out = nullptr)
 {
-    return a.order == MI_ORDER_RGB ? packed422_dev<BgrOut<1>>(c, s, a, op, clip_limit, tiles_x, tiles_y)
-                                   : packed422_dev<BgrOut<0>>(c, s, a, op, clip_limit, tiles_x, tiles_y);
+    return a.order == MI_ORDER_RGB ? packed422_dev<BgrOut<1>>(c, s, a, op, clip_limit, tiles_x, tiles_y, fl_in, fl_out)
+                                   : packed422_dev<BgrOut<0>>(c, s, a, op, clip_limit, tiles_x, tiles_y, fl_in, fl_out);
 }
 
 // The host form's checks: the input side and the shape are the device form's (on the caller's input and a stand-in image); the output

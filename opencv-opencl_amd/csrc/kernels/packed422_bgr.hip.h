@@ -8,7 +8,7 @@
 // the arithmetic of cvt420_kernel<1>) and leave as 48 bytes.  Here the chroma ORDER matters: OFF = 0 is exactly Y0 U Y1 V, OFF = 1
 // exactly U Y0 V Y1 (a YVYU frame would come out with U and V swapped).
 // Input rows start at multiples of 4 as in every packed form.  The output has no alignment rule.  `wide` (host: the output pointer, its
-// pitch and its frame stride are multiples of 4): a lane's 48 bytes start at a multiple of 4 and leave as three unaligned-capable
+// pitch and its frame stride are multiples of 4; in a list, the pitch and the frame's own address): a lane's 48 bytes start at a multiple of 4 and leave as three unaligned-capable
 // 16-byte stores, the ragged last group of a row (W % 16 != 0, 3 * n bytes) as dwords and at most one final 2-byte store.  Otherwise
 // every byte is stored on its own: slower, the same bytes.  Nothing beyond byte 3 * W of any row is written.
 // ORDER 0: B, G, R in memory (MI_ORDER_BGR); 1: R, G, B (MI_ORDER_RGB).
@@ -26,14 +26,31 @@ struct Packed422Bgr {
     long long src_frame, out_frame;
     int dwords, rows;                 // macropixels per row (W / 2), rows (H, any value >= 1)
     int wide;                         // 1: out, out_step and out_frame are multiples of 4 -> vector stores; 0: byte stores
+                                      // (a table launch: out_step alone, each frame adds its own address -- Table422Bgr::wide_of)
 };
 
-// Where frame f lives.  The bodies below are templates on such a policy from the start, as packed422_nv12.hip.h's are: a frame-list
-// form adds a table policy and *_frames_kernel entries, not new bodies.  Only the strided policy exists so far.
+// Where frame f lives, and which store path it takes.  The bodies below are templates on such a policy, as packed422_nv12.hip.h's
+// are: the batch kernels wrap them with the strided policy, the *_frames_kernel entries with the table.
 struct Strided422Bgr {
     const Packed422Bgr& p;
     __device__ __forceinline__ const uint8_t* src_of(long long f) const { return p.src + f * p.src_frame; }
     __device__ __forceinline__ uint8_t* out_of(long long f) const { return p.out + f * p.out_frame; }
+    __device__ __forceinline__ bool wide_of(long long) const { return p.wide != 0; }
+};
+// A list of frames, each at its own addresses (mi_*_packed422_to_bgr_frames_dev: a capture device's buffer pool in, an image pool out).
+// An entry is packed422.hip.h's own {in, out} pair, so the table is its Packed422List -- by value in the kernel arguments, read with
+// scalar loads indexed by the frame's grid coordinate -- and the chunks are those of the histogram stages.  The shape is the launch's
+// Packed422Bgr, whose src / out / *_frame a table launch ignores and whose `wide` says only that out_step is a multiple of 4: each
+// frame adds its own address.  The frame index is uniform across a workgroup, so the choice stays a scalar branch.
+// clahe_interp422_bgr_frames_kernel(l, p, g, luts, subs, groups, pair_cap) is the longest list; 256: the implicit arguments
+static_assert(sizeof(Packed422List) + sizeof(Packed422Bgr) + sizeof(ClaheGeom) + 8 + sizeof(const uint8_t*) + 3 * sizeof(int) + 8 + 256 <= 4096,
+              "the kernel arguments of a table launch stay within 4 KiB");
+struct Table422Bgr {
+    const Packed422List& l;
+    const Packed422Bgr& p;
+    __device__ __forceinline__ const uint8_t* src_of(long long f) const { return l.f[f].in; }
+    __device__ __forceinline__ uint8_t* out_of(long long f) const { return l.f[f].out; }
+    __device__ __forceinline__ bool wide_of(long long f) const { return p.wide != 0 && ((uintptr_t)l.f[f].out & 3) == 0; }
 };
 
 // 16 luma bytes (already mapped) and the 8 U,V pairs of the same macropixels -> the 48 bytes of 16 pixels as 12 dwords.  The decode of
@@ -111,7 +128,7 @@ __device__ __forceinline__ void lut_apply422_bgr_body(const Packed422Bgr& p, con
     }
     __syncthreads();
     const uint32_t copy = t & (kCopies - 1);
-    const bool wide = p.wide != 0;
+    const bool wide = fr.wide_of(f);
     const int r0 = (int)((long long)p.rows * blockIdx.x / gridDim.x), r1 = (int)((long long)p.rows * (blockIdx.x + 1) / gridDim.x);
     const uint8_t* src0 = fr.src_of(f) + (long long)r0 * p.src_step;
     uint8_t* out0 = fr.out_of(f) + (long long)r0 * p.out_step;
@@ -140,6 +157,11 @@ template <int OFF, int ORDER>
 __global__ __launch_bounds__(kThreads) void lut_apply422_bgr_kernel(Packed422Bgr p, const uint8_t* __restrict__ luts)
 {
     lut_apply422_bgr_body<OFF, ORDER>(p, Strided422Bgr{p}, luts);
+}
+template <int OFF, int ORDER>
+__global__ __launch_bounds__(kThreads) void lut_apply422_bgr_frames_kernel(Packed422List l, Packed422Bgr p, const uint8_t* __restrict__ luts)
+{
+    lut_apply422_bgr_body<OFF, ORDER>(p, Table422Bgr{l, p}, luts);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -180,7 +202,7 @@ __device__ __forceinline__ void clahe_interp422_bgr_body(const Packed422Bgr& p, 
     const uint8_t* src = fr.src_of(f) + 2LL * x0;
     uint8_t* dst = fr.out_of(f) + 3LL * x0;
     const bool full = x0 + kInterpPx <= g.width;
-    const bool wide = p.wide != 0;
+    const bool wide = fr.wide_of(f);
     auto ty1_of = [&](int y) { return floor_f32_to_int(tile_coord<FMA>(y, g.inv_th)); };
     int ya_lo = y_lo, ya_hi = y_hi;
     while (ya_lo < ya_hi && ty1_of(ya_lo) != ty1u) ++ya_lo;
@@ -244,6 +266,12 @@ __global__ __launch_bounds__(kThreads) void clahe_interp422_bgr_kernel(Packed422
 {
     clahe_interp422_bgr_body<FT, FMA, OFF, ORDER>(p, Strided422Bgr{p}, g, luts, subs, groups, pair_cap);
 }
+template <bool FT, bool FMA, int OFF, int ORDER>
+__global__ __launch_bounds__(kThreads) void clahe_interp422_bgr_frames_kernel(Packed422List l, Packed422Bgr p, ClaheGeom g,
+                                                                             const uint8_t* __restrict__ luts, int subs, int groups, int pair_cap)
+{
+    clahe_interp422_bgr_body<FT, FMA, OFF, ORDER>(p, Table422Bgr{l, p}, g, luts, subs, groups, pair_cap);
+}
 
 // Fallback for tile grids too wide for the LDS pair table (clahe_interp422_global_kernel's arithmetic): one macropixel per thread, the
 // LUTs gathered from global memory (L2), two pixels decoded with the macropixel's own U and V: 6 bytes, as three 2-byte stores when the
@@ -284,7 +312,7 @@ __device__ __forceinline__ void clahe_interp422_bgr_global_body(const Packed422B
     bt601_px_bgr(e[0], ruv, guv, buv, c[B], c[1], c[R]);
     bt601_px_bgr(e[1], ruv, guv, buv, c[3 + B], c[4], c[3 + R]);
     uint8_t* o = fr.out_of(f) + (long long)y * p.out_step + 6LL * d;
-    if (p.wide) {
+    if (fr.wide_of(f)) {
         uint16_t* o2 = reinterpret_cast<uint16_t*>(o);
         o2[0] = (uint16_t)(c[0] | (c[1] << 8)); o2[1] = (uint16_t)(c[2] | (c[3] << 8)); o2[2] = (uint16_t)(c[4] | (c[5] << 8));
     } else {
@@ -296,6 +324,12 @@ template <int OFF, int ORDER>
 __global__ __launch_bounds__(kThreads) void clahe_interp422_bgr_global_kernel(Packed422Bgr p, ClaheGeom g, const uint8_t* __restrict__ luts)
 {
     clahe_interp422_bgr_global_body<OFF, ORDER>(p, Strided422Bgr{p}, g, luts);
+}
+template <int OFF, int ORDER>
+__global__ __launch_bounds__(kThreads) void clahe_interp422_bgr_global_frames_kernel(Packed422List l, Packed422Bgr p, ClaheGeom g,
+                                                                                    const uint8_t* __restrict__ luts)
+{
+    clahe_interp422_bgr_global_body<OFF, ORDER>(p, Table422Bgr{l, p}, g, luts);
 }
 
 }  // namespace mi

@@ -48,6 +48,7 @@ using namespace mi;
 #include "host/packed422_nv12.inc.hpp"     // packed 4:2:2 frames in, NV12 frames out (capture card -> encoder in one pass)
 #include "host/packed422_nv12_frames.inc.hpp"   // ... as lists of pitched device frames (buffer pool in, surface pool out) and as one host frame
 #include "host/packed422_bgr.inc.hpp"      // packed 4:2:2 frames in, interleaved BGR / RGB out, every row with its own chroma (capture card -> display / writer / model)
+#include "host/packed422_bgr_frames.inc.hpp"   // ... as a list of pitched device frames (a capture device's buffer pool in, an image pool out)
 #include "host/nv12_bgr.inc.hpp"       // NV12 frames in, interleaved BGR / RGB out in the pass that maps the luma (decoder -> display / writer / model)
 #include "host/nv12_bgr_frames.inc.hpp"   // ... as a list of pitched device frames (a decoder's surface pool in, an image pool out)
 #include "host/bgr_nv12.inc.hpp"       // interleaved BGR / RGB in, pitched NV12 out: convert and count, then map the luma in place (renderer / model -> encoder)

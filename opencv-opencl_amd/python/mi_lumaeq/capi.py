@@ -56,6 +56,7 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_packed422_to_nv12", "mi_clahe_packed422_to_nv12",
     "mi_equalize_hist_packed422_to_bgr_batch_dev", "mi_clahe_packed422_to_bgr_batch_dev",
     "mi_equalize_hist_packed422_to_bgr", "mi_clahe_packed422_to_bgr",
+    "mi_equalize_hist_packed422_to_bgr_frames_dev", "mi_clahe_packed422_to_bgr_frames_dev",
     "mi_equalize_hist_nv12_to_bgr_batch_dev", "mi_clahe_nv12_to_bgr_batch_dev", "mi_equalize_hist_nv12_to_bgr", "mi_clahe_nv12_to_bgr",
     "mi_equalize_hist_nv12_to_bgr_frames_dev", "mi_clahe_nv12_to_bgr_frames_dev",
     "mi_equalize_hist_bgr_to_nv12_batch_dev", "mi_clahe_bgr_to_nv12_batch_dev", "mi_equalize_hist_bgr_to_nv12", "mi_clahe_bgr_to_nv12",
@@ -99,6 +100,11 @@ class Packed422Nv12FrameDev(C.Structure):
     """mi_packed422_nv12_frame_dev: one frame of a packed 4:2:2 -> NV12 list, its input and its two output plane addresses (device
     pointers)."""
     _fields_ = [("in_", C.c_void_p), ("y_out", C.c_void_p), ("uv_out", C.c_void_p)]
+
+
+class Packed422BgrFrameDev(C.Structure):
+    """mi_packed422_bgr_frame_dev: one frame of a packed 4:2:2 -> BGR / RGB list, its input and its image address (device pointers)."""
+    _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p)]
 
 
 class Nv12BgrFrameDev(C.Structure):
@@ -273,6 +279,8 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_packed422_to_bgr_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_packed422_to_bgr.argtypes = [vp, vp, sz, vp, sz, i, i, i, i]
     L.mi_clahe_packed422_to_bgr.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, d, i, i]
+    L.mi_equalize_hist_packed422_to_bgr_frames_dev.argtypes = [vp, C.POINTER(Packed422BgrFrameDev), i, i, i, sz, sz, i, i, vp]
+    L.mi_clahe_packed422_to_bgr_frames_dev.argtypes = [vp, C.POINTER(Packed422BgrFrameDev), i, i, i, sz, sz, i, i, d, i, i, vp]
     L.mi_equalize_hist_nv12_to_bgr_batch_dev.argtypes = [vp, vp, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp]
     L.mi_clahe_nv12_to_bgr_batch_dev.argtypes = [vp, vp, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_nv12_to_bgr.argtypes = [vp, vp, vp, sz, i, i, i]
@@ -447,6 +455,23 @@ def _packed422_nv12_list(inputs, y_outputs, uv_outputs, width, in_pitch, y_pitch
     for k in range(len(inputs)):
         arr[k] = Packed422Nv12FrameDev(_dptr(inputs[k]), _dptr(y_outputs[k]), _dptr(uv_outputs[k]))
     return arr, len(inputs), ip, yp, up
+
+
+def _packed422_bgr_list(inputs, outs, width, in_pitch, out_pitch, what):
+    """inputs / outs: sequences of equal length (torch CUDA tensors or raw device addresses).  Returns the mi_packed422_bgr_frame_dev
+    array, its length and the two pitches (given, else the row stride of the tensors -- H x pitch frames, H x 3W or H x W x 3 images --
+    else 2 * width for the frames and 3 * width for the images)."""
+    inputs, outs = list(inputs), list(outs)
+    if len(inputs) != len(outs):
+        raise MiError(1, what, f"{len(inputs)} inputs but {len(outs)} images")
+    ip = _plane_pitch(inputs, in_pitch, 2 * int(width), what)
+    # an H x W x 3 image's rows are its first axis: seen as H x 3W for the pitch
+    rows = [o if isinstance(o, int) or o is None or o.dim() != 3 else o[:, :, 0] for o in outs]
+    op = int(out_pitch) if out_pitch is not None else _plane_pitch(rows, None, 3 * int(width), what)
+    arr = (Packed422BgrFrameDev * max(1, len(inputs)))()
+    for k in range(len(inputs)):
+        arr[k] = Packed422BgrFrameDev(_dptr(inputs[k]), _dptr(outs[k]))
+    return arr, len(inputs), ip, op
 
 
 def _nv12_bgr_list(ys, uvs, outs, width, y_pitch, uv_pitch, out_pitch, what):
@@ -934,6 +959,24 @@ class Context:
         self._chk(self._L.mi_clahe_packed422_to_bgr_batch_dev(self._h, _dptr(d_in), ip, fi, _dptr(d_out), op, fo, int(width), int(height),
                                                             int(n_frames), int(fmt), int(order), float(clip_limit), int(tiles_x),
                                                             int(tiles_y), stream), "mi_clahe_packed422_to_bgr_batch_dev")
+
+    def equalize_hist_packed422_to_bgr_frames(self, inputs, outs, width, height, fmt=FMT_YUY2, order=ORDER_BGR, in_pitch=None,
+                                              out_pitch=None, stream=0):
+        """mi_equalize_hist_packed422_to_bgr_frames_dev.  inputs: the packed frames, outs: the images, each its own buffer -- lists of
+        torch CUDA tensors or raw device addresses, one entry per frame.  A pitch left at None is the row stride of the 2-D tensors of
+        that list (H x W x 3 images: of their first axis), or the tight one (2 * width; 3 * width)."""
+        arr, n, ip, op = _packed422_bgr_list(inputs, outs, width, in_pitch, out_pitch, "equalize_hist_packed422_to_bgr_frames")
+        self._chk(self._L.mi_equalize_hist_packed422_to_bgr_frames_dev(self._h, arr, n, int(width), int(height), ip, op, int(fmt),
+                                                                     int(order), stream),
+                  "mi_equalize_hist_packed422_to_bgr_frames_dev")
+
+    def clahe_packed422_to_bgr_frames(self, inputs, outs, width, height, fmt=FMT_YUY2, order=ORDER_BGR, clip_limit=2.0, tiles_x=8,
+                                      tiles_y=8, in_pitch=None, out_pitch=None, stream=0):
+        """mi_clahe_packed422_to_bgr_frames_dev; arguments as equalize_hist_packed422_to_bgr_frames, plus the CLAHE parameters."""
+        arr, n, ip, op = _packed422_bgr_list(inputs, outs, width, in_pitch, out_pitch, "clahe_packed422_to_bgr_frames")
+        self._chk(self._L.mi_clahe_packed422_to_bgr_frames_dev(self._h, arr, n, int(width), int(height), ip, op, int(fmt), int(order),
+                                                             float(clip_limit), int(tiles_x), int(tiles_y), stream),
+                  "mi_clahe_packed422_to_bgr_frames_dev")
 
     def _packed_bgr_host(self, frame, width, out, name):
         frame = self._packed_host(frame, width, name)

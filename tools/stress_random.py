@@ -4,7 +4,8 @@ tiles (several tiles per histogram workgroup), 16-bit CLAHE at random value rang
 at random pitched layouts (aligned and not) and tile grids on both sides of its one-pass conditions, as a batch and as a frame list
 (random order, every image at its own offset), and the same pixels from planar chroma (I420 / YV12 in, BGR out) at chroma layouts that are
 multiples of 8 or of 1, as a batch and as a frame list against the batch form's bytes, and the way back on a frame list (those images in,
-I420 / YV12 planes out at that layout, every frame at an offset of its own) against the oracle.
+I420 / YV12 planes out at that layout, every frame at an offset of its own) against the oracle, and packed 4:2:2 in (YUY2 / UYVY), BGR
+out on a frame list (every buffer and every image an allocation of its own, images at any byte offset) against the oracle and the batch form.
     python tools/stress_random.py [seconds] [seed] [option=value ...]        prints a line every ~15 s, exits non-zero on the first mismatch"""
 import sys, time
 sys.path.insert(0, "opencv-opencl_amd/python"); sys.path.insert(0, ".")
@@ -16,12 +17,12 @@ rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 ctx = mi_lumaeq.Context(0)
 for kv in sys.argv[3:]:                                          # name=value options for the whole run, e.g. clahe16_wide=2 (mid kernel always launched)
     k_, v_ = kv.split("="); ctx.set_option(k_, int(v_)); print("option", k_, "=", v_, flush=True)
-t0 = last = time.time(); n = {"roi": 0, "grid": 0, "small": 0, "c16": 0, "420": 0, "nv12": 0, "nv12bgr": 0, "yuv420bgr": 0, "yuv420bgrlist": 0, "bgryuv420list": 0}
+t0 = last = time.time(); n = {"roi": 0, "grid": 0, "small": 0, "c16": 0, "420": 0, "nv12": 0, "nv12bgr": 0, "yuv420bgr": 0, "yuv420bgrlist": 0, "bgryuv420list": 0, "p422bgrlist": 0}
 def dev(a): return xfer.to_device(np.ascontiguousarray(a))
 def fail(what, *info):
     print("MISMATCH", what, info, flush=True); sys.exit(1)
 while time.time() - t0 < budget:
-    k = int(rng.integers(0, 7))
+    k = int(rng.integers(0, 8))
     if k == 0:      # ROI batch on the device: random pitches, origins, sizes
         w, h, nf = int(rng.integers(1, 700)), int(rng.integers(1, 90)), int(rng.integers(1, 6))
         sp = w + int(rng.integers(0, 40)); sp += (16 - sp % 16) % 16 if rng.integers(0, 2) else 0
@@ -186,6 +187,36 @@ while time.time() - t0 < budget:
         if not np.array_equal(got, want): fail("bgryuv420 list", w, h, nf, op, order, uvm, clip, tx, ty, al, opi, yp, cp, g0, g1, pfi, yv12, off, perm, jy, np.flatnonzero(got != want)[:8])
         if not np.array_equal(xfer.to_host(d_out4), out): fail("bgryuv420 list wrote its input", w, h, nf, op)
         n["bgryuv420list"] += 1
+    elif k == 7:    # packed 4:2:2 in, BGR / RGB out on a frame list: every row its own chroma, every image at its own byte offset (wide and byte stores in one launch)
+        w, h, nf = int(rng.integers(1, 120)) * 2, int(rng.integers(1, 70)), int(rng.integers(1, 7))
+        op, order, fmt = int(rng.integers(0, 2)), int(rng.integers(0, 2)), int(rng.integers(2, 4)); off = fmt - 2
+        tx, ty = int(rng.choice([1, 3, 8, 16, 64])), int(rng.integers(1, 6)); clip = float(rng.choice([0.0, 1.0, 2.0, 40.0]))
+        ipi = 2 * w + 4 * int(rng.integers(0, 10)); opi = 3 * w + (4 - 3 * w % 4) % 4 + 4 * int(rng.integers(0, 4)) if rng.integers(0, 3) else 3 * w + int(rng.integers(0, 9))
+        fr = rng.integers(0, 256, (nf, h, ipi), dtype=np.uint8)
+        ioff = [4 * int(rng.integers(0, 4)) for _ in range(nf)]; ooff = [int(rng.integers(0, 16)) if rng.integers(0, 2) else 4 * int(rng.integers(0, 4)) for _ in range(nf)]
+        imgs_in = [np.full(ioff[f] + ipi * h + 32, 0x5A, np.uint8) for f in range(nf)]
+        for f in range(nf): imgs_in[f][ioff[f]: ioff[f] + ipi * h] = fr[f].reshape(-1)
+        d_ins = [dev(a) for a in imgs_in]; d_outs = [torch.full((ooff[f] + opi * h + 32,), 0x5A, dtype=torch.uint8, device="cuda") for f in range(nf)]
+        la = ([d_ins[f].data_ptr() + ioff[f] for f in range(nf)], [d_outs[f].data_ptr() + ooff[f] for f in range(nf)], w, h, fmt, order)
+        d_bat = torch.full((nf, h, w, 3), 0x5A, dtype=torch.uint8, device="cuda"); ba = (dev(fr), d_bat, w, h, nf, fmt, order); bkw = dict(in_pitch=ipi)
+        try:
+            if op == 0: ctx.equalize_hist_packed422_to_bgr_frames(*la, in_pitch=ipi, out_pitch=opi); ctx.equalize_hist_packed422_to_bgr_batch_dev(*ba, **bkw)
+            else: ctx.clahe_packed422_to_bgr_frames(*la, clip, tx, ty, in_pitch=ipi, out_pitch=opi); ctx.clahe_packed422_to_bgr_batch_dev(*ba, clip, tx, ty, **bkw)
+        except mi_lumaeq.MiError as e:
+            if e.status != 2: fail("p422bgr list status", w, h, nf, op, tx, ty, e.status)
+            continue                                                   # a tile grid the planar forms refuse
+        ctx.synchronize(); bat = xfer.to_host(d_bat)
+        for f in range(nf):
+            y = np.ascontiguousarray(fr[f, :, off:2 * w:2]); uvr = np.ascontiguousarray(fr[f, :, 1 - off:2 * w:2])
+            ym = oracle.equalize_hist(y) if op == 0 else oracle.clahe(y, clip, tx, ty)
+            bgr = oracle.nv12_to_bgr(np.concatenate([np.repeat(ym, 2, axis=0).reshape(-1), uvr.reshape(-1)]), w, 2 * h)[0::2]   # row r decoded with chroma row r
+            bgr = np.ascontiguousarray(bgr if order == 0 else bgr[:, :, ::-1])
+            want = np.full(d_outs[f].numel(), 0x5A, np.uint8); want[ooff[f]: ooff[f] + opi * h].reshape(h, opi)[:, : 3 * w] = bgr.reshape(h, 3 * w)
+            got = xfer.to_host(d_outs[f])
+            if not np.array_equal(got, want): fail("p422bgr list", w, h, nf, op, order, fmt, clip, tx, ty, ipi, opi, ioff, ooff, f, np.flatnonzero(got != want)[:8])
+            if not np.array_equal(bat[f], bgr): fail("p422bgr batch", w, h, nf, op, order, fmt, clip, tx, ty, f)
+            if not np.array_equal(xfer.to_host(d_ins[f]), imgs_in[f]): fail("p422bgr list wrote its input", w, h, nf, op, f)
+        n["p422bgrlist"] += 1
     else:           # 4:2:0 codes
         w, h = int(rng.integers(1, 60)) * (16 if rng.integers(0, 2) else 2), int(rng.integers(1, 40)) * 2
         bgr = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
