@@ -1046,6 +1046,66 @@ mi_status mi_equalize_hist_bgr_to_yuv420_frames_dev(mi_ctx* ctx, const mi_bgr_yu
 mi_status mi_clahe_bgr_to_yuv420_frames_dev(mi_ctx* ctx, const mi_bgr_yuv420_frame_dev* frames, int n_frames,
         int width, int height, size_t in_pitch, size_t y_pitch, size_t c_pitch, int chroma, int order, mi_uv_mode uv_mode,
         double clip_limit, int tiles_x, int tiles_y, void* stream);
+/* mi_*_bgr_to_packed422*: interleaved 8-bit BGR (or RGB) images in, packed 4:2:2 frames (YUY2 / UYVY) out with the luma equalized --
+ * renderer, model output or image reader -> SDI / HDMI playout card, v4l2 output or loopback device, virtual camera, without an NV12
+ * intermediate (which has already dropped every second chroma row) and without an interleave outside the library.
+ * Pixels, per frame:
+ *   luma   : Y = bt601_y(b, g, r) for every pixel -- the Y of cv::cvtColor(COLOR_BGR2YUV_I420) (COLOR_RGB2YUV_I420 for MI_ORDER_RGB) as
+ *            mi_cvt_color_420_u8 computes it -- then cv::equalizeHist / clahe->apply on the W x H luma plane: byte for byte what
+ *            mi_equalize_hist_u8_batch_dev / mi_clahe_u8_batch_dev return on that plane.  The same clahe_fp_contract option, the same
+ *            REFLECT_101 padding when the tile grid does not divide the frame and the same limits on sizes and tile grids as those
+ *            forms.
+ *   chroma : MI_UV_COPY: the U and V of macropixel (k, y) are bt601_uv of the LEFT pixel (2k, y) of that row, without averaging -- the
+ *            library's 4:2:0 rule (top-left pixel of each 2 x 2 block) applied to every row on its own.  MI_UV_FILL128: every chroma
+ *            byte 128, the chroma arithmetic is skipped.
+ *   This is the library's own definition, consistent with its decode: mi_*_packed422_to_bgr* reads back the same U and V for both
+ *   pixels of the macropixel.  No claim is made about COLOR_BGR2YUV_YUY2 / COLOR_BGR2YUV_UYVY of OpenCV releases later than the 4.4
+ *   the oracle restates (4.4 has no such codes).
+ *   MI_FMT_YUY2 writes exactly Y0 U Y1 V, MI_FMT_UYVY exactly U Y0 V Y1.  MI_ORDER_BGR reads B, G, R per pixel, MI_ORDER_RGB reads R, G, B.
+ *   input  : frame f at d_in + f * in_frame_stride, H rows of 3*W bytes at in_pitch >= 3*W, at any address.  The input is never written.
+ *   output : frame f at d_out + f * out_frame_stride, H rows of 2*W bytes at out_pitch >= 2*W; d_out, out_pitch and out_frame_stride
+ *            are multiples of 4 (the packed forms' rule).  Only the 2*W bytes of each output row are written: not the pitch padding,
+ *            not the gaps between frames.
+ * Width is even; height is any value >= 1, odd heights are legal.
+ * Alignment: a call moves 16 pixels of one row per lane (three 16-byte loads, two 16-byte stores) when W % 16 == 0 and d_in, in_pitch,
+ *   in_frame_stride, d_out, out_pitch and out_frame_stride are all multiples of 16.  Otherwise it processes one macropixel per lane
+ *   with six byte loads and one aligned dword store -- slower, the same bytes out.
+ * Two stages per chunk of 256 frames, as in mi_*_bgr_to_nv12_batch_dev.  Y is not in the input, so stage 1 converts: ONE kernel (charged
+ *   to MI_K_COLOR) reads the image once, writes the packed frame with unequalized luma into d_out and, for equalizeHist, counts the
+ *   luma bytes it has just produced.  Stage 2 is the packed form's own kernels IN PLACE on the output frame, the chroma bytes kept
+ *   whatever uv_mode is: equalizeHist one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch (no MI_K_HIST launch); CLAHE exactly what
+ *   mi_clahe_packed422_batch_dev launches for those frames in place, every shape in one pass.  Never the fused equalizeHist kernel nor
+ *   the single-launch histogram + LUT kernel: option two_kernel_max_frames does not apply.  Bytes moved per pixel: equalizeHist
+ *   3 + 2 + 2 + 2 = 9, CLAHE 5 + 2 + 4 = 11.  Between the stages d_out holds the unequalized luma.
+ * Counters (mi_ctx_get_stat): "bgr_packed422_vec" / "bgr_packed422_bytes", one count per call by the walk stage 1 took (16-pixel
+ *   groups / macropixels).  A device or host call with work to do moves exactly one of them; a call that returns an error or has a
+ *   zero size moves neither.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of the
+ *   same shape as the other batched device forms.
+ * mi_equalize_hist_bgr_to_packed422 / mi_clahe_bgr_to_packed422: ONE CV_8UC3 image in host memory at in_step >= 3*W, at any address, in;
+ *   one packed frame in host memory at any address and any out_pitch >= 2*W out.  Synchronous; the image is staged in like
+ *   mi_*_bgr_to_yuv420's and the frame comes back like mi_*_packed422's (frames in pinned memory that are tight are DMA'd as they are,
+ *   everything else goes through the context's pinned staging).  On the device the frame is tight and 16-byte aligned, so a
+ *   W % 16 == 0 image takes the 16-pixel groups.  Whatever the call returns, no copy on the caller's memory is in flight any more when
+ *   it returns.  W*H beyond what mi_*_bgr_to_nv12 accepts: MI_ERR_UNSUPPORTED.
+ * There is no in-place form: d_out == d_in is MI_ERR_BAD_ARG; any other overlap of input and output is undefined, not checked.
+ * Errors, MI_ERR_BAD_ARG: a null ctx, d_in or d_out; an odd width (refused even when another size is 0, as in the packed forms); a
+ *   negative size; in_pitch < 3*W; out_pitch < 2*W; a d_out, out_pitch or out_frame_stride of the device form that is not a multiple
+ *   of 4; an `order` other than the two; a `format` other than the two; a bad uv_mode; tiles <= 0.  width, height or n_frames of 0:
+ *   MI_OK, nothing written (pointers and pitches are not looked at then).  Sizes and tile grids the packed or planar forms refuse:
+ *   MI_ERR_UNSUPPORTED, nothing written.  Nothing is enqueued unless every check passes.
+ * Not built: the frame-list form mi_*_bgr_to_packed422_frames_dev (the follow-up), YVYU / VYUY, BGRA input, chroma averaging. */
+mi_status mi_equalize_hist_bgr_to_packed422_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        void* d_out, size_t out_pitch, size_t out_frame_stride,
+        int width, int height, int n_frames, int order, int format, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_bgr_to_packed422_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        void* d_out, size_t out_pitch, size_t out_frame_stride,
+        int width, int height, int n_frames, int order, int format, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
+mi_status mi_equalize_hist_bgr_to_packed422(mi_ctx* ctx, const uint8_t* in, size_t in_step, uint8_t* out, size_t out_pitch,
+        int width, int height, int order, int format, mi_uv_mode uv_mode);
+mi_status mi_clahe_bgr_to_packed422(mi_ctx* ctx, const uint8_t* in, size_t in_step, uint8_t* out, size_t out_pitch,
+        int width, int height, int order, int format, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
 
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at

@@ -363,7 +363,10 @@ mi_status mi_ctx_synchronize(mi_ctx* c, void* stream)
 // "bgr_yuv420_bytes", and an INTERLEAVED list is the NV12 list form's call and moves none of the four),
 // "packed422_bgr_list_frames_wide" / "packed422_bgr_list_frames_bytes" (FRAMES of mi_*_packed422_to_bgr_frames_dev calls whose image was
 // stored 16 bytes per access / byte by byte: out_pitch and the frame's own `out` multiples of 4, or not; counted once the whole call is
-// enqueued, never for a refused call or one with nothing to do).
+// enqueued, never for a refused call or one with nothing to do),
+// "bgr_packed422_vec" / "bgr_packed422_bytes" (mi_*_bgr_to_packed422* calls, device and host forms, whose conversion kernel walked 16 x 1
+// pixel groups with 16-byte accesses / macropixels with byte loads: one count per call with work to do, by the walk stage 1 took; a
+// refused or empty call moves neither).
 mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
 {
     ENTER(c);
@@ -405,6 +408,8 @@ mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
     if (!strcmp(name, "bgr_yuv420_list_frames_bytes")) { *out = c->bgr_yuv420_list_frames_bytes; return MI_OK; }
     if (!strcmp(name, "packed422_bgr_list_frames_wide")) { *out = c->packed422_bgr_list_frames_wide; return MI_OK; }
     if (!strcmp(name, "packed422_bgr_list_frames_bytes")) { *out = c->packed422_bgr_list_frames_bytes; return MI_OK; }
+    if (!strcmp(name, "bgr_packed422_vec")) { *out = c->bgr_packed422_vec; return MI_OK; }
+    if (!strcmp(name, "bgr_packed422_bytes")) { *out = c->bgr_packed422_bytes; return MI_OK; }
     return fail(c, MI_ERR_BAD_ARG, "unknown stat");
 }
 

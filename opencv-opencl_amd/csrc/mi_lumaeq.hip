@@ -59,5 +59,6 @@ using namespace mi;
 #include "host/yuv420_bgr_frames.inc.hpp"   // ... as a list of separately allocated, pitched planes (a decoder's frame pool in, an image pool out)
 #include "host/bgr_yuv420.inc.hpp"     // interleaved BGR / RGB in, planar 4:2:0 (I420 / YV12) or NV12 out: convert and count, then map the luma in place (renderer / model -> software encoder)
 #include "host/bgr_yuv420_frames.inc.hpp"   // ... as a list of pitched device frames (an image pool in, a software encoder's frame pool out)
+#include "host/bgr_packed422.inc.hpp"  // interleaved BGR / RGB in, packed 4:2:2 (YUY2 / UYVY) out: convert and count, then map the luma in place in the packed frame (renderer / model -> playout)
 #include "host/pipe.inc.hpp"
 #include "host/diff.inc.hpp"

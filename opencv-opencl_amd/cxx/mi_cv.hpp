@@ -591,6 +591,25 @@ inline void claheBGRToYUV420(const unsigned char* in, size_t inStep, const YUV42
     detail::check(c, mi_clahe_bgr_to_yuv420(c, in, inStep, &b, width, height, (int)order, (mi_uv_mode)uv, clipLimit, tiles.width,
                                             tiles.height), "mi_clahe_bgr_to_yuv420");
 }
+// The playout edge: one interleaved CV_8UC3 host image (BGR, or RGB) at inStep >= 3*W in, one packed 4:2:2 frame (FMT_YUY2 / FMT_UYVY) at
+// outPitch >= 2*W out: the luma of cv::cvtColor(COLOR_BGR2YUV_I420) equalized, every row with the chroma of its own pixels (the left pixel
+// of each macropixel, UV_COPY) or chroma 128 (UV_FILL128): a renderer's or a model's image -> a playout card, a v4l2 output or loopback
+// device, a virtual camera.  Width is even; any height.
+inline void equalizeHistBGRToPacked422(const unsigned char* in, size_t inStep, unsigned char* out, size_t outPitch, int width, int height,
+                                       PackedFormat format = FMT_YUY2, ChannelOrder order = ORDER_BGR, UVMode uv = UV_COPY)
+{
+    mi_ctx* c = detail::thread_ctx();
+    detail::check(c, mi_equalize_hist_bgr_to_packed422(c, in, inStep, out, outPitch, width, height, (int)order, (int)format, (mi_uv_mode)uv),
+                  "mi_equalize_hist_bgr_to_packed422");
+}
+inline void claheBGRToPacked422(const unsigned char* in, size_t inStep, unsigned char* out, size_t outPitch, int width, int height,
+                                double clipLimit, Size tiles, PackedFormat format = FMT_YUY2, ChannelOrder order = ORDER_BGR,
+                                UVMode uv = UV_COPY)
+{
+    mi_ctx* c = detail::thread_ctx();
+    detail::check(c, mi_clahe_bgr_to_packed422(c, in, inStep, out, outPitch, width, height, (int)order, (int)format, (mi_uv_mode)uv, clipLimit,
+                                               tiles.width, tiles.height), "mi_clahe_bgr_to_packed422");
+}
 
 // BASELINE.json config 5 read literally: cvtColor(COLOR_YUV2BGR_NV12) -> split -> equalizeHist on B, G and R -> merge ->
 // cvtColor(COLOR_BGR2YUV_I420) + U/V interleave, NV12 in -> NV12 out in one call (no file of the reference does this;

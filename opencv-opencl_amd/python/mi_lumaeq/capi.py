@@ -67,6 +67,8 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_yuv420_to_bgr_frames_dev", "mi_clahe_yuv420_to_bgr_frames_dev",
     "mi_equalize_hist_bgr_to_yuv420_batch_dev", "mi_clahe_bgr_to_yuv420_batch_dev", "mi_equalize_hist_bgr_to_yuv420", "mi_clahe_bgr_to_yuv420",
     "mi_equalize_hist_bgr_to_yuv420_frames_dev", "mi_clahe_bgr_to_yuv420_frames_dev",
+    "mi_equalize_hist_bgr_to_packed422_batch_dev", "mi_clahe_bgr_to_packed422_batch_dev",
+    "mi_equalize_hist_bgr_to_packed422", "mi_clahe_bgr_to_packed422",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -312,6 +314,10 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_bgr_to_yuv420.argtypes = [vp, vp, sz, yp, i, i, i, i, d, i, i]
     L.mi_equalize_hist_bgr_to_yuv420_frames_dev.argtypes = [vp, C.POINTER(BgrYuv420FrameDev), i, i, i, sz, sz, sz, i, i, i, vp]
     L.mi_clahe_bgr_to_yuv420_frames_dev.argtypes = [vp, C.POINTER(BgrYuv420FrameDev), i, i, i, sz, sz, sz, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_bgr_to_packed422_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, i, vp]
+    L.mi_clahe_bgr_to_packed422_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_bgr_to_packed422.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, i]
+    L.mi_clahe_bgr_to_packed422.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, i, d, i, i]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -1370,6 +1376,60 @@ class Context:
         self._chk(self._L.mi_clahe_bgr_to_yuv420_frames_dev(self._h, arr, n, int(width), int(height), int(in_pitch), int(y_pitch),
                                                           int(c_pitch), int(chroma), int(order), int(uv_mode), float(clip_limit),
                                                           int(tiles_x), int(tiles_y), stream), "mi_clahe_bgr_to_yuv420_frames_dev")
+
+    # ---- interleaved BGR / RGB in, packed 4:2:2 (YUY2 / UYVY) out: convert and count in one pass, then map the luma in place ----
+    def equalize_hist_bgr_to_packed422_batch_dev(self, d_in, d_out, width, height, n_frames, order=ORDER_BGR, fmt=FMT_YUY2,
+                                                 uv_mode=UV_COPY, in_pitch=None, in_frame=None, out_pitch=None, out_frame=None, stream=0):
+        """mi_equalize_hist_bgr_to_packed422_batch_dev: n_frames interleaved BGR / RGB images in, packed 4:2:2 frames out (torch tensors
+        or raw addresses).  Tight layouts are the defaults: in_pitch 3*W, in_frame = in_pitch * H, out_pitch 2*W, out_frame =
+        out_pitch * H."""
+        ip = 3 * int(width) if in_pitch is None else int(in_pitch)
+        fi = ip * int(height) if in_frame is None else int(in_frame)
+        op = 2 * int(width) if out_pitch is None else int(out_pitch)
+        fo = op * int(height) if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_equalize_hist_bgr_to_packed422_batch_dev(self._h, _dptr(d_in), ip, fi, _dptr(d_out), op, fo, int(width),
+                                                                    int(height), int(n_frames), int(order), int(fmt), int(uv_mode),
+                                                                    stream), "mi_equalize_hist_bgr_to_packed422_batch_dev")
+
+    def clahe_bgr_to_packed422_batch_dev(self, d_in, d_out, width, height, n_frames, order=ORDER_BGR, fmt=FMT_YUY2, uv_mode=UV_COPY,
+                                         clip_limit=2.0, tiles_x=8, tiles_y=8, in_pitch=None, in_frame=None, out_pitch=None,
+                                         out_frame=None, stream=0):
+        """mi_clahe_bgr_to_packed422_batch_dev; arguments as equalize_hist_bgr_to_packed422_batch_dev, plus the CLAHE parameters."""
+        ip = 3 * int(width) if in_pitch is None else int(in_pitch)
+        fi = ip * int(height) if in_frame is None else int(in_frame)
+        op = 2 * int(width) if out_pitch is None else int(out_pitch)
+        fo = op * int(height) if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_clahe_bgr_to_packed422_batch_dev(self._h, _dptr(d_in), ip, fi, _dptr(d_out), op, fo, int(width), int(height),
+                                                            int(n_frames), int(order), int(fmt), int(uv_mode), float(clip_limit),
+                                                            int(tiles_x), int(tiles_y), stream), "mi_clahe_bgr_to_packed422_batch_dev")
+
+    def _bgr_packed422_host(self, img, out, name):
+        img = self._host3(img, name)
+        h, w = img.shape[:2]
+        if out is None:
+            out = np.empty((h, 2 * w), np.uint8)
+        out = self._packed_host(out, w, name)
+        if out.shape[0] != h:
+            raise MiError(1, name, "out must have one row per image row")
+        return img, h, w, (int(img.strides[0]) if h > 1 else max(int(img.strides[0]), 3 * w)), out
+
+    def equalize_hist_bgr_to_packed422(self, img: np.ndarray, order: int = ORDER_BGR, fmt: int = FMT_YUY2, uv_mode: int = UV_COPY,
+                                       out: np.ndarray | None = None) -> np.ndarray:
+        """mi_equalize_hist_bgr_to_packed422 on a host image: an H x W x 3 uint8 array in (a view with padded rows included), the packed
+        frame out -- `out` when given (an H x pitch-bytes uint8 array, pitch >= 2*W; a view with padded rows is fine), else a new tight
+        H x 2W array."""
+        img, h, w, step, out = self._bgr_packed422_host(img, out, "equalize_hist_bgr_to_packed422")
+        self._chk(self._L.mi_equalize_hist_bgr_to_packed422(self._h, img.ctypes.data, step, out.ctypes.data, _step(out), w, h, int(order),
+                                                          int(fmt), int(uv_mode)), "mi_equalize_hist_bgr_to_packed422")
+        return out
+
+    def clahe_bgr_to_packed422(self, img: np.ndarray, order: int = ORDER_BGR, fmt: int = FMT_YUY2, uv_mode: int = UV_COPY,
+                               clip_limit: float = 2.0, tiles_x: int = 8, tiles_y: int = 8, out: np.ndarray | None = None) -> np.ndarray:
+        """mi_clahe_bgr_to_packed422; arguments as equalize_hist_bgr_to_packed422, plus the CLAHE parameters."""
+        img, h, w, step, out = self._bgr_packed422_host(img, out, "clahe_bgr_to_packed422")
+        self._chk(self._L.mi_clahe_bgr_to_packed422(self._h, img.ctypes.data, step, out.ctypes.data, _step(out), w, h, int(order), int(fmt),
+                                                  int(uv_mode), float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_bgr_to_packed422")
+        return out
 
     # ---- colour-domain neighbours (N3) ----
     @staticmethod
