@@ -1094,7 +1094,7 @@ mi_status mi_clahe_bgr_to_yuv420_frames_dev(mi_ctx* ctx, const mi_bgr_yuv420_fra
  *   of 4; an `order` other than the two; a `format` other than the two; a bad uv_mode; tiles <= 0.  width, height or n_frames of 0:
  *   MI_OK, nothing written (pointers and pitches are not looked at then).  Sizes and tile grids the packed or planar forms refuse:
  *   MI_ERR_UNSUPPORTED, nothing written.  Nothing is enqueued unless every check passes.
- * Not built: the frame-list form mi_*_bgr_to_packed422_frames_dev (the follow-up), YVYU / VYUY, BGRA input, chroma averaging. */
+ * The frame-list form mi_*_bgr_to_packed422_frames_dev is described below.  Not built: YVYU / VYUY, BGRA input, chroma averaging. */
 mi_status mi_equalize_hist_bgr_to_packed422_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
         void* d_out, size_t out_pitch, size_t out_frame_stride,
         int width, int height, int n_frames, int order, int format, mi_uv_mode uv_mode, void* stream);
@@ -1106,6 +1106,55 @@ mi_status mi_equalize_hist_bgr_to_packed422(mi_ctx* ctx, const uint8_t* in, size
         int width, int height, int order, int format, mi_uv_mode uv_mode);
 mi_status mi_clahe_bgr_to_packed422(mi_ctx* ctx, const uint8_t* in, size_t in_step, uint8_t* out, size_t out_pitch,
         int width, int height, int order, int format, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
+/* mi_*_bgr_to_packed422_frames_dev: the same conversion on a LIST of device frames, each at its own two addresses -- a pool of CV_8UC3
+ * images in (a renderer or a model hands over one image per frame), a playout card's, a v4l2 output queue's or a virtual camera's
+ * buffer pool out (every packed frame its own allocation, padded to bytesperline, at whatever alignment the driver chose).  The batch
+ * form needs both sides in one allocation each at a constant frame stride; one n_frames = 1 batch call per frame costs a launch
+ * sequence per frame with tiny grids, and repacking both pools into strided scratch and back moves 3 + 2 bytes per pixel more.
+ * `frames` is a host array of n_frames entries, read only during the call; the pointers in it are device pointers on the context's
+ * device.
+ * Shape: all frames of one call share width, height, the pair of pitches (bytes between rows), order, format and uv_mode; each has its
+ *   own two addresses.  There are no per-frame pitches.
+ *   in  : H rows of 3*W bytes at in_pitch >= 3*W, at any address -- B, G, R per pixel (MI_ORDER_BGR) or R, G, B (MI_ORDER_RGB).  The
+ *         images are never written.
+ *   out : H rows of 2*W bytes at out_pitch >= 2*W; every `out` and out_pitch are multiples of 4 (the packed forms' rule).  Only the
+ *         2*W bytes of each output row are written: not the pitch padding, nothing before or behind a frame.
+ * Bytes: per frame the output is byte for byte exactly what mi_*_bgr_to_packed422_batch_dev writes for that frame alone at the same
+ *   pitches -- luma and chroma as defined there (bt601_y of every pixel, then cv::equalizeHist / CLAHE::apply; bt601_uv of the LEFT
+ *   pixel of each macropixel, or every chroma byte 128), MI_FMT_YUY2 exactly Y0 U Y1 V, MI_FMT_UYVY exactly U Y0 V Y1; the
+ *   clahe_fp_contract option is honoured, REFLECT_101 padding applies when the tile grid does not divide the frame, width is even, odd
+ *   heights are legal, and the limits on sizes and tile grids are the batch form's, with the same statuses.
+ * Alignment: beyond the multiples of 4 above, none is required.  The per-frame alignment decides the walk of stage 1: the shape
+ *   allows 16-pixel groups (three 16-byte loads, two 16-byte stores per lane) when W % 16 == 0 and in_pitch and out_pitch are multiples
+ *   of 16; a frame then takes the groups when its own `in` and `out` are both multiples of 16, and any other frame of the same call
+ *   processes one macropixel per lane with six byte loads and one aligned dword store while its neighbours stay vectorised -- slower,
+ *   the same bytes out.
+ * Stages, per chunk of 128 frames of the list (not the batch form's 256): stage 1 is ONE launch charged to MI_K_COLOR that converts
+ *   into the caller's frames and, for equalizeHist, counts the luma bytes it has just produced.  Stage 2 maps the luma IN PLACE on the
+ *   chunk's output frames, the chroma bytes kept whatever uv_mode is: equalizeHist one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch (no
+ *   MI_K_HIST launch; never the fused equalizeHist kernel nor the single-launch histogram + LUT kernel, option two_kernel_max_frames
+ *   does not apply); CLAHE exactly what mi_clahe_packed422_frames_dev launches in place on those frames, every shape in one pass.
+ *   Between the stages a frame's `out` holds the unequalized luma.
+ * Counters (mi_ctx_get_stat): "bgr_packed422_list_frames_vec" / "bgr_packed422_list_frames_bytes" count the FRAMES (not calls) of list
+ *   calls by the walk their stage-1 kernel took: 16-pixel groups / macropixels.  A list call moves the two by n_frames in total and
+ *   does not touch "bgr_packed422_vec" / "bgr_packed422_bytes".  A call that returns an error or has nothing to do moves none.
+ * Overlap: there is no in-place form.  MI_ERR_BAD_ARG when the rows of a frame's image meet the rows of its own output frame (compared
+ *   as address ranges).  The same image may appear in several entries (inputs are only read).  Outputs that overlap ANOTHER frame's
+ *   image or output give undefined results and are not checked.
+ * Errors, MI_ERR_BAD_ARG: a null ctx; a null `frames` with n_frames > 0; a null `in` or `out` in any entry; an `out` in any entry or
+ *   an out_pitch that is not a multiple of 4; an `order` other than the two; a `format` other than the two; a bad uv_mode; a negative
+ *   size; an odd width (refused even when another size is 0, as in the batch form); in_pitch < 3*W; out_pitch < 2*W; tiles <= 0; the
+ *   overlap above.  Sizes and tile grids the packed or planar forms refuse: MI_ERR_UNSUPPORTED.  width, height or n_frames of 0: MI_OK,
+ *   nothing written (the entries and the pitches are not looked at then; n_frames == 0 with a null list is MI_OK).  Nothing is enqueued
+ *   unless every frame passes the checks: a bad last entry leaves the earlier frames' outputs untouched.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of
+ *   the same shape as the other device list forms; a captured graph holds the addresses it was captured with. */
+typedef struct mi_bgr_packed422_frame_dev { const void* in; void* out; } mi_bgr_packed422_frame_dev;  /* 16 bytes on LP64 */
+mi_status mi_equalize_hist_bgr_to_packed422_frames_dev(mi_ctx* ctx, const mi_bgr_packed422_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t out_pitch, int order, int format, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_bgr_to_packed422_frames_dev(mi_ctx* ctx, const mi_bgr_packed422_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t out_pitch, int order, int format, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
 
 /* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at

@@ -8,7 +8,8 @@
 // luma it writes into the partials equalize_lut_kernel reads; stage 2 is the packed form's own kernels (packed422.inc.hpp: PackedOut)
 // IN PLACE on the output frame with keep = the chroma mask and fill = 0, whatever uv_mode is -- stage 1 has written the chroma.  Never
 // the fused kernel and never hist_lut_kernel: option two_kernel_max_frames does not apply.  Every CLAHE shape runs in one pass.
-// The frame-list form (mi_*_bgr_to_packed422_frames_dev) is not built.
+// The frame-list form (mi_*_bgr_to_packed422_frames_dev) is bgr_packed422_frames.inc.hpp: the same stage 1 on its *_frames_kernel
+// entry (launch_bgr_to_packed422 with a Packed422List), the same stage 2 with the list.
 
 namespace {
 
@@ -48,7 +49,11 @@ mi_status check_bgr_packed422(mi_ctx* c, const BgrP422Args& a, bool host, bool i
 // *vec_out: the walk the kernel takes.  The grid rule is launch_bgr_to_nv12's on this form's bytes: half of what is read and written
 // (3 + 2 B/px) as the byte basis, one row unit per image row, the cap 2048; a workgroup pass covers 4096 pixels in 16 x 1 groups, 512
 // in macropixels.
-mi_status launch_bgr_to_packed422(mi_ctx* c, hipStream_t s, const BgrP422Args& a, int f0, int nf, bool hist, int* nparts_out, bool* vec_out)
+// With a frame table (fl: one chunk of at most kPacked422FramesPerLaunch frames, bgr_packed422_frames.inc.hpp): the same grid on the
+// *_frames_kernel entry; `a` then carries the shape, its base pointers (stand-ins for the vec rule) and frame strides are not used by
+// the kernel, and j.vec -- *vec_out -- says what the shape allows: a byte-walk frame of such a launch simply takes more grid-stride steps.
+mi_status launch_bgr_to_packed422(mi_ctx* c, hipStream_t s, const BgrP422Args& a, int f0, int nf, bool hist, int* nparts_out, bool* vec_out,
+                                  const Packed422List* fl = nullptr)
 {
     BgrPacked422Job j{};
     j.in = a.in + (size_t)f0 * a.in_frame; j.out = a.out + (size_t)f0 * a.out_frame;
@@ -68,8 +73,10 @@ mi_status launch_bgr_to_packed422(mi_ctx* c, hipStream_t s, const BgrP422Args& a
     const bool rgb = a.order == MI_ORDER_RGB, uyvy = a.format == MI_FMT_UYVY, cp = a.uv_mode == MI_UV_COPY;
 #define MI_BGR_P422_LAUNCH(O, F, U)                                                                                                  \
     do {                                                                                                                             \
-        if (hist) LAUNCH(c, s, MI_K_COLOR, (bgr_to_packed422_hist_kernel<O, F, U, true>), grid, block, 0, j, c->d_partial);            \
-        else      LAUNCH(c, s, MI_K_COLOR, (bgr_to_packed422_hist_kernel<O, F, U, false>), grid, block, 0, j, (uint32_t*)nullptr);     \
+        if (fl && hist) LAUNCH(c, s, MI_K_COLOR, (bgr_to_packed422_hist_frames_kernel<O, F, U, true>), grid, block, 0, j, *fl, c->d_partial); \
+        else if (fl)    LAUNCH(c, s, MI_K_COLOR, (bgr_to_packed422_hist_frames_kernel<O, F, U, false>), grid, block, 0, j, *fl, (uint32_t*)nullptr); \
+        else if (hist)  LAUNCH(c, s, MI_K_COLOR, (bgr_to_packed422_hist_kernel<O, F, U, true>), grid, block, 0, j, c->d_partial);      \
+        else            LAUNCH(c, s, MI_K_COLOR, (bgr_to_packed422_hist_kernel<O, F, U, false>), grid, block, 0, j, (uint32_t*)nullptr); \
     } while (0)
 #define MI_BGR_P422_LAUNCH_OF(O, F)                                                                                                  \
     do {                                                                                                                             \

@@ -179,6 +179,9 @@ struct mi_ctx {
                                                                         // left as 16-byte / as byte stores, each by its own address
     uint64_t bgr_packed422_vec = 0, bgr_packed422_bytes = 0;            // statistics "bgr_packed422_vec" / "bgr_packed422_bytes": mi_*_bgr_to_packed422* calls by the
                                                                         // walk their conversion kernel took (16 x 1 pixel groups / macropixels with byte loads)
+    unsigned long long bgr_packed422_list_frames_vec = 0, bgr_packed422_list_frames_bytes = 0;   // statistics "bgr_packed422_list_frames_vec" /
+                                                                        // "bgr_packed422_list_frames_bytes": FRAMES of mi_*_bgr_to_packed422_frames_dev calls by that
+                                                                        // walk, each by its own two addresses
 };
 
 namespace {

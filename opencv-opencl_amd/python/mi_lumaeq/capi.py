@@ -69,6 +69,7 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_bgr_to_yuv420_frames_dev", "mi_clahe_bgr_to_yuv420_frames_dev",
     "mi_equalize_hist_bgr_to_packed422_batch_dev", "mi_clahe_bgr_to_packed422_batch_dev",
     "mi_equalize_hist_bgr_to_packed422", "mi_clahe_bgr_to_packed422",
+    "mi_equalize_hist_bgr_to_packed422_frames_dev", "mi_clahe_bgr_to_packed422_frames_dev",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -119,6 +120,12 @@ class BgrNv12FrameDev(C.Structure):
     """mi_bgr_nv12_frame_dev: one frame of a BGR / RGB -> NV12 list, its image address and its two output plane addresses (device
     pointers)."""
     _fields_ = [("in_", C.c_void_p), ("y", C.c_void_p), ("uv", C.c_void_p)]
+
+
+class BgrPacked422FrameDev(C.Structure):
+    """mi_bgr_packed422_frame_dev: one frame of a BGR / RGB -> packed 4:2:2 list, its image address and its packed frame's address
+    (device pointers)."""
+    _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p)]
 
 
 class Yuv420Planes(C.Structure):
@@ -318,6 +325,8 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_bgr_to_packed422_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_bgr_to_packed422.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, i]
     L.mi_clahe_bgr_to_packed422.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, i, d, i, i]
+    L.mi_equalize_hist_bgr_to_packed422_frames_dev.argtypes = [vp, C.POINTER(BgrPacked422FrameDev), i, i, i, sz, sz, i, i, i, vp]
+    L.mi_clahe_bgr_to_packed422_frames_dev.argtypes = [vp, C.POINTER(BgrPacked422FrameDev), i, i, i, sz, sz, i, i, i, d, i, i, vp]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -514,6 +523,23 @@ def _bgr_nv12_list(ins, ys, uvs, width, in_pitch, y_pitch, uv_pitch, what):
     for k in range(len(ins)):
         arr[k] = BgrNv12FrameDev(_dptr(ins[k]), _dptr(ys[k]), _dptr(uvs[k]))
     return arr, len(ins), ip, yp, up
+
+
+def _bgr_packed422_list(ins, outs, width, in_pitch, out_pitch, what):
+    """ins / outs: sequences of equal length (torch CUDA tensors or raw device addresses).  Returns the mi_bgr_packed422_frame_dev
+    array, its length and the two pitches (given, else the row stride of the tensors -- H x 3W or H x W x 3 images, H x pitch frames --
+    else 3 * width for the images and 2 * width for the frames)."""
+    ins, outs = list(ins), list(outs)
+    if len(ins) != len(outs):
+        raise MiError(1, what, f"{len(ins)} images but {len(outs)} frames")
+    # an H x W x 3 image's rows are its first axis: seen as H x 3W for the pitch
+    rows = [o if isinstance(o, int) or o is None or o.dim() != 3 else o[:, :, 0] for o in ins]
+    ip = int(in_pitch) if in_pitch is not None else _plane_pitch(rows, None, 3 * int(width), what)
+    op = _plane_pitch(outs, out_pitch, 2 * int(width), what)
+    arr = (BgrPacked422FrameDev * max(1, len(ins)))()
+    for k in range(len(ins)):
+        arr[k] = BgrPacked422FrameDev(_dptr(ins[k]), _dptr(outs[k]))
+    return arr, len(ins), ip, op
 
 
 _live_contexts: "weakref.WeakSet[Context]" = weakref.WeakSet()
@@ -1402,6 +1428,24 @@ class Context:
         self._chk(self._L.mi_clahe_bgr_to_packed422_batch_dev(self._h, _dptr(d_in), ip, fi, _dptr(d_out), op, fo, int(width), int(height),
                                                             int(n_frames), int(order), int(fmt), int(uv_mode), float(clip_limit),
                                                             int(tiles_x), int(tiles_y), stream), "mi_clahe_bgr_to_packed422_batch_dev")
+
+    def equalize_hist_bgr_to_packed422_frames(self, ins, outs, width, height, order=ORDER_BGR, fmt=FMT_YUY2, uv_mode=UV_COPY, in_pitch=None,
+                                              out_pitch=None, stream=0):
+        """mi_equalize_hist_bgr_to_packed422_frames_dev.  ins: the images, outs: the packed frames, each its own buffer -- lists of torch
+        CUDA tensors or raw device addresses, one entry per frame.  A pitch left at None is the row stride of the 2-D tensors of that
+        list (H x W x 3 images: of their rows), or the tight one (3 * width; 2 * width)."""
+        arr, n, ip, op = _bgr_packed422_list(ins, outs, width, in_pitch, out_pitch, "equalize_hist_bgr_to_packed422_frames")
+        self._chk(self._L.mi_equalize_hist_bgr_to_packed422_frames_dev(self._h, arr, n, int(width), int(height), ip, op, int(order),
+                                                                     int(fmt), int(uv_mode), stream),
+                  "mi_equalize_hist_bgr_to_packed422_frames_dev")
+
+    def clahe_bgr_to_packed422_frames(self, ins, outs, width, height, order=ORDER_BGR, fmt=FMT_YUY2, uv_mode=UV_COPY, clip_limit=2.0,
+                                      tiles_x=8, tiles_y=8, in_pitch=None, out_pitch=None, stream=0):
+        """mi_clahe_bgr_to_packed422_frames_dev; arguments as equalize_hist_bgr_to_packed422_frames, plus the CLAHE parameters."""
+        arr, n, ip, op = _bgr_packed422_list(ins, outs, width, in_pitch, out_pitch, "clahe_bgr_to_packed422_frames")
+        self._chk(self._L.mi_clahe_bgr_to_packed422_frames_dev(self._h, arr, n, int(width), int(height), ip, op, int(order), int(fmt),
+                                                             int(uv_mode), float(clip_limit), int(tiles_x), int(tiles_y), stream),
+                  "mi_clahe_bgr_to_packed422_frames_dev")
 
     def _bgr_packed422_host(self, img, out, name):
         img = self._host3(img, name)

@@ -17,7 +17,19 @@ No bar: (a) moves fewer bytes than (b) in fewer launches, so (a) is expected ahe
 spread is reported as a finding.  After the timed legs each row runs 30 profiled calls of (a), of the library call of (b) and of (c) and
 records every kernel's launches per call and p50 time, and the bytes per second of stage 1 (MI_K_COLOR: 5 B/px here, 4.5 B/px in
 mi_*_bgr_to_nv12_batch_dev) from the same run.
-    python tools/bgr_to_packed422_ab.py [--out DIR] [--calls N]   -> DIR/r27_bgr_to_packed422_ab.json and .md (default DIR: profiles)"""
+    python tools/bgr_to_packed422_ab.py [--out DIR] [--calls N]   -> DIR/r27_bgr_to_packed422_ab.json and .md (default DIR: profiles)
+
+--list: the frame-list form (mi_*_bgr_to_packed422_frames_dev) with the same cases, pixels and method, tight pitches (3W, 2W):
+    (A)  the list form on the addresses of a strided batch layout: base + f * frame stride, every address a multiple of 16
+    (B)  mi_*_bgr_to_packed422_batch_dev on the same addresses -- the yardstick: its code and ISA are unchanged
+    (P)  the list form on a pool: every image and every frame its own allocation, frame k a further 16 * (k % 16) bytes into its
+         allocation (differently aligned, all on the 16-pixel groups)
+    (C)  one n_frames = 1 batch call per frame on the addresses of (A)
+    (A2) leg (A) once more in the same rotation: |A / A2 - 1| is the run's own spread
+A, B, P and C are compared byte for byte before anything is timed.  After the timed legs each row runs 30 profiled calls of A and of B
+and records the launches and the p50 time of each kernel role.  Nothing is gated: the run records A / B, P / B and A / C beside the
+spread, and names the rows in which A / B lies outside 0.87 .. 1.05 (where the sibling list forms landed) by more than the spread.
+    python tools/bgr_to_packed422_ab.py --list [--out DIR] [--calls N]   -> DIR/r28_bgr_to_packed422_frames_ab.json and .md"""
 import argparse
 import json
 import sys
@@ -44,13 +56,190 @@ def pct(v, q):
     return v[min(len(v) - 1, int(q * (len(v) - 1) + 0.5))]
 
 
+def timed(stream, legs, warmup, calls):
+    """Every call of every leg between its own pair of events, the legs' order rotating every iteration."""
+    names = list(legs)
+    times = {k: [] for k in names}
+    for it in range(warmup + calls):
+        order = names[it % len(names):] + names[: it % len(names)]
+        for name in order:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            legs[name](it & 1)
+            e1.record(stream)
+            if it >= warmup:
+                times[name].append((e0, e1))
+        if it % 20 == 19:
+            torch.cuda.synchronize()
+    torch.cuda.synchronize()
+    out = {}
+    for name, ev in times.items():
+        ms = [a.elapsed_time(b) for a, b in ev]
+        out[name] = {"median_us": pct(ms, 0.5) * 1e3, "p10_us": pct(ms, 0.1) * 1e3, "p90_us": pct(ms, 0.9) * 1e3}
+    return out
+
+
+LIST_LEGS = ("A_list", "B_batch", "P_list_pool", "C_per_frame", "A2_list_again")
+LIST_ROLES = {"equalize": ("color_kernel", "equalize_lut_kernel", "lut_apply_kernel"),
+              "clahe": ("color_kernel", "tile_hist_kernel", "tile_lut_kernel", "clahe_interp_kernel")}
+SIBLINGS = (0.87, 1.05)                                         # A / B of the sibling list forms (profiles/r22 .. r26)
+
+
+def main_list(args):
+    ctx = mi_lumaeq.Context(0)
+    stream = torch.cuda.current_stream()
+    s = stream.cuda_stream
+    L, hd = ctx._L, ctx._h
+    Entry = mi_lumaeq.BgrPacked422FrameDev
+    rows, outside = [], []
+    for w, h, n in CASES:
+        ip, op_ = 3 * w, 2 * w
+        in_bytes, out_bytes = ip * h, op_ * h
+        sets = []                                                # two input sets a leg alternates between, as the batch run does
+        for k in range(2):
+            g = torch.Generator(device="cuda:0")
+            g.manual_seed(0x5EED2800 + w + k)
+            x = torch.randint(0, 256, (n, h, w, 3), dtype=torch.uint8, device="cuda:0", generator=g)
+            x.copy_(x // 4 + 64 + 16 * k)                        # low contrast: ~60 populated luma bins
+            sets.append(x)
+        out_a, out_b, out_c = (torch.zeros((n, h, op_), dtype=torch.uint8, device="cuda:0") for _ in range(3))
+        skew = [16 * (f % 16) for f in range(n)]                 # the pool: own allocations, differently aligned, all multiples of 16
+        pool_in = [[torch.empty(in_bytes + 256, dtype=torch.uint8, device="cuda:0") for f in range(n)] for k in range(2)]
+        pool_out = [torch.zeros(out_bytes + 256, dtype=torch.uint8, device="cuda:0") for f in range(n)]
+        for k in range(2):
+            for f in range(n):
+                pool_in[k][f][skew[f]: skew[f] + in_bytes].copy_(sets[k][f].reshape(-1))
+
+        def table(ins, outs):
+            t = (Entry * n)()
+            for f in range(n):
+                t[f] = Entry(ins[f], outs[f])
+            return t
+        t_same = [table([sets[k].data_ptr() + f * in_bytes for f in range(n)], [out_a.data_ptr() + f * out_bytes for f in range(n)])
+                  for k in range(2)]
+        t_pool = [table([pool_in[k][f].data_ptr() + skew[f] for f in range(n)], [pool_out[f].data_ptr() + skew[f] for f in range(n)])
+                  for k in range(2)]
+        for fname, fmt in FMTS:
+            for op in OPS:
+                eq = op == "equalize"
+
+                def list_call(t):
+                    if eq:
+                        rc = L.mi_equalize_hist_bgr_to_packed422_frames_dev(hd, t, n, w, h, ip, op_, ORDER_BGR, fmt, UV_COPY, s)
+                    else:
+                        rc = L.mi_clahe_bgr_to_packed422_frames_dev(hd, t, n, w, h, ip, op_, ORDER_BGR, fmt, UV_COPY, *CLAHE, s)
+                    assert rc == 0, rc
+
+                def batch(d_in, d_out, nf):
+                    if eq:
+                        ctx.equalize_hist_bgr_to_packed422_batch_dev(d_in, d_out, w, h, nf, ORDER_BGR, fmt, UV_COPY, stream=s)
+                    else:
+                        ctx.clahe_bgr_to_packed422_batch_dev(d_in, d_out, w, h, nf, ORDER_BGR, fmt, UV_COPY, *CLAHE, stream=s)
+
+                def leg_a(k):
+                    list_call(t_same[k])
+
+                def leg_b(k):
+                    batch(sets[k], out_b, n)
+
+                def leg_p(k):
+                    list_call(t_pool[k])
+
+                def leg_c(k):
+                    for f in range(n):
+                        batch(sets[k][f], out_c[f], 1)
+
+                vec0, byte0 = ctx.get_stat("bgr_packed422_list_frames_vec"), ctx.get_stat("bgr_packed422_list_frames_bytes")
+                for leg in (leg_a, leg_b, leg_p, leg_c):
+                    leg(0)
+                torch.cuda.synchronize()
+                assert (ctx.get_stat("bgr_packed422_list_frames_vec"), ctx.get_stat("bgr_packed422_list_frames_bytes")) == (vec0 + 2 * n, byte0), \
+                    "a frame of a list left the 16-pixel groups"
+                assert torch.equal(out_a, out_b) and torch.equal(out_a, out_c), ("A, B and C differ", w, fname, op)
+                for f in range(n):
+                    assert torch.equal(pool_out[f][skew[f]: skew[f] + out_bytes], out_a[f].reshape(-1)), ("A and P differ", w, fname, op, f)
+                assert int(out_a.max()) > 0, "A wrote nothing"
+                legs = {"A_list": leg_a, "B_batch": leg_b, "P_list_pool": leg_p, "C_per_frame": leg_c, "A2_list_again": leg_a}
+                res = {"width": w, "height": h, "frames_per_call": n, "format": fname, "op": op, "order": "BGR", "uv_mode": "COPY",
+                       "calls": args.calls, "in_pitch": ip, "out_pitch": op_}
+                for name, r in timed(stream, legs, args.warmup, args.calls).items():
+                    r["frames_per_s"] = n / (r["median_us"] * 1e-6)
+                    res[name] = r
+                med = {k: res[k]["median_us"] for k in LIST_LEGS}
+                res["spread"] = abs(med["A_list"] / med["A2_list_again"] - 1.0)
+                res["A_rate_over_B_rate"] = med["B_batch"] / med["A_list"]
+                res["P_rate_over_B_rate"] = med["B_batch"] / med["P_list_pool"]
+                res["A_rate_over_C_rate"] = med["C_per_frame"] / med["A_list"]
+                ctx.set_profiling(1)
+                kern = {}
+                for leg, tag in ((leg_a, "A"), (leg_b, "B")):
+                    ctx.profile_read(reset=True)
+                    for it in range(30):
+                        leg(it & 1)
+                    torch.cuda.synchronize()
+                    prof = ctx.profile_read(reset=True)
+                    for role in LIST_ROLES[op]:
+                        if prof[role]["launches"]:
+                            kern.setdefault(role, {})[tag + "_p50_us"] = prof[role]["p50_ms"] * 1e3
+                            kern[role][tag + "_launches_per_call"] = prof[role]["launches"] / 30.0
+                ctx.set_profiling(0)
+                res["kernels"] = kern
+                rows.append(res)
+                ab = res["A_rate_over_B_rate"]
+                if ab < SIBLINGS[0] - res["spread"] or ab > SIBLINGS[1] + res["spread"]:
+                    outside.append(f"{n} x {w}x{h} {fname} {op}: A / B = {ab:.3f} (spread {res['spread']:.3f})")
+                print(json.dumps(res), flush=True)
+        del sets, out_a, out_b, out_c, pool_in, pool_out, t_same, t_pool
+        torch.cuda.empty_cache()
+    meta = {"device": torch.cuda.get_device_name(0), "library": mi_lumaeq.version(), "clahe": {"clip": CLAHE[0], "tiles": list(CLAHE[1:])},
+            "order": "BGR", "uv_mode": "COPY", "warmup": args.warmup, "bars": "none: recorded, not gated",
+            "list_frames_vec": ctx.get_stat("bgr_packed422_list_frames_vec"), "list_frames_bytes": ctx.get_stat("bgr_packed422_list_frames_bytes"),
+            "a_over_b_outside_the_siblings_range": outside}
+    ctx.close()
+    outdir = Path(args.out)
+    outdir.mkdir(parents=True, exist_ok=True)
+    (outdir / "r28_bgr_to_packed422_frames_ab.json").write_text(json.dumps({"meta": meta, "rows": rows}, indent=1) + "\n")
+    md = ["# BGR in, packed 4:2:2 out on lists of device frames: the list form against the batch form and per-frame calls", "",
+          f"{meta['device']}, {meta['library']}; {args.warmup} warm-up and {args.calls} timed calls per leg, legs interleaved in one process, "
+          "medians of per-call HIP event times; CLAHE 8x8 clip 2.0; MI_ORDER_BGR, MI_UV_COPY; tight pitches (3W, 2W).  Rates are frames per "
+          "second.  (A): mi_*_bgr_to_packed422_frames_dev on the addresses of a strided batch layout.  (B): "
+          "mi_*_bgr_to_packed422_batch_dev on the same addresses.  (P): the list form on a pool, every image and every frame its own "
+          "allocation, frame k 16 * (k % 16) bytes into it.  (C): one n_frames = 1 batch call per frame.  Spread: |A / A2 - 1|, the two (A) "
+          "legs of the same rotation.  Slots: p50 of one launch (launches per call), list / batch.  "
+          f"Frames by walk over the whole run: {meta['list_frames_vec']} on 16-pixel groups, {meta['list_frames_bytes']} on macropixels.  "
+          "The list form cuts a call into chunks of 128 frames, the batch form into chunks of 256: at 256 frames a call (A) and (P) run "
+          "two launch sequences where (B) runs one.", "",
+          "| frames | format | op | (A) list | (B) batch | (P) list, pool | (C) per frame | A / B | P / B | A / C | spread | stage 1 A / B | writer A / B |",
+          "|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        def cell(k):
+            return f"{r[k]['frames_per_s']:.0f} ({r[k]['median_us']:.0f} us)"
+
+        def slot(role):
+            v = r["kernels"].get(role, {})
+            return (f"{v.get('A_p50_us', 0):.0f} us x{v.get('A_launches_per_call', 0):.0f} / "
+                    f"{v.get('B_p50_us', 0):.0f} us x{v.get('B_launches_per_call', 0):.0f}")
+        md.append(f"| {r['frames_per_call']} x {r['width']}x{r['height']} | {r['format']} | {r['op']} | {cell('A_list')} | {cell('B_batch')} | "
+                  f"{cell('P_list_pool')} | {cell('C_per_frame')} | {r['A_rate_over_B_rate']:.3f} | {r['P_rate_over_B_rate']:.3f} | "
+                  f"{r['A_rate_over_C_rate']:.3f} | {r['spread']:.3f} | {slot('color_kernel')} | "
+                  f"{slot('lut_apply_kernel' if r['op'] == 'equalize' else 'clahe_interp_kernel')} |")
+    md += ["", f"Rows in which A / B lies outside {SIBLINGS[0]} .. {SIBLINGS[1]} by more than the spread: " +
+           ("; ".join(outside) if outside else "none") + "."]
+    (outdir / "r28_bgr_to_packed422_frames_ab.md").write_text("\n".join(md) + "\n")
+    if outside:
+        print("FINDING: A / B outside the range of the sibling list forms in", outside)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=str(ROOT / "profiles"))
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--list", action="store_true", help="measure the frame-list form (mi_*_bgr_to_packed422_frames_dev)")
     args = ap.parse_args()
     assert args.calls >= 200 and args.warmup >= 20, "the method wants >= 20 warm-up and >= 200 timed calls"
+    if args.list:
+        return main_list(args)
     ctx = mi_lumaeq.Context(0)
     stream = torch.cuda.current_stream()
     s = stream.cuda_stream

@@ -7,7 +7,8 @@ multiples of 8 or of 1, as a batch and as a frame list against the batch form's 
 I420 / YV12 planes out at that layout, every frame at an offset of its own) against the oracle, and packed 4:2:2 in (YUY2 / UYVY), BGR
 out on a frame list (every buffer and every image an allocation of its own, images at any byte offset) against the oracle and the batch form,
 and BGR / RGB in, packed 4:2:2 out (every row with the chroma of its own left pixels) at random pitched layouts, aligned and not, odd heights
-included, against the oracle on the row-doubled image (tests/bgr_packed422_ref.py).
+included, against the oracle on the row-doubled image (tests/bgr_packed422_ref.py), as a batch and as a frame list (every image and every
+frame an allocation of its own at an offset of its own: 16-pixel groups and macropixels in one launch).
     python tools/stress_random.py [seconds] [seed] [option=value ...]        prints a line every ~15 s, exits non-zero on the first mismatch"""
 import sys, time
 sys.path.insert(0, "opencv-opencl_amd/python"); sys.path.insert(0, ".")
@@ -19,12 +20,12 @@ rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 ctx = mi_lumaeq.Context(0)
 for kv in sys.argv[3:]:                                          # name=value options for the whole run, e.g. clahe16_wide=2 (mid kernel always launched)
     k_, v_ = kv.split("="); ctx.set_option(k_, int(v_)); print("option", k_, "=", v_, flush=True)
-t0 = last = time.time(); n = {"roi": 0, "grid": 0, "small": 0, "c16": 0, "420": 0, "nv12": 0, "nv12bgr": 0, "yuv420bgr": 0, "yuv420bgrlist": 0, "bgryuv420list": 0, "p422bgrlist": 0, "bgrp422": 0}
+t0 = last = time.time(); n = {"roi": 0, "grid": 0, "small": 0, "c16": 0, "420": 0, "nv12": 0, "nv12bgr": 0, "yuv420bgr": 0, "yuv420bgrlist": 0, "bgryuv420list": 0, "p422bgrlist": 0, "bgrp422": 0, "bgrp422list": 0}
 def dev(a): return xfer.to_device(np.ascontiguousarray(a))
 def fail(what, *info):
     print("MISMATCH", what, info, flush=True); sys.exit(1)
 while time.time() - t0 < budget:
-    k = int(rng.integers(0, 9))
+    k = int(rng.integers(0, 10))
     if k == 0:      # ROI batch on the device: random pitches, origins, sizes
         w, h, nf = int(rng.integers(1, 700)), int(rng.integers(1, 90)), int(rng.integers(1, 6))
         sp = w + int(rng.integers(0, 40)); sp += (16 - sp % 16) % 16 if rng.integers(0, 2) else 0
@@ -249,6 +250,43 @@ while time.time() - t0 < budget:
         if not np.array_equal(out, want): fail("bgrp422", w, h, nf, op, order, fmt, uvm, clip, tx, ty, al, ipi, opi, ioff, ifgap, ooff, ofgap, np.flatnonzero(out != want)[:8])
         if not np.array_equal(xfer.to_host(d_in), img): fail("bgrp422 wrote its input", w, h, nf, op)
         n["bgrp422"] += 1
+    elif k == 9:    # the same on a frame list: every image and every frame its own allocation; each frame on the groups or the macropixels by its own addresses
+        w, h, nf = int(rng.integers(1, 40)) * (16 if rng.integers(0, 2) else 2), int(rng.integers(1, 70)), int(rng.integers(1, 7))
+        op, order, fmt, uvm = int(rng.integers(0, 2)), int(rng.integers(0, 2)), int(rng.integers(2, 4)), int(rng.integers(0, 2))
+        tx, ty = int(rng.choice([1, 3, 8, 16, 64])), int(rng.integers(1, 6)); clip = float(rng.choice([0.0, 1.0, 2.0, 40.0]))
+        al = 16 if rng.integers(0, 4) else 1; oal = max(al, 4)         # the pitches: multiples of 16 three times in four
+        def pad(v, a): return (v + a - 1) // a * a + a * int(rng.integers(0, 40 // a + 1))
+        ipi, opi = pad(3 * w, al), pad(2 * w, oal)
+        ioff = [16 * int(rng.integers(0, 4)) if rng.integers(0, 2) else int(rng.integers(0, 32)) for _ in range(nf)]      # any address
+        ooff = [16 * int(rng.integers(0, 4)) if rng.integers(0, 2) else 4 * int(rng.integers(0, 8)) for _ in range(nf)]   # multiples of 4
+        px = rng.integers(0, 256, (nf, h, w, 3), dtype=np.uint8)
+        imgs = [np.full(ioff[f] + ipi * h + 32, 0x5A, np.uint8) for f in range(nf)]
+        for f in range(nf): imgs[f][ioff[f]: ioff[f] + ipi * h].reshape(h, ipi)[:, : 3 * w] = px[f].reshape(h, 3 * w)
+        d_ins = [dev(a) for a in imgs]; d_outs = [torch.full((ooff[f] + opi * h + 32,), 0x5A, dtype=torch.uint8, device="cuda") for f in range(nf)]
+        perm = [int(v) for v in rng.permutation(nf)]                     # the list order is not the allocation order
+        la = ([d_ins[f].data_ptr() + ioff[f] for f in perm], [d_outs[f].data_ptr() + ooff[f] for f in perm], w, h, order, fmt, uvm)
+        nvec = sum(1 for f in range(nf) if w % 16 == 0 and ipi % 16 == 0 and opi % 16 == 0 and ioff[f] % 16 == 0 and ooff[f] % 16 == 0)
+        st0 = (ctx.get_stat("bgr_packed422_list_frames_vec"), ctx.get_stat("bgr_packed422_list_frames_bytes"))
+        try:
+            if op == 0: ctx.equalize_hist_bgr_to_packed422_frames(*la, in_pitch=ipi, out_pitch=opi)
+            else: ctx.clahe_bgr_to_packed422_frames(*la, clip, tx, ty, in_pitch=ipi, out_pitch=opi)
+        except mi_lumaeq.MiError as e:
+            if e.status != 2: fail("bgrp422 list status", w, h, nf, op, tx, ty, e.status)
+            continue                                                   # a tile grid the planar forms refuse
+        ctx.synchronize()
+        if (ctx.get_stat("bgr_packed422_list_frames_vec") - st0[0], ctx.get_stat("bgr_packed422_list_frames_bytes") - st0[1]) != (nvec, nf - nvec):
+            fail("bgrp422 list counters", w, h, nf, ipi, opi, ioff, ooff, nvec)
+        for f in range(nf):
+            bgr = px[f] if order == 0 else px[f][:, :, ::-1]
+            nv = oracle.bgr_to_nv12(np.ascontiguousarray(np.repeat(bgr, 2, axis=0)))      # Y row 2r: row r's luma; UV row r: its left-pixel U V U V ...
+            y = np.ascontiguousarray(nv[: 2 * h * w].reshape(2 * h, w)[0::2]); uvr = nv[2 * h * w:].reshape(h, w)
+            fr = np.empty((h, 2 * w), np.uint8); fr[:, fmt - 2::2] = oracle.equalize_hist(y) if op == 0 else oracle.clahe(y, clip, tx, ty)
+            fr[:, 3 - fmt::2] = uvr if uvm == 1 else 128
+            want = np.full(d_outs[f].numel(), 0x5A, np.uint8); want[ooff[f]: ooff[f] + opi * h].reshape(h, opi)[:, : 2 * w] = fr
+            got = xfer.to_host(d_outs[f])
+            if not np.array_equal(got, want): fail("bgrp422 list", w, h, nf, op, order, fmt, uvm, clip, tx, ty, ipi, opi, ioff, ooff, perm, f, np.flatnonzero(got != want)[:8])
+            if not np.array_equal(xfer.to_host(d_ins[f]), imgs[f]): fail("bgrp422 list wrote its input", w, h, nf, op, f)
+        n["bgrp422list"] += 1
     else:           # 4:2:0 codes
         w, h = int(rng.integers(1, 60)) * (16 if rng.integers(0, 2) else 2), int(rng.integers(1, 40)) * 2
         bgr = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
