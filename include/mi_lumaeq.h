@@ -1155,8 +1155,71 @@ mi_status mi_equalize_hist_bgr_to_packed422_frames_dev(mi_ctx* ctx, const mi_bgr
 mi_status mi_clahe_bgr_to_packed422_frames_dev(mi_ctx* ctx, const mi_bgr_packed422_frame_dev* frames, int n_frames,
         int width, int height, size_t in_pitch, size_t out_pitch, int order, int format, mi_uv_mode uv_mode,
         double clip_limit, int tiles_x, int tiles_y, void* stream);
+/* mi_*_yuv420_to_packed422*: 4:2:0 frames (NV12, or planar I420 / YV12) in, packed 4:2:2 frames (YUY2 / UYVY) out with the luma
+ * equalized -- the decoder-to-playout path: a hardware decoder hands over NV12 and a software decoder I420 / YV12; SDI / HDMI playout
+ * cards, v4l2 output and loopback devices and virtual cameras take YUY2 / UYVY.  One pass instead of mi_*_yuv420_batch_dev /
+ * mi_*_nv12_batch_dev into scratch followed by a scatter of Y and a row-repeated UV plane outside the library.
+ * Pixels, per frame:
+ *   input  : as for mi_*_yuv420_to_bgr_batch_dev: `in` describes frame 0, frame f lies in->frame_stride bytes further in every plane;
+ *            in->chroma is MI_CHROMA_INTERLEAVED (NV12: c0 = the UV plane, c1 ignored) or MI_CHROMA_PLANAR (I420: c0 = U, c1 = V, both
+ *            at c_pitch).  A YV12 caller exchanges c0 and c1: c0 is always U.  Any address and any pitch are accepted (y_pitch >= W;
+ *            c_pitch >= W interleaved, >= W/2 planar).  The input is never written.  Width and height are even.
+ *   output : frame f at d_out + f * out_frame_stride, H rows of 2*W bytes at out_pitch >= 2*W.  MI_FMT_YUY2 writes exactly Y0 U Y1 V,
+ *            MI_FMT_UYVY exactly U Y0 V Y1.  d_out, out_pitch and out_frame_stride are multiples of 4 (the packed forms' rule).
+ *            Only the 2*W bytes of each output row are written: not the pitch padding, not the gaps between frames.
+ *   luma   : cv::equalizeHist / clahe->apply on the W x H Y plane: byte for byte what mi_equalize_hist_u8_batch_dev /
+ *            mi_clahe_u8_batch_dev give on the input Y plane.  The same clahe_fp_contract option, the same REFLECT_101 padding when the
+ *            tile grid does not divide the frame and the same limits on sizes and tile grids, with the same statuses, as those forms.
+ *   chroma : MI_UV_COPY: output rows 2r and 2r+1 both carry input chroma row r unchanged: macropixel k of both rows gets U[r][k],
+ *            V[r][k].  There is no vertical interpolation and no change of siting.  MI_UV_FILL128: every chroma byte 128; in->c0,
+ *            in->c1 and in->c_pitch are not read and the pointers may be NULL, as in mi_*_yuv420*.
+ *   This chroma rule is the library's own definition, consistent with the rest of the library: it is the chroma that
+ *   mi_*_nv12_to_bgr* / mi_*_yuv420_to_bgr* already apply to both rows of a pair, and mi_*_packed422_to_nv12* maps it back to the same
+ *   NV12 chroma, because (a + a + 1) >> 1 == a.  OpenCV has no call for it.
+ * Alignment: a lane moves a 16 x 2 pixel group (two 16-byte Y loads, one 16-byte UV load or two 8-byte loads from the U and V planes,
+ *   four 16-byte stores) when W % 16 == 0, in->y, y_pitch, in->frame_stride, d_out, out_pitch and out_frame_stride are all multiples of
+ *   16 and, under MI_UV_COPY, c0 and c_pitch are multiples of 16 (interleaved) or c0, c1 and c_pitch multiples of 8 (planar).  Otherwise
+ *   it processes a 2 x 2 block per lane with byte loads and one aligned dword store per macropixel -- slower, the same bytes out.
+ * Stages, per chunk of 256 frames: Y is a plane, so the histogram stages are the planar forms' own.  equalizeHist: one MI_K_HIST, one
+ *   MI_K_EQ_LUT and one MI_K_LUT_APPLY launch (LUT apply + pack), for either uv_mode.  CLAHE: the tile histograms and LUTs of
+ *   mi_clahe_u8_batch_dev, then ONE kernel charged to MI_K_CLAHE_INTERP that blends and packs (one pass, no MI_K_COLOR launch) when the
+ *   tile grid divides the frame, the tile width is a multiple of 16, clahe_fp_contract is off and the alignment above holds;
+ *   everything else runs mi_clahe_u8_batch_dev's launches into scratch Y planes and then one MI_K_COLOR launch that packs (two passes,
+ *   the same bytes).  Never the fused equalizeHist kernel nor the single-launch histogram + LUT kernel: option two_kernel_max_frames
+ *   does not apply.  Bytes moved per pixel: equalizeHist 1 + 1.5 + 2 = 4.5, one-pass CLAHE 4.5, two-pass CLAHE 6.5.
+ * Counters (mi_ctx_get_stat): "yuv420_packed422_onepass" / "yuv420_packed422_twopass" and "yuv420_packed422_vec" /
+ *   "yuv420_packed422_bytes" (the walk the pixel-writing kernel took: 16 x 2 groups / 2 x 2 blocks).  A device or host call with work
+ *   to do moves exactly one of each pair, NV12 and planar input alike; a call that returns an error or has a zero size moves none.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of the
+ *   same shape as the other batched device forms.
+ * mi_equalize_hist_yuv420_to_packed422 / mi_clahe_yuv420_to_packed422: ONE frame whose planes lie in host memory (in->frame_stride is
+ *   ignored) in; one packed frame in host memory at any address and any out_pitch >= 2*W out.  Synchronous; the planes are staged in
+ *   like mi_*_yuv420_to_bgr's and the frame comes back like mi_*_bgr_to_packed422's (tight planes and frames in pinned memory are DMA'd
+ *   as they are, everything else goes through the context's pinned staging).  On the device the frame is tight with every plane 16-byte
+ *   aligned, so a W % 16 == 0 frame takes the 16 x 2 groups.  Whatever the call returns, no copy on the caller's memory is in flight
+ *   any more when it returns.
+ * There is no in-place form: d_out equal to any input plane pointer is MI_ERR_BAD_ARG; any other overlap of input and output is
+ *   undefined, not checked.
+ * Errors, MI_ERR_BAD_ARG: a null ctx, `in`, in->y or d_out; under MI_UV_COPY a null c0 (or c1, planar); an odd width or an odd height
+ *   (refused even when another size is 0); a negative size; y_pitch < W; c_pitch below its row; out_pitch < 2*W; a d_out, out_pitch or
+ *   out_frame_stride of the device form that is not a multiple of 4; a `format` other than the two; a `chroma` other than the two; a
+ *   bad uv_mode; tiles <= 0.  width, height or n_frames of 0: MI_OK, nothing written (pointers and pitches are not looked at then).
+ *   Sizes and tile grids the planar forms refuse: MI_ERR_UNSUPPORTED, nothing written.  Nothing is enqueued unless every check passes.
+ * Not built: a frame-list form, a mi_pipe format, YVYU / VYUY, NV21, vertical chroma interpolation. */
+mi_status mi_equalize_hist_yuv420_to_packed422_batch_dev(mi_ctx* ctx, const mi_yuv420_planes* in,
+        void* d_out, size_t out_pitch, size_t out_frame_stride,
+        int width, int height, int n_frames, int format, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_yuv420_to_packed422_batch_dev(mi_ctx* ctx, const mi_yuv420_planes* in,
+        void* d_out, size_t out_pitch, size_t out_frame_stride,
+        int width, int height, int n_frames, int format, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
+mi_status mi_equalize_hist_yuv420_to_packed422(mi_ctx* ctx, const mi_yuv420_planes* in,
+        uint8_t* out, size_t out_pitch, int width, int height, int format, mi_uv_mode uv_mode);
+mi_status mi_clahe_yuv420_to_packed422(mi_ctx* ctx, const mi_yuv420_planes* in,
+        uint8_t* out, size_t out_pitch, int width, int height, int format, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y);
 
-/* ---- optional: pin caller-owned host buffers ----------------------------------------------------------------
+/* ---- optional: pin caller-owned host buffers----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at
  * OpenCVequalHist.cpp:115/:158).  Registering a pool's memory once lets the host-pointer forms DMA straight
  * from / into it instead of staging through the context's pinned buffers (contiguous planes only; anything

@@ -367,6 +367,10 @@ mi_status mi_ctx_synchronize(mi_ctx* c, void* stream)
 // "bgr_packed422_vec" / "bgr_packed422_bytes" (mi_*_bgr_to_packed422* calls, device and host forms, whose conversion kernel walked 16 x 1
 // pixel groups with 16-byte accesses / macropixels with byte loads: one count per call with work to do, by the walk stage 1 took; a
 // refused or empty call moves neither),
+// "yuv420_packed422_onepass" / "yuv420_packed422_twopass" and "yuv420_packed422_vec" / "yuv420_packed422_bytes" (mi_*_yuv420_to_packed422*
+// calls, device and host forms, NV12 and planar input alike: mapped and packed in one kernel / planar CLAHE into scratch first;
+// pixel-writing kernel on 16 x 2 pixel groups with 16-byte accesses / on 2 x 2 blocks with byte loads.  Every such call with work to do
+// moves exactly one counter of each pair; a refused or empty call moves none),
 // "bgr_packed422_list_frames_vec" / "bgr_packed422_list_frames_bytes" (FRAMES of mi_*_bgr_to_packed422_frames_dev calls whose conversion
 // kernel walked 16 x 1 pixel groups / macropixels, each by its own two addresses: the shape allows the groups and the frame's `in` and
 // `out` are multiples of 16, or not; counted once the whole call is enqueued, never for a refused call or one with nothing to do; list
@@ -414,6 +418,10 @@ mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
     if (!strcmp(name, "packed422_bgr_list_frames_bytes")) { *out = c->packed422_bgr_list_frames_bytes; return MI_OK; }
     if (!strcmp(name, "bgr_packed422_vec")) { *out = c->bgr_packed422_vec; return MI_OK; }
     if (!strcmp(name, "bgr_packed422_bytes")) { *out = c->bgr_packed422_bytes; return MI_OK; }
+    if (!strcmp(name, "yuv420_packed422_onepass")) { *out = c->yuv420_packed422_onepass; return MI_OK; }
+    if (!strcmp(name, "yuv420_packed422_twopass")) { *out = c->yuv420_packed422_twopass; return MI_OK; }
+    if (!strcmp(name, "yuv420_packed422_vec")) { *out = c->yuv420_packed422_vec; return MI_OK; }
+    if (!strcmp(name, "yuv420_packed422_bytes")) { *out = c->yuv420_packed422_bytes; return MI_OK; }
     if (!strcmp(name, "bgr_packed422_list_frames_vec")) { *out = c->bgr_packed422_list_frames_vec; return MI_OK; }
     if (!strcmp(name, "bgr_packed422_list_frames_bytes")) { *out = c->bgr_packed422_list_frames_bytes; return MI_OK; }
     return fail(c, MI_ERR_BAD_ARG, "unknown stat");

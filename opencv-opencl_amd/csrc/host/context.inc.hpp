@@ -179,6 +179,10 @@ struct mi_ctx {
                                                                         // left as 16-byte / as byte stores, each by its own address
     uint64_t bgr_packed422_vec = 0, bgr_packed422_bytes = 0;            // statistics "bgr_packed422_vec" / "bgr_packed422_bytes": mi_*_bgr_to_packed422* calls by the
                                                                         // walk their conversion kernel took (16 x 1 pixel groups / macropixels with byte loads)
+    uint64_t yuv420_packed422_onepass = 0, yuv420_packed422_twopass = 0;   // statistics "yuv420_packed422_onepass" / "yuv420_packed422_twopass": mi_*_yuv420_to_packed422*
+                                                                        // calls whose pixels were mapped and packed in one kernel / that ran the planar CLAHE into scratch first
+    uint64_t yuv420_packed422_vec = 0, yuv420_packed422_bytes = 0;      // statistics "yuv420_packed422_vec" / "yuv420_packed422_bytes": the same calls by the walk their
+                                                                        // pixel-writing kernel took (16 x 2 pixel groups / 2 x 2 blocks with byte loads)
     unsigned long long bgr_packed422_list_frames_vec = 0, bgr_packed422_list_frames_bytes = 0;   // statistics "bgr_packed422_list_frames_vec" /
                                                                         // "bgr_packed422_list_frames_bytes": FRAMES of mi_*_bgr_to_packed422_frames_dev calls by that
                                                                         // walk, each by its own two addresses

@@ -36,6 +36,8 @@
 //   kernels/bgr_nv12.hip.h         stage 1 of interleaved BGR / RGB in, NV12 out: convert into pitched planes and count the luma written
 //   kernels/bgr_yuv420.hip.h       that stage with planar 4:2:0 (I420 / YV12) out: the chroma stored into a U and a V plane
 //   kernels/bgr_packed422.hip.h    that stage with packed 4:2:2 (YUY2 / UYVY) out: every row with its own chroma, one dword per macropixel
+//   kernels/yuv420_packed422.hip.h the pixel-writing stages of 4:2:0 (NV12 / I420 / YV12) in, packed 4:2:2 (YUY2 / UYVY) out: LUT apply / CLAHE
+//                                  blend + pack, a byte zip of the mapped luma with the chroma row both output rows share
 //   kernels/yuv420.hip.h           the chroma of 4:2:0 frames between planar (I420 / YV12) and interleaved (NV12) layouts: copy, relayout or fill,
 //                                  on a batch at a frame stride or on a list of per-frame plane addresses
 //   kernels/yuv420_bgr.hip.h       the pixel-writing stages of planar 4:2:0 (I420 / YV12) in, interleaved BGR / RGB out: those of nv12_bgr.hip.h
@@ -59,6 +61,7 @@
 #include "kernels/bgr_nv12.hip.h"
 #include "kernels/bgr_yuv420.hip.h"
 #include "kernels/bgr_packed422.hip.h"
+#include "kernels/yuv420_packed422.hip.h"
 #include "kernels/yuv420.hip.h"
 #include "kernels/yuv420_bgr.hip.h"
 #include "kernels/packed422_bgr.hip.h"

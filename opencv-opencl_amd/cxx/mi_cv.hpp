@@ -610,6 +610,25 @@ inline void claheBGRToPacked422(const unsigned char* in, size_t inStep, unsigned
     detail::check(c, mi_clahe_bgr_to_packed422(c, in, inStep, out, outPitch, width, height, (int)order, (int)format, (mi_uv_mode)uv, clipLimit,
                                                tiles.width, tiles.height), "mi_clahe_bgr_to_packed422");
 }
+// The decoder-to-playout edge: the planes of the view (NV12, I420 or YV12 in host memory) in, one packed 4:2:2 frame (FMT_YUY2 /
+// FMT_UYVY) at outPitch >= 2*W out: cv::equalizeHist / CLAHE::apply on the Y plane, output rows 2r and 2r+1 both with input chroma row r
+// unchanged (UV_COPY) or chroma 128 (UV_FILL128, the view's chroma is not read).  Width and height are even.
+inline void equalizeHistYUV420ToPacked422(const YUV420View& in, unsigned char* out, size_t outPitch, int width, int height,
+                                          PackedFormat format = FMT_YUY2, UVMode uv = UV_COPY)
+{
+    mi_ctx* c = detail::thread_ctx();
+    const mi_yuv420_planes a = in.planes();
+    detail::check(c, mi_equalize_hist_yuv420_to_packed422(c, &a, out, outPitch, width, height, (int)format, (mi_uv_mode)uv),
+                  "mi_equalize_hist_yuv420_to_packed422");
+}
+inline void claheYUV420ToPacked422(const YUV420View& in, unsigned char* out, size_t outPitch, int width, int height, double clipLimit,
+                                   Size tiles, PackedFormat format = FMT_YUY2, UVMode uv = UV_COPY)
+{
+    mi_ctx* c = detail::thread_ctx();
+    const mi_yuv420_planes a = in.planes();
+    detail::check(c, mi_clahe_yuv420_to_packed422(c, &a, out, outPitch, width, height, (int)format, (mi_uv_mode)uv, clipLimit, tiles.width,
+                                                  tiles.height), "mi_clahe_yuv420_to_packed422");
+}
 
 // BASELINE.json config 5 read literally: cvtColor(COLOR_YUV2BGR_NV12) -> split -> equalizeHist on B, G and R -> merge ->
 // cvtColor(COLOR_BGR2YUV_I420) + U/V interleave, NV12 in -> NV12 out in one call (no file of the reference does this;

@@ -70,6 +70,8 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_bgr_to_packed422_batch_dev", "mi_clahe_bgr_to_packed422_batch_dev",
     "mi_equalize_hist_bgr_to_packed422", "mi_clahe_bgr_to_packed422",
     "mi_equalize_hist_bgr_to_packed422_frames_dev", "mi_clahe_bgr_to_packed422_frames_dev",
+    "mi_equalize_hist_yuv420_to_packed422_batch_dev", "mi_clahe_yuv420_to_packed422_batch_dev",
+    "mi_equalize_hist_yuv420_to_packed422", "mi_clahe_yuv420_to_packed422",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -327,6 +329,10 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_bgr_to_packed422.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, i, d, i, i]
     L.mi_equalize_hist_bgr_to_packed422_frames_dev.argtypes = [vp, C.POINTER(BgrPacked422FrameDev), i, i, i, sz, sz, i, i, i, vp]
     L.mi_clahe_bgr_to_packed422_frames_dev.argtypes = [vp, C.POINTER(BgrPacked422FrameDev), i, i, i, sz, sz, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_yuv420_to_packed422_batch_dev.argtypes = [vp, yp, vp, sz, sz, i, i, i, i, i, vp]
+    L.mi_clahe_yuv420_to_packed422_batch_dev.argtypes = [vp, yp, vp, sz, sz, i, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_yuv420_to_packed422.argtypes = [vp, yp, vp, sz, i, i, i, i]
+    L.mi_clahe_yuv420_to_packed422.argtypes = [vp, yp, vp, sz, i, i, i, i, d, i, i]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -1473,6 +1479,65 @@ class Context:
         img, h, w, step, out = self._bgr_packed422_host(img, out, "clahe_bgr_to_packed422")
         self._chk(self._L.mi_clahe_bgr_to_packed422(self._h, img.ctypes.data, step, out.ctypes.data, _step(out), w, h, int(order), int(fmt),
                                                   int(uv_mode), float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_bgr_to_packed422")
+        return out
+
+    # ---- 4:2:0 frames (NV12, or I420 / YV12 planes) in, packed 4:2:2 (YUY2 / UYVY) out in the pass that maps the luma ----
+    def equalize_hist_yuv420_to_packed422_batch_dev(self, src, d_out, width, height, n_frames, fmt=FMT_YUY2, uv_mode=UV_COPY,
+                                                    out_pitch=None, out_frame=None, stream=0):
+        """mi_equalize_hist_yuv420_to_packed422_batch_dev.  src: a Yuv420Planes holding device addresses (Yuv420Planes.nv12 / .i420 /
+        .yv12 for tight batches, the fields themselves for pitched or separately allocated planes); d_out: the packed frames (a torch
+        tensor or a raw address).  The tight output is the default: out_pitch 2*W, out_frame = out_pitch * H."""
+        op = 2 * int(width) if out_pitch is None else int(out_pitch)
+        fo = op * int(height) if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_equalize_hist_yuv420_to_packed422_batch_dev(self._h, C.byref(src), _dptr(d_out), op, fo, int(width),
+                                                                       int(height), int(n_frames), int(fmt), int(uv_mode), stream),
+                  "mi_equalize_hist_yuv420_to_packed422_batch_dev")
+
+    def clahe_yuv420_to_packed422_batch_dev(self, src, d_out, width, height, n_frames, fmt=FMT_YUY2, uv_mode=UV_COPY, clip_limit=2.0,
+                                            tiles_x=8, tiles_y=8, out_pitch=None, out_frame=None, stream=0):
+        """mi_clahe_yuv420_to_packed422_batch_dev; arguments as equalize_hist_yuv420_to_packed422_batch_dev, plus the CLAHE parameters."""
+        op = 2 * int(width) if out_pitch is None else int(out_pitch)
+        fo = op * int(height) if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_clahe_yuv420_to_packed422_batch_dev(self._h, C.byref(src), _dptr(d_out), op, fo, int(width), int(height),
+                                                               int(n_frames), int(fmt), int(uv_mode), float(clip_limit), int(tiles_x),
+                                                               int(tiles_y), stream), "mi_clahe_yuv420_to_packed422_batch_dev")
+
+    def _yuv420_packed422_host(self, frame, width, height, src_fmt, out, name):
+        if isinstance(frame, Yuv420Planes):                 # host addresses and pitches of the caller's own planes
+            a = frame
+        else:
+            if src_fmt not in _YUV420_FMTS:
+                raise MiError(1, name, 'src_fmt must be "nv12", "i420" or "yv12"')
+            if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or not frame.flags.c_contiguous:
+                raise MiError(2, name, "expected a contiguous uint8 ndarray")
+            if width >= 0 and height >= 0 and frame.size != width * height * 3 // 2:
+                raise MiError(1, name, "a 4:2:0 frame must hold width*height*3/2 bytes")
+            a = _YUV420_FMTS[src_fmt](frame.ctypes.data, width, height)
+        if out is None:
+            out = np.empty((max(height, 0), 2 * max(width, 0)), np.uint8)
+        out = self._packed_host(out, width, name)
+        if out.shape[0] != height:
+            raise MiError(1, name, "out must have one row per frame row")
+        return a, out
+
+    def equalize_hist_yuv420_to_packed422(self, frame, width: int, height: int, src_fmt: str = "nv12", fmt: int = FMT_YUY2,
+                                          uv_mode: int = UV_COPY, out: np.ndarray | None = None) -> np.ndarray:
+        """mi_equalize_hist_yuv420_to_packed422 on a tight host frame of W*H*3/2 bytes whose chroma lies as src_fmt in {"nv12", "i420",
+        "yv12"} says (or a Yuv420Planes of host addresses; src_fmt is then ignored): the packed frame out -- `out` when given (an
+        H x pitch-bytes uint8 array, pitch >= 2*W; a view with padded rows is fine), else a new tight H x 2W array."""
+        a, out = self._yuv420_packed422_host(frame, int(width), int(height), src_fmt, out, "equalize_hist_yuv420_to_packed422")
+        self._chk(self._L.mi_equalize_hist_yuv420_to_packed422(self._h, C.byref(a), out.ctypes.data, _step(out), int(width), int(height),
+                                                             int(fmt), int(uv_mode)), "mi_equalize_hist_yuv420_to_packed422")
+        return out
+
+    def clahe_yuv420_to_packed422(self, frame, width: int, height: int, src_fmt: str = "nv12", fmt: int = FMT_YUY2,
+                                  uv_mode: int = UV_COPY, clip_limit: float = 2.0, tiles_x: int = 8, tiles_y: int = 8,
+                                  out: np.ndarray | None = None) -> np.ndarray:
+        """mi_clahe_yuv420_to_packed422; arguments as equalize_hist_yuv420_to_packed422, plus the CLAHE parameters."""
+        a, out = self._yuv420_packed422_host(frame, int(width), int(height), src_fmt, out, "clahe_yuv420_to_packed422")
+        self._chk(self._L.mi_clahe_yuv420_to_packed422(self._h, C.byref(a), out.ctypes.data, _step(out), int(width), int(height),
+                                                     int(fmt), int(uv_mode), float(clip_limit), int(tiles_x), int(tiles_y)),
+                  "mi_clahe_yuv420_to_packed422")
         return out
 
     # ---- colour-domain neighbours (N3) ----

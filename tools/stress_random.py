@@ -8,7 +8,9 @@ I420 / YV12 planes out at that layout, every frame at an offset of its own) agai
 out on a frame list (every buffer and every image an allocation of its own, images at any byte offset) against the oracle and the batch form,
 and BGR / RGB in, packed 4:2:2 out (every row with the chroma of its own left pixels) at random pitched layouts, aligned and not, odd heights
 included, against the oracle on the row-doubled image (tests/bgr_packed422_ref.py), as a batch and as a frame list (every image and every
-frame an allocation of its own at an offset of its own: 16-pixel groups and macropixels in one launch).
+frame an allocation of its own at an offset of its own: 16-pixel groups and macropixels in one launch), and 4:2:0 in (NV12 / I420 / YV12),
+packed 4:2:2 out (mi_*_yuv420_to_packed422_batch_dev: every chroma row under two output rows) at random pitched layouts on both sides
+of its vector and one-pass conditions, against the oracle's luma and the input's own chroma.
     python tools/stress_random.py [seconds] [seed] [option=value ...]        prints a line every ~15 s, exits non-zero on the first mismatch"""
 import sys, time
 sys.path.insert(0, "opencv-opencl_amd/python"); sys.path.insert(0, ".")
@@ -20,12 +22,12 @@ rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 ctx = mi_lumaeq.Context(0)
 for kv in sys.argv[3:]:                                          # name=value options for the whole run, e.g. clahe16_wide=2 (mid kernel always launched)
     k_, v_ = kv.split("="); ctx.set_option(k_, int(v_)); print("option", k_, "=", v_, flush=True)
-t0 = last = time.time(); n = {"roi": 0, "grid": 0, "small": 0, "c16": 0, "420": 0, "nv12": 0, "nv12bgr": 0, "yuv420bgr": 0, "yuv420bgrlist": 0, "bgryuv420list": 0, "p422bgrlist": 0, "bgrp422": 0, "bgrp422list": 0}
+t0 = last = time.time(); n = {"roi": 0, "grid": 0, "small": 0, "c16": 0, "420": 0, "nv12": 0, "nv12bgr": 0, "yuv420bgr": 0, "yuv420bgrlist": 0, "bgryuv420list": 0, "p422bgrlist": 0, "bgrp422": 0, "bgrp422list": 0, "yuv420p422": 0}
 def dev(a): return xfer.to_device(np.ascontiguousarray(a))
 def fail(what, *info):
     print("MISMATCH", what, info, flush=True); sys.exit(1)
 while time.time() - t0 < budget:
-    k = int(rng.integers(0, 10))
+    k = int(rng.integers(0, 11))
     if k == 0:      # ROI batch on the device: random pitches, origins, sizes
         w, h, nf = int(rng.integers(1, 700)), int(rng.integers(1, 90)), int(rng.integers(1, 6))
         sp = w + int(rng.integers(0, 40)); sp += (16 - sp % 16) % 16 if rng.integers(0, 2) else 0
@@ -287,6 +289,51 @@ while time.time() - t0 < budget:
             if not np.array_equal(got, want): fail("bgrp422 list", w, h, nf, op, order, fmt, uvm, clip, tx, ty, ipi, opi, ioff, ooff, perm, f, np.flatnonzero(got != want)[:8])
             if not np.array_equal(xfer.to_host(d_ins[f]), imgs[f]): fail("bgrp422 list wrote its input", w, h, nf, op, f)
         n["bgrp422list"] += 1
+    elif k == 10:   # 4:2:0 in (NV12 / I420 / YV12), packed 4:2:2 out: pitched layouts, aligned (16 x 2 groups, CLAHE in one pass where the grid allows) or not, both ops
+        w, h, nf = int(rng.integers(1, 40)) * (16 if rng.integers(0, 2) else 2), int(rng.integers(1, 40)) * 2, int(rng.integers(1, 6))
+        op, sfmt, fmt, uvm = int(rng.integers(0, 2)), str(rng.choice(["nv12", "i420", "yv12"])), int(rng.integers(2, 4)), int(rng.integers(0, 2))
+        tx, ty = int(rng.choice([1, 2, 4, 8, 3, 16])), int(rng.integers(1, 6)); clip = float(rng.choice([0.0, 1.0, 2.0, 40.0]))
+        planar = sfmt != "nv12"; cw = w // 2 if planar else w
+        al = 16 if rng.integers(0, 4) else 1; cal = (8 if planar and al == 16 and rng.integers(0, 2) else al); oal = max(al, 4)
+        def pad(v, a): return (v + a - 1) // a * a + a * int(rng.integers(0, 40 // a + 1))
+        ypi, cpi, opi = pad(w, al), pad(cw, cal), pad(2 * w, oal)
+        yoff = pad(0, al); a_off = pad(yoff + ypi * h, cal); b_off = pad(a_off + cpi * (h // 2), cal) if planar else a_off
+        fi = pad(b_off + cpi * (h // 2), al); ooff, fo = pad(0, oal), pad(opi * h, oal)
+        u_off, v_off = (a_off, b_off) if sfmt != "yv12" else (b_off, a_off)
+        Y = rng.integers(0, int(rng.integers(2, 257)), (nf, h, w), dtype=np.uint8); U, V = (rng.integers(0, 256, (nf, h // 2, w // 2), dtype=np.uint8) for _ in range(2))
+        img = np.full(fi * nf + 64, 0x5A, np.uint8)
+        for f in range(nf):
+            b = f * fi
+            img[b + yoff: b + yoff + ypi * h].reshape(h, ypi)[:, :w] = Y[f]
+            if planar:
+                img[b + u_off: b + u_off + cpi * (h // 2)].reshape(h // 2, cpi)[:, :cw] = U[f]; img[b + v_off: b + v_off + cpi * (h // 2)].reshape(h // 2, cpi)[:, :cw] = V[f]
+            else:
+                r = img[b + a_off: b + a_off + cpi * (h // 2)].reshape(h // 2, cpi); r[:, 0:w:2] = U[f]; r[:, 1:w:2] = V[f]
+        d_in = dev(img); d_out = torch.full((ooff + fo * nf + 64,), 0x5A, dtype=torch.uint8, device="cuda"); base = d_in.data_ptr()
+        pl = mi_lumaeq.Yuv420Planes(base + yoff, ypi, base + u_off if uvm else None, base + v_off if uvm and planar else None, cpi if uvm else 0, fi,
+                                    mi_lumaeq.CHROMA_PLANAR if planar else mi_lumaeq.CHROMA_INTERLEAVED)
+        terms = [yoff, ypi, fi, ooff, opi, fo]; cterms = ([u_off, cpi] + ([v_off] if planar else [])) if uvm else []
+        vec = w % 16 == 0 and all(t % 16 == 0 for t in terms) and all(t % (8 if planar else 16) == 0 for t in cterms)
+        one = op == 0 or (vec and w % tx == 0 and h % ty == 0 and (w // tx) % 16 == 0 and tx + 1 <= 15)
+        names = ("yuv420_packed422_onepass", "yuv420_packed422_twopass", "yuv420_packed422_vec", "yuv420_packed422_bytes"); st0 = [ctx.get_stat(s) for s in names]
+        a = (pl, d_out.data_ptr() + ooff, w, h, nf, fmt, uvm); kw = dict(out_pitch=opi, out_frame=fo)
+        try:
+            if op == 0: ctx.equalize_hist_yuv420_to_packed422_batch_dev(*a, **kw)
+            else: ctx.clahe_yuv420_to_packed422_batch_dev(*a, clip, tx, ty, **kw)
+        except mi_lumaeq.MiError as e:
+            if e.status != 2: fail("yuv420p422 status", w, h, nf, op, tx, ty, e.status)
+            continue                                                   # a tile grid the planar forms refuse
+        ctx.synchronize(); out = xfer.to_host(d_out); want = np.full(out.size, 0x5A, np.uint8)
+        if [ctx.get_stat(s) - v for s, v in zip(names, st0)] != [int(one), int(not one), int(vec), int(not vec)]:
+            fail("yuv420p422 counters", w, h, nf, op, sfmt, uvm, tx, ty, terms, cterms, vec, one)
+        for f in range(nf):
+            fr = np.empty((h, 2 * w), np.uint8); fr[:, fmt - 2::2] = oracle.equalize_hist(Y[f]) if op == 0 else oracle.clahe(Y[f], clip, tx, ty)
+            uvr = np.empty((h // 2, w), np.uint8); uvr[:, 0::2] = U[f]; uvr[:, 1::2] = V[f]
+            fr[:, 3 - fmt::2] = np.repeat(uvr, 2, axis=0) if uvm == 1 else 128          # chroma row r under output rows 2r and 2r + 1
+            want[ooff + f * fo: ooff + f * fo + opi * h].reshape(h, opi)[:, : 2 * w] = fr
+        if not np.array_equal(out, want): fail("yuv420p422", w, h, nf, op, sfmt, fmt, uvm, clip, tx, ty, terms, cterms, np.flatnonzero(out != want)[:8])
+        if not np.array_equal(xfer.to_host(d_in), img): fail("yuv420p422 wrote its input", w, h, nf, op)
+        n["yuv420p422"] += 1
     else:           # 4:2:0 codes
         w, h = int(rng.integers(1, 60)) * (16 if rng.integers(0, 2) else 2), int(rng.integers(1, 40)) * 2
         bgr = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
