@@ -1218,6 +1218,70 @@ mi_status mi_equalize_hist_yuv420_to_packed422(mi_ctx* ctx, const mi_yuv420_plan
 mi_status mi_clahe_yuv420_to_packed422(mi_ctx* ctx, const mi_yuv420_planes* in,
         uint8_t* out, size_t out_pitch, int width, int height, int format, mi_uv_mode uv_mode,
         double clip_limit, int tiles_x, int tiles_y);
+/* mi_*_yuv420_to_packed422_frames_dev: the same conversion on a LIST of device frames, each at its own four addresses -- the form in
+ * which both real sides are pools: a decoder hands out surfaces whose Y, U and V (or UV) planes are separate pitched allocations
+ * (data[0..2], linesize[0..2]); a playout card, a v4l2 output queue or a virtual camera hands out one buffer per frame, padded to
+ * bytesperline.  The batch form needs each side in one allocation at a constant frame stride; one n_frames = 1 batch call per frame
+ * costs a launch sequence per frame with tiny grids, and repacking both pools through strided scratch moves 1.5 + 2 bytes per pixel
+ * more each way.  `frames` is a host array of n_frames entries, read only during the call; the pointers in it are device pointers on
+ * the context's device.
+ * Shape: all frames of one call share width, height (both even), y_pitch, c_pitch, chroma, out_pitch, format and uv_mode; each has
+ *   its own four addresses.  There are no per-frame pitches.
+ *   y  : H rows of W bytes at y_pitch >= W
+ *   chroma == MI_CHROMA_INTERLEAVED: c0 is the UV plane, H/2 rows of W bytes at c_pitch >= W; c1 is ignored and may be NULL.
+ *   chroma == MI_CHROMA_PLANAR: c0 is always U and c1 always V, each H/2 rows of W/2 bytes at c_pitch >= W/2 (both planes share the
+ *        pitch): a YV12 caller exchanges the two addresses.
+ *   out: H rows of 2*W bytes at out_pitch >= 2*W; every `out` and out_pitch are multiples of 4 (the packed forms' rule).
+ *   Unlike mi_*_yuv420_to_bgr_frames_dev an interleaved list is not handed to another form: one pair of entry points and one set of
+ *   counters serves both layouts.
+ * Bytes: per frame the output is byte for byte what mi_*_yuv420_to_packed422_batch_dev writes for that frame alone at the same pitches:
+ *   MI_FMT_YUY2 exactly Y0 U Y1 V, MI_FMT_UYVY exactly U Y0 V Y1; the luma is cv::equalizeHist / CLAHE::apply on the Y plane (what the
+ *   planar forms give); input chroma row r goes unchanged under output rows 2r and 2r+1, or every chroma byte is 128.  The
+ *   clahe_fp_contract option is honoured, REFLECT_101 padding applies when the tile grid does not divide the frame, and the limits on
+ *   sizes and tile grids are the batch form's, with the same statuses.
+ * Writes: only the 2*W bytes of each output row are written, not the pitch padding, nothing before or behind a frame; the input planes
+ *   are never written.
+ * MI_UV_FILL128: c0, c1 and c_pitch are not read and decide nothing -- not the walk, not the overlap check, not an error; the pointers
+ *   may be NULL.
+ * Alignment: beyond the multiples of 4 above, none is required.  The per-frame alignment decides the access width: the shape allows
+ *   16 x 2 pixel groups when W % 16 == 0, y_pitch and out_pitch are multiples of 16 and, under MI_UV_COPY, c_pitch is a multiple of 16
+ *   (interleaved) or 8 (planar); a frame then takes the groups when its y and out are multiples of 16 and, under MI_UV_COPY, its c0 is
+ *   a multiple of 16 (interleaved) or its c0 and c1 are multiples of 8 (planar), and any other frame of the same call processes 2 x 2
+ *   blocks with byte loads and one aligned dword store per macropixel while its neighbours stay vectorised -- slower, the same bytes out.
+ * Stages, per chunk of 64 frames of the list (not the batch form's 256): equalizeHist is one MI_K_HIST, one MI_K_EQ_LUT and one
+ *   MI_K_LUT_APPLY launch (LUT apply + pack), for either uv_mode; never the fused equalizeHist kernel nor the single-launch histogram
+ *   + LUT kernel (option two_kernel_max_frames does not apply).  CLAHE runs in one pass (the tile LUTs, then ONE MI_K_CLAHE_INTERP
+ *   launch that blends and packs) when the shape is the batch form's one-pass shape (the tile grid divides the frame, tile width a
+ *   multiple of 16, tiles_x <= 14), clahe_fp_contract is off, the shape rule above holds and every frame of the call satisfies the
+ *   address rule; otherwise the whole call runs the planar CLAHE into scratch Y planes of the context and then one MI_K_COLOR launch
+ *   that packs from there: the same bytes in one more pass.  (In that fallback the Y address the rule sees is the scratch plane's,
+ *   which is aligned: the frame's y drops out of its rule; the pitches are still the caller's.)  Launches are charged to the same
+ *   profiling slots as the batch form.
+ * Counters (mi_ctx_get_stat): "yuv420_packed422_onepass" / "yuv420_packed422_twopass" count the calls of the list form too, one count
+ *   a call (equalizeHist always counts as one-pass).  "yuv420_packed422_list_frames_vec" / "yuv420_packed422_list_frames_bytes" count
+ *   the FRAMES (not calls) of list calls by the walk their pixel-writing kernel took, n_frames in total per call.
+ *   "yuv420_packed422_vec" / "yuv420_packed422_bytes" are not touched by list calls.  A call that returns an error or has nothing to do
+ *   moves none.
+ * Overlap: there is no in-place form.  MI_ERR_BAD_ARG when the rows of a frame's `out` meet the rows of its own Y plane or, under
+ *   MI_UV_COPY, of its own chroma plane(s) (compared as address ranges).  U and V are not compared with each other: they may be the two
+ *   halves of the rows of one pitched plane (c1 = c0 + W/2, c_pitch = W).  The same input planes may appear in several entries (inputs
+ *   are only read).  Outputs that overlap each other or ANOTHER frame's planes give undefined results and are not checked.
+ * Errors, MI_ERR_BAD_ARG: a null ctx; a null `frames` with n_frames > 0; a null y or out in any entry; under MI_UV_COPY a null c0 (or
+ *   c1, planar) in any entry; an `out` in any entry or an out_pitch that is not a multiple of 4; a `format` other than the two; a
+ *   `chroma` other than the two; a bad uv_mode; a negative size; an odd width or an odd height (refused even when another size is 0, as
+ *   in the batch form); y_pitch < W; under MI_UV_COPY a c_pitch below its row (W interleaved, W/2 planar); out_pitch < 2*W; tiles <= 0;
+ *   the overlap above.  Sizes and tile grids the planar forms refuse: the status they give (MI_ERR_UNSUPPORTED).  width, height or
+ *   n_frames of 0: MI_OK, nothing written (n_frames == 0 with a null list is MI_OK).  Nothing is enqueued unless every frame passes the
+ *   checks: a bad last entry leaves the earlier frames' outputs untouched.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of
+ *   the same shape as the other device list forms; a captured graph holds the addresses it was captured with.
+ * Not built: a mi_pipe format, per-frame pitches, YVYU / VYUY, NV21, vertical chroma interpolation. */
+typedef struct mi_yuv420_packed422_frame_dev { const void* y; const void* c0; const void* c1; void* out; } mi_yuv420_packed422_frame_dev;  /* 32 bytes on LP64 */
+mi_status mi_equalize_hist_yuv420_to_packed422_frames_dev(mi_ctx* ctx, const mi_yuv420_packed422_frame_dev* frames, int n_frames,
+        int width, int height, size_t y_pitch, size_t c_pitch, int chroma, size_t out_pitch, int format, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_yuv420_to_packed422_frames_dev(mi_ctx* ctx, const mi_yuv420_packed422_frame_dev* frames, int n_frames,
+        int width, int height, size_t y_pitch, size_t c_pitch, int chroma, size_t out_pitch, int format, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
 
 /* ---- optional: pin caller-owned host buffers----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at

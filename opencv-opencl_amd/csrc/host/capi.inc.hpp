@@ -374,7 +374,13 @@ mi_status mi_ctx_synchronize(mi_ctx* c, void* stream)
 // "bgr_packed422_list_frames_vec" / "bgr_packed422_list_frames_bytes" (FRAMES of mi_*_bgr_to_packed422_frames_dev calls whose conversion
 // kernel walked 16 x 1 pixel groups / macropixels, each by its own two addresses: the shape allows the groups and the frame's `in` and
 // `out` are multiples of 16, or not; counted once the whole call is enqueued, never for a refused call or one with nothing to do; list
-// calls do not touch "bgr_packed422_vec" / "bgr_packed422_bytes").
+// calls do not touch "bgr_packed422_vec" / "bgr_packed422_bytes"),
+// "yuv420_packed422_list_frames_vec" / "yuv420_packed422_list_frames_bytes" (FRAMES of mi_*_yuv420_to_packed422_frames_dev calls whose
+// pixel-writing kernel walked 16 x 2 pixel groups / 2 x 2 blocks, each by its own addresses: the shape allows the groups, the frame's
+// `y` -- the caller's, or the scratch plane's in the two-pass CLAHE fallback -- and `out` are multiples of 16 and, under MI_UV_COPY, its
+// c0 a multiple of 16 (interleaved) or its c0 and c1 multiples of 8 (planar), or not; n_frames in total per call, counted once the whole
+// call is enqueued, never for a refused call or one with nothing to do.  A list call moves one of "yuv420_packed422_onepass" /
+// "yuv420_packed422_twopass" and does not touch "yuv420_packed422_vec" / "yuv420_packed422_bytes").
 mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
 {
     ENTER(c);
@@ -424,6 +430,8 @@ mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
     if (!strcmp(name, "yuv420_packed422_bytes")) { *out = c->yuv420_packed422_bytes; return MI_OK; }
     if (!strcmp(name, "bgr_packed422_list_frames_vec")) { *out = c->bgr_packed422_list_frames_vec; return MI_OK; }
     if (!strcmp(name, "bgr_packed422_list_frames_bytes")) { *out = c->bgr_packed422_list_frames_bytes; return MI_OK; }
+    if (!strcmp(name, "yuv420_packed422_list_frames_vec")) { *out = c->yuv420_packed422_list_frames_vec; return MI_OK; }
+    if (!strcmp(name, "yuv420_packed422_list_frames_bytes")) { *out = c->yuv420_packed422_list_frames_bytes; return MI_OK; }
     return fail(c, MI_ERR_BAD_ARG, "unknown stat");
 }
 

@@ -186,6 +186,9 @@ struct mi_ctx {
     unsigned long long bgr_packed422_list_frames_vec = 0, bgr_packed422_list_frames_bytes = 0;   // statistics "bgr_packed422_list_frames_vec" /
                                                                         // "bgr_packed422_list_frames_bytes": FRAMES of mi_*_bgr_to_packed422_frames_dev calls by that
                                                                         // walk, each by its own two addresses
+    unsigned long long yuv420_packed422_list_frames_vec = 0, yuv420_packed422_list_frames_bytes = 0;   // statistics "yuv420_packed422_list_frames_vec" /
+                                                                        // "yuv420_packed422_list_frames_bytes": FRAMES of mi_*_yuv420_to_packed422_frames_dev calls by
+                                                                        // the walk their pixel-writing kernel took (16 x 2 groups / 2 x 2 blocks), each by its own addresses
 };
 
 namespace {

@@ -76,8 +76,11 @@ Yuv420P422Job yuv420_packed422_job(const Yuv420P422Args& a, int f0, const uint8_
 
 // LUT apply + pack (luts != nullptr, MI_K_LUT_APPLY) or the pack alone (MI_K_COLOR).  The grid rule is launch_nv12_to_bgr's on this
 // form's bytes: half of what is read and written (1.5 + 2 B/px) as the byte basis, one row unit per pair of rows, the cap 2048; in
-// 16 x 2 groups a workgroup pass covers 8192 pixels, in 2 x 2 blocks 1024.
-mi_status launch_yuv420_to_packed422(mi_ctx* c, hipStream_t s, const Yuv420P422Job& j, int nf, int format, bool planar, const uint8_t* luts)
+// 16 x 2 groups a workgroup pass covers 8192 pixels, in 2 x 2 blocks 1024.  `fl`: a chunk of a frame list (at most kFramesPerLaunch
+// frames, yuv420_packed422_frames.inc.hpp): the same grid on the *_frames_kernel entry; `j` then carries the shape, and j.vec what
+// the shape allows.
+mi_status launch_yuv420_to_packed422(mi_ctx* c, hipStream_t s, const Yuv420P422Job& j, int nf, int format, bool planar, const uint8_t* luts,
+                                     const Yuv420P422List* fl = nullptr)
 {
     const long long px = (long long)j.width * j.height;
     int B = blocks_per_frame(c, px * 7 / 4, j.height / 2, nf, 2048);
@@ -86,8 +89,10 @@ mi_status launch_yuv420_to_packed422(mi_ctx* c, hipStream_t s, const Yuv420P422J
     const dim3 grid(B, nf), block(kThreads);
 #define MI_YUV420_P422_LAUNCH(F, P)                                                                                                  \
     do {                                                                                                                             \
-        if (luts) LAUNCH(c, s, MI_K_LUT_APPLY, (yuv420_to_packed422_kernel<F, P, true>), grid, block, 0, j, luts);                   \
-        else      LAUNCH(c, s, MI_K_COLOR, (yuv420_to_packed422_kernel<F, P, false>), grid, block, 0, j, luts);                      \
+        if (fl && luts) LAUNCH(c, s, MI_K_LUT_APPLY, (yuv420_to_packed422_frames_kernel<F, P, true>), grid, block, 0, *fl, j, luts); \
+        else if (fl)    LAUNCH(c, s, MI_K_COLOR, (yuv420_to_packed422_frames_kernel<F, P, false>), grid, block, 0, *fl, j, luts);    \
+        else if (luts)  LAUNCH(c, s, MI_K_LUT_APPLY, (yuv420_to_packed422_kernel<F, P, true>), grid, block, 0, j, luts);             \
+        else            LAUNCH(c, s, MI_K_COLOR, (yuv420_to_packed422_kernel<F, P, false>), grid, block, 0, j, luts);                \
     } while (0)
     const bool uyvy = format == MI_FMT_UYVY;
     if (uyvy && planar) MI_YUV420_P422_LAUNCH(1, true);
@@ -98,9 +103,10 @@ mi_status launch_yuv420_to_packed422(mi_ctx* c, hipStream_t s, const Yuv420P422J
     return MI_OK;
 }
 
-// CLAHE blend + pack of nf frames whose tile LUTs are in `luts`: the grid of launch_nv12_bgr_interp
+// CLAHE blend + pack of nf frames whose tile LUTs are in `luts`: the grid of launch_nv12_bgr_interp.  `fl`: as for
+// launch_yuv420_to_packed422.
 mi_status launch_yuv420_packed422_interp(mi_ctx* c, hipStream_t s, const Yuv420P422Job& j, const ClaheGeom& g, int nf, int format, bool planar,
-                                         const uint8_t* luts)
+                                         const uint8_t* luts, const Yuv420P422List* fl = nullptr)
 {
     const int ngroups = j.width / kInterpPx;
     const int groups = std::min(ngroups, kThreads);
@@ -111,6 +117,16 @@ mi_status launch_yuv420_packed422_interp(mi_ctx* c, hipStream_t s, const Yuv420P
     const dim3 grid(bands * subs, nf, segs);
     const size_t lds = (size_t)(g.tiles_x + 1) * 256 * 4 * sizeof(float);
     const bool uyvy = format == MI_FMT_UYVY;
+#define MI_YUV420_P422_INTERP_FRAMES(F, P)                                                                                           \
+    LAUNCH(c, s, MI_K_CLAHE_INTERP, (yuv420_packed422_clahe_interp_frames_kernel<F, P>), grid, dim3(kThreads), lds, *fl, j, g, luts, subs, groups)
+    if (fl) {
+        if (uyvy && planar) MI_YUV420_P422_INTERP_FRAMES(1, true);
+        else if (uyvy)      MI_YUV420_P422_INTERP_FRAMES(1, false);
+        else if (planar)    MI_YUV420_P422_INTERP_FRAMES(0, true);
+        else                MI_YUV420_P422_INTERP_FRAMES(0, false);
+        return MI_OK;
+    }
+#undef MI_YUV420_P422_INTERP_FRAMES
     if (uyvy && planar) LAUNCH(c, s, MI_K_CLAHE_INTERP, (yuv420_packed422_clahe_interp_kernel<1, true>), grid, dim3(kThreads), lds, j, g, luts, subs, groups);
     else if (uyvy)      LAUNCH(c, s, MI_K_CLAHE_INTERP, (yuv420_packed422_clahe_interp_kernel<1, false>), grid, dim3(kThreads), lds, j, g, luts, subs, groups);
     else if (planar)    LAUNCH(c, s, MI_K_CLAHE_INTERP, (yuv420_packed422_clahe_interp_kernel<0, true>), grid, dim3(kThreads), lds, j, g, luts, subs, groups);

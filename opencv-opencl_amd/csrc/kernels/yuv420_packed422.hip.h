@@ -212,4 +212,173 @@ __global__ __launch_bounds__(kThreads) void yuv420_packed422_clahe_interp_kernel
     }
 }
 
+// =============================================================================================
+// The same two stages on a LIST of frames, each at its own four addresses (mi_*_yuv420_to_packed422_frames_dev: a decoder's surface
+// pool in -- separately allocated, pitched Y, U and V (or UV) planes -- a playout or v4l2 buffer pool out).  The {y, c0, c1, out}
+// entries travel BY VALUE in the kernel arguments like Yuv420BgrList -- 64 x 32 B = 2 KiB -- and are read with scalar kernarg loads
+// indexed by the frame's grid coordinate.  The shape (pitches, width, height, copy_uv) is the launch's Yuv420P422Job, whose y / c0 / c1 /
+// out / *_frame a table launch ignores and whose vec says what the SHAPE allows (W % 16 == 0, the Y and output pitches multiples of 16,
+// under copy_uv the chroma pitch a multiple of 16 interleaved or 8 planar): whether frame f takes the 16 x 2 groups is then decided by
+// its own addresses -- per frame, so uniform for a workgroup.  Interleaved entries carry c1 = nullptr, MI_UV_FILL128 entries c0 = c1 =
+// nullptr (the host clears them): they are not dereferenced and decide nothing.
+// Both kernels are COPIES of the two above with the frame's addresses read from the table, so that those keep their ISA:
+// a change there is made here too.
+// =============================================================================================
+struct Yuv420P422Frame { const uint8_t* y; const uint8_t* c0; const uint8_t* c1; uint8_t* out; };
+struct Yuv420P422List { Yuv420P422Frame f[kFramesPerLaunch]; };
+static_assert(sizeof(Yuv420P422Frame) == 32, "four addresses an entry");
+
+// THE rule "does this frame of a list take the 16 x 2 groups": what the shape allows, the frame's own Y and output addresses
+// multiples of 16 and, under copy_uv only, its UV address a multiple of 16 (interleaved; c1 is not looked at) or its U and V addresses
+// multiples of 8 (planar).  The kernel decides by it and the host counts by it.
+__host__ __device__ __forceinline__ bool yuv420_packed422_frame_vec(int shape_vec, int copy_uv, bool planar, const void* y, const void* c0,
+                                                                    const void* c1, const void* out)
+{
+    const uintptr_t c = !copy_uv ? 0 : planar ? (((uintptr_t)c0 | (uintptr_t)c1) & 7) : ((uintptr_t)c0 & 15);
+    return shape_vec && ((((uintptr_t)y | (uintptr_t)out) & 15) | c) == 0;
+}
+
+// yuv420_to_packed422_kernel on a frame list: both loops are grid-stride, so one grid (sized by the shape alone) serves frames of
+// either walk
+template <int OFF, bool PLANAR, bool LUT>
+__global__ __launch_bounds__(kThreads) void yuv420_to_packed422_frames_kernel(Yuv420P422List l, Yuv420P422Job j, const uint8_t* __restrict__ luts)
+{
+    __shared__ uint32_t lut[LUT ? 256 * kCopies : 1];
+    const int t = threadIdx.x;
+    const int f = LUT ? (int)gridDim.y - 1 - (int)blockIdx.y : (int)blockIdx.y;      // frame order as yuv420_to_packed422_kernel
+    const uint32_t copy = t & (kCopies - 1);
+    if (LUT) {
+        const uint32_t v = luts[(size_t)f * 256 + t];
+#pragma unroll
+        for (int k = 0; k < kCopies; ++k) lut[(t << kCopyShift) + ((k + t) & (kCopies - 1))] = v;
+        __syncthreads();
+    }
+    const uint8_t* yp = l.f[f].y;
+    const uint8_t* c0p = l.f[f].c0;                            // not dereferenced unless copy_uv
+    const uint8_t* c1p = l.f[f].c1;
+    uint8_t* op = l.f[f].out;
+    if (yuv420_packed422_frame_vec(j.vec, j.copy_uv, PLANAR, yp, c0p, c1p, op)) {
+        const int gx_n = j.width >> 4;
+        const int groups = gx_n * (j.height >> 1);            // < 2^26 (W*H < 2^31)
+        const int stride = (int)gridDim.x * kThreads, dby = stride / gx_n, dgx = stride - dby * gx_n;
+        int gi = (int)blockIdx.x * kThreads + t;
+        int by = gi / gx_n, gx = gi - by * gx_n;
+        for (; gi < groups; gi += stride, by += dby, gx += dgx) {
+            if (gx >= gx_n) { gx -= gx_n; ++by; }
+            const uint8_t* y0p = yp + (long long)(2 * by) * j.y_step + (gx << 4);
+            u32x4 y0 = *reinterpret_cast<const u32x4*>(y0p);
+            u32x4 y1 = *reinterpret_cast<const u32x4*>(y0p + j.y_step);
+            u32x4 uv = {kChroma128, kChroma128, kChroma128, kChroma128};
+            if (j.copy_uv) {
+                const long long co = (long long)by * j.c_step;
+                uv = load_uv16<PLANAR>(c0p + co, c1p + co, gx << 4);
+            }
+            if (LUT) { y0 = lut_vec(lut, y0, copy); y1 = lut_vec(lut, y1, copy); }
+            uint8_t* d0 = op + (long long)(2 * by) * j.out_step + (gx << 5);
+            pack_store16<OFF>(d0, y0, uv);
+            pack_store16<OFF>(d0 + j.out_step, y1, uv);
+        }
+        return;
+    }
+    constexpr int kUShift = OFF ? 0 : 8, kVShift = kUShift + 16;
+    const int bx_n = j.width >> 1;
+    const long long blocks = (long long)bx_n * (j.height >> 1);
+    for (long long bi = (long long)blockIdx.x * kThreads + t; bi < blocks; bi += (long long)gridDim.x * kThreads) {
+        const int by = (int)(bi / bx_n), bx = (int)(bi - (long long)by * bx_n);
+        const uint8_t* r0 = yp + (long long)(2 * by) * j.y_step + 2 * bx;
+        const uint8_t* r1 = r0 + j.y_step;
+        uint8_t* d0 = op + (long long)(2 * by) * j.out_step + 4 * bx;
+        uint32_t Y00 = r0[0], Y01 = r0[1], Y10 = r1[0], Y11 = r1[1];
+        if (LUT) {
+            Y00 = lut[(Y00 << kCopyShift) + copy]; Y01 = lut[(Y01 << kCopyShift) + copy];
+            Y10 = lut[(Y10 << kCopyShift) + copy]; Y11 = lut[(Y11 << kCopyShift) + copy];
+        }
+        uint32_t U = 128, V = 128;
+        if (j.copy_uv) {
+            const long long co = (long long)by * j.c_step;
+            if (PLANAR) { U = c0p[co + bx]; V = c1p[co + bx]; }
+            else        { U = c0p[co + 2 * bx]; V = c0p[co + 2 * bx + 1]; }
+        }
+        const uint32_t cw = (U << kUShift) | (V << kVShift);
+        *reinterpret_cast<uint32_t*>(d0) = put_y<OFF>(Y00, Y01) | cw;
+        *reinterpret_cast<uint32_t*>(d0 + j.out_step) = put_y<OFF>(Y10, Y11) | cw;
+    }
+}
+
+// yuv420_packed422_clahe_interp_kernel on a frame list.  No byte path: the host takes this kernel only when every frame of the call
+// passes yuv420_packed422_frame_vec.
+template <int OFF, bool PLANAR>
+__global__ __launch_bounds__(kThreads) void yuv420_packed422_clahe_interp_frames_kernel(Yuv420P422List l, Yuv420P422Job j, ClaheGeom g,
+                                                                                       const uint8_t* __restrict__ luts, int subs, int groups)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t quad[];
+    f32x4* quadf = reinterpret_cast<f32x4*>(quad);
+    const int t = threadIdx.x, f = (int)gridDim.y - 1 - (int)blockIdx.y;      // last-to-first, see clahe_interp_kernel
+    const int band = blockIdx.x / subs, sub = blockIdx.x - band * subs;
+    const int ty1u = band - 1;
+    const int ty1 = max(ty1u, 0), ty2 = min(ty1u + 1, g.tiles_y - 1);
+    const uint8_t* lf = luts + (size_t)f * g.tiles_x * g.tiles_y * 256;
+    const uint8_t* l1 = lf + (size_t)ty1 * g.tiles_x * 256;
+    const uint8_t* l2 = lf + (size_t)ty2 * g.tiles_x * 256;
+    const int npairs = g.tiles_x + 1;
+    for (int i = t; i < npairs * 256; i += kThreads) {
+        const int pr = i >> 8, v = i & 255;
+        const int ta = max(pr - 1, 0), tb = min(pr, g.tiles_x - 1);
+        const f32x4 e = {(float)l1[ta * 256 + v], (float)l2[ta * 256 + v], (float)l1[tb * 256 + v], (float)l2[tb * 256 + v]};   // {a, c, b, d}
+        quadf[i] = e;
+    }
+    __syncthreads();
+    const int y_lo_band = (int)max(0LL, ((long long)(2 * band - 1) * g.tile_h) / 2 - kBandMargin);
+    const int y_hi_band = (int)min((long long)g.height, ((long long)(2 * band + 1) * g.tile_h + 1) / 2 + kBandMargin);
+    const int nrows = max(0, y_hi_band - y_lo_band);
+    const int y_lo = y_lo_band + (int)((long long)nrows * sub / subs);
+    const int y_hi = y_lo_band + (int)((long long)nrows * (sub + 1) / subs);
+    const int phases = kThreads / groups;
+    const int grp = t % groups, phase = t / groups;
+    const int x0 = (blockIdx.z * groups + grp) * kInterpPx;
+    if (phase >= phases || x0 >= g.width) return;
+    f32x2 xw[kInterpPx];
+    int poff[kInterpPx];
+#pragma unroll
+    for (int k = 0; k < kInterpPx; ++k) {
+        const float txf = tile_coord<false>(x0 + k, g.inv_tw);
+        const int tx1 = floor_f32_to_int(txf);
+        const float xa = __fsub_rn(txf, (float)tx1);
+        xw[k].x = __fsub_rn(1.0f, xa); xw[k].y = xa;
+        int pr = tx1 + 1;
+        pr = pr < 0 ? 0 : (pr > g.tiles_x ? g.tiles_x : pr);
+        poff[k] = pr << 8;
+    }
+    const uint8_t* yp = l.f[f].y + x0;
+    const uint8_t* c0p = l.f[f].c0;                            // not dereferenced unless copy_uv
+    const uint8_t* c1p = l.f[f].c1;
+    uint8_t* dst = l.f[f].out + (long long)x0 * 2;
+    auto ty1_of = [&](int y) { return floor_f32_to_int(tile_coord<false>(y, g.inv_th)); };
+    int ya_lo = y_lo, ya_hi = y_hi;
+    while (ya_lo < ya_hi && ty1_of(ya_lo) != ty1u) ++ya_lo;
+    while (ya_hi > ya_lo && ty1_of(ya_hi - 1) != ty1u) --ya_hi;
+    auto do_row = [&](int y, const u32x4& yq, const u32x4& uv) {
+        const float tyf = tile_coord<false>(y, g.inv_th);
+        const float ya = __fsub_rn(tyf, (float)ty1u), ya1 = __fsub_rn(1.0f, ya);
+        const u32x4 yo = clahe_vec16_f32<false>(quadf, yq, poff, xw, ya, ya1);       // the host takes the fallback for ClaheGeom::contract
+        pack_store16<OFF>(dst + (long long)y * j.out_step, yo, uv);
+    };
+    for (int y = ya_lo + ((phase - (ya_lo - y_lo) % phases) % phases + phases) % phases; y < ya_hi; y += phases) {
+        const u32x4 q = *reinterpret_cast<const u32x4*>(yp + (long long)y * j.y_step);
+        u32x4 uv = {kChroma128, kChroma128, kChroma128, kChroma128};
+        if (j.copy_uv) {
+            const long long co = (long long)(y >> 1) * j.c_step;
+            uv = load_uv16<PLANAR>(c0p + co, c1p + co, x0);
+        }
+        do_row(y, q, uv);
+    }
+}
+// yuv420_packed422_clahe_interp_frames_kernel(l, j, g, luts, subs, groups) is the longer list of the two; 256: the implicit arguments a
+// code object carries behind the explicit ones
+static_assert(sizeof(Yuv420P422List) == (size_t)kFramesPerLaunch * 32 && sizeof(Yuv420P422List) <= 2048, "the table is at most 2 KiB");
+static_assert(sizeof(Yuv420P422List) + sizeof(Yuv420P422Job) + sizeof(ClaheGeom) + 8 + sizeof(const uint8_t*) + 2 * sizeof(int) + 8 + 256 <= 4096,
+              "the table and the remaining arguments of either *_frames_kernel stay below HIP's 4 KiB of kernel arguments");
+static_assert(sizeof(Yuv420P422List) + sizeof(Yuv420P422Job) + sizeof(const uint8_t*) + 8 + 256 <= 4096,
+              "yuv420_to_packed422_frames_kernel's arguments");
+
 }  // namespace mi

@@ -62,5 +62,6 @@ using namespace mi;
 #include "host/bgr_packed422.inc.hpp"  // interleaved BGR / RGB in, packed 4:2:2 (YUY2 / UYVY) out: convert and count, then map the luma in place in the packed frame (renderer / model -> playout)
 #include "host/bgr_packed422_frames.inc.hpp"  // the same on a list of frames, each at its own two addresses (image pool -> playout / v4l2 output buffer pool)
 #include "host/yuv420_packed422.inc.hpp"  // NV12 or planar 4:2:0 (I420 / YV12) in, packed 4:2:2 (YUY2 / UYVY) out in the pass that maps the luma (decoder -> playout)
+#include "host/yuv420_packed422_frames.inc.hpp"  // the same on a list of frames, each at its own four addresses (decoder surface pool -> playout / v4l2 output buffer pool)
 #include "host/pipe.inc.hpp"
 #include "host/diff.inc.hpp"

@@ -72,6 +72,7 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_bgr_to_packed422_frames_dev", "mi_clahe_bgr_to_packed422_frames_dev",
     "mi_equalize_hist_yuv420_to_packed422_batch_dev", "mi_clahe_yuv420_to_packed422_batch_dev",
     "mi_equalize_hist_yuv420_to_packed422", "mi_clahe_yuv420_to_packed422",
+    "mi_equalize_hist_yuv420_to_packed422_frames_dev", "mi_clahe_yuv420_to_packed422_frames_dev",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -170,6 +171,18 @@ class Yuv420BgrFrameDev(C.Structure):
     """mi_yuv420_bgr_frame_dev: one frame of a mi_*_yuv420_to_bgr_frames_dev list, its three input plane addresses and its image address
     (device pointers).  c0 is always the U plane and c1 the V plane (a YV12 frame exchanges the two); an INTERLEAVED list has its UV
     plane in c0 and its c1 is ignored (None)."""
+    _fields_ = [("y", C.c_void_p), ("c0", C.c_void_p), ("c1", C.c_void_p), ("out", C.c_void_p)]
+
+    @classmethod
+    def of(cls, y, c0, c1, out):
+        """the same from torch CUDA tensors, raw device addresses or None"""
+        return cls(*(None if p is None else _dptr(p) for p in (y, c0, c1, out)))
+
+
+class Yuv420Packed422FrameDev(C.Structure):
+    """mi_yuv420_packed422_frame_dev: one frame of a mi_*_yuv420_to_packed422_frames_dev list, its three input plane addresses and its
+    packed frame's address (device pointers).  c0 is always the U plane and c1 the V plane (a YV12 frame exchanges the two); an
+    INTERLEAVED list has its UV plane in c0 and its c1 is ignored (None); with UV_FILL128 c0 and c1 are ignored (None)."""
     _fields_ = [("y", C.c_void_p), ("c0", C.c_void_p), ("c1", C.c_void_p), ("out", C.c_void_p)]
 
     @classmethod
@@ -333,6 +346,8 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_yuv420_to_packed422_batch_dev.argtypes = [vp, yp, vp, sz, sz, i, i, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_yuv420_to_packed422.argtypes = [vp, yp, vp, sz, i, i, i, i]
     L.mi_clahe_yuv420_to_packed422.argtypes = [vp, yp, vp, sz, i, i, i, i, d, i, i]
+    L.mi_equalize_hist_yuv420_to_packed422_frames_dev.argtypes = [vp, C.POINTER(Yuv420Packed422FrameDev), i, i, i, sz, sz, i, sz, i, i, vp]
+    L.mi_clahe_yuv420_to_packed422_frames_dev.argtypes = [vp, C.POINTER(Yuv420Packed422FrameDev), i, i, i, sz, sz, i, sz, i, i, d, i, i, vp]
     L.mi_analyze_diff_u8.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, i, vp]
     L.mi_analyze_diff_u8_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp, vp]
     L.mi_host_register.argtypes = [vp, sz]
@@ -1501,6 +1516,38 @@ class Context:
         self._chk(self._L.mi_clahe_yuv420_to_packed422_batch_dev(self._h, C.byref(src), _dptr(d_out), op, fo, int(width), int(height),
                                                                int(n_frames), int(fmt), int(uv_mode), float(clip_limit), int(tiles_x),
                                                                int(tiles_y), stream), "mi_clahe_yuv420_to_packed422_batch_dev")
+
+    @staticmethod
+    def _yuv420_packed422_list(frames):
+        """frames: a sequence of Yuv420Packed422FrameDev, or a ctypes array of them.  Returns the array and its length."""
+        if isinstance(frames, C.Array):
+            return frames, len(frames)
+        frames = list(frames)
+        arr = (Yuv420Packed422FrameDev * max(1, len(frames)))()
+        for k, f in enumerate(frames):
+            arr[k] = f
+        return arr, len(frames)
+
+    def equalize_hist_yuv420_to_packed422_frames_dev(self, frames, width, height, y_pitch, c_pitch, chroma, fmt=FMT_YUY2, uv_mode=UV_COPY,
+                                                     out_pitch=None, stream=0):
+        """mi_equalize_hist_yuv420_to_packed422_frames_dev.  frames: Yuv420Packed422FrameDev entries, one per frame, every plane and
+        every packed frame at its own device address (a decoder's surface pool in, a playout or v4l2 buffer pool out); one shape, one
+        set of pitches, one chroma layout, one format and one uv_mode for the call.  The tight frame is the default: out_pitch 2*W."""
+        arr, n = self._yuv420_packed422_list(frames)
+        op = 2 * int(width) if out_pitch is None else int(out_pitch)
+        self._chk(self._L.mi_equalize_hist_yuv420_to_packed422_frames_dev(self._h, arr, n, int(width), int(height), int(y_pitch),
+                                                                        int(c_pitch), int(chroma), op, int(fmt), int(uv_mode), stream),
+                  "mi_equalize_hist_yuv420_to_packed422_frames_dev")
+
+    def clahe_yuv420_to_packed422_frames_dev(self, frames, width, height, y_pitch, c_pitch, chroma, fmt=FMT_YUY2, uv_mode=UV_COPY,
+                                             clip_limit=2.0, tiles_x=8, tiles_y=8, out_pitch=None, stream=0):
+        """mi_clahe_yuv420_to_packed422_frames_dev; arguments as equalize_hist_yuv420_to_packed422_frames_dev, plus the CLAHE
+        parameters."""
+        arr, n = self._yuv420_packed422_list(frames)
+        op = 2 * int(width) if out_pitch is None else int(out_pitch)
+        self._chk(self._L.mi_clahe_yuv420_to_packed422_frames_dev(self._h, arr, n, int(width), int(height), int(y_pitch), int(c_pitch),
+                                                                int(chroma), op, int(fmt), int(uv_mode), float(clip_limit), int(tiles_x),
+                                                                int(tiles_y), stream), "mi_clahe_yuv420_to_packed422_frames_dev")
 
     def _yuv420_packed422_host(self, frame, width, height, src_fmt, out, name):
         if isinstance(frame, Yuv420Planes):                 # host addresses and pitches of the caller's own planes

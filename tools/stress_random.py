@@ -10,7 +10,9 @@ and BGR / RGB in, packed 4:2:2 out (every row with the chroma of its own left pi
 included, against the oracle on the row-doubled image (tests/bgr_packed422_ref.py), as a batch and as a frame list (every image and every
 frame an allocation of its own at an offset of its own: 16-pixel groups and macropixels in one launch), and 4:2:0 in (NV12 / I420 / YV12),
 packed 4:2:2 out (mi_*_yuv420_to_packed422_batch_dev: every chroma row under two output rows) at random pitched layouts on both sides
-of its vector and one-pass conditions, against the oracle's luma and the input's own chroma.
+of its vector and one-pass conditions, against the oracle's luma and the input's own chroma, and the same on a frame list
+(mi_*_yuv420_to_packed422_frames_dev: every plane and every packed frame an allocation of its own at a skew of its own, both layouts, both
+formats, both UV modes, 16 x 2 groups and 2 x 2 blocks in one launch, the four list counters asserted).
     python tools/stress_random.py [seconds] [seed] [option=value ...]        prints a line every ~15 s, exits non-zero on the first mismatch"""
 import sys, time
 sys.path.insert(0, "opencv-opencl_amd/python"); sys.path.insert(0, ".")
@@ -22,12 +24,12 @@ rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 ctx = mi_lumaeq.Context(0)
 for kv in sys.argv[3:]:                                          # name=value options for the whole run, e.g. clahe16_wide=2 (mid kernel always launched)
     k_, v_ = kv.split("="); ctx.set_option(k_, int(v_)); print("option", k_, "=", v_, flush=True)
-t0 = last = time.time(); n = {"roi": 0, "grid": 0, "small": 0, "c16": 0, "420": 0, "nv12": 0, "nv12bgr": 0, "yuv420bgr": 0, "yuv420bgrlist": 0, "bgryuv420list": 0, "p422bgrlist": 0, "bgrp422": 0, "bgrp422list": 0, "yuv420p422": 0}
+t0 = last = time.time(); n = {"roi": 0, "grid": 0, "small": 0, "c16": 0, "420": 0, "nv12": 0, "nv12bgr": 0, "yuv420bgr": 0, "yuv420bgrlist": 0, "bgryuv420list": 0, "p422bgrlist": 0, "bgrp422": 0, "bgrp422list": 0, "yuv420p422": 0, "yuv420p422list": 0}
 def dev(a): return xfer.to_device(np.ascontiguousarray(a))
 def fail(what, *info):
     print("MISMATCH", what, info, flush=True); sys.exit(1)
 while time.time() - t0 < budget:
-    k = int(rng.integers(0, 11))
+    k = int(rng.integers(0, 12))
     if k == 0:      # ROI batch on the device: random pitches, origins, sizes
         w, h, nf = int(rng.integers(1, 700)), int(rng.integers(1, 90)), int(rng.integers(1, 6))
         sp = w + int(rng.integers(0, 40)); sp += (16 - sp % 16) % 16 if rng.integers(0, 2) else 0
@@ -334,6 +336,57 @@ while time.time() - t0 < budget:
         if not np.array_equal(out, want): fail("yuv420p422", w, h, nf, op, sfmt, fmt, uvm, clip, tx, ty, terms, cterms, np.flatnonzero(out != want)[:8])
         if not np.array_equal(xfer.to_host(d_in), img): fail("yuv420p422 wrote its input", w, h, nf, op)
         n["yuv420p422"] += 1
+    elif k == 11:   # the same on a frame list: every plane and every frame its own allocation at its own skew; each frame on the groups or the blocks by its own addresses
+        w, h, nf = int(rng.integers(1, 40)) * (16 if rng.integers(0, 2) else 2), int(rng.integers(1, 40)) * 2, int(rng.integers(1, 7))
+        op, sfmt, fmt, uvm = int(rng.integers(0, 2)), str(rng.choice(["nv12", "i420"])), int(rng.integers(2, 4)), int(rng.integers(0, 2))      # a pool has no YV12 of its own: c0 is U
+        tx, ty = int(rng.choice([1, 2, 4, 8, 3, 16])), int(rng.integers(1, 6)); clip = float(rng.choice([0.0, 1.0, 2.0, 40.0]))
+        planar = sfmt != "nv12"; cw = w // 2 if planar else w; cm = 8 if planar else 16
+        al = 16 if rng.integers(0, 4) else 1; cal = (8 if planar and al == 16 and rng.integers(0, 2) else al); oal = max(al, 4)
+        def pad(v, a): return (v + a - 1) // a * a + a * int(rng.integers(0, 40 // a + 1))
+        ypi, cpi, opi = pad(w, al), pad(cw, cal), pad(2 * w, oal)
+        def skew(m): return m * int(rng.integers(0, 4)) if rng.integers(0, 4) else int(rng.integers(0, 32))      # a multiple of the rule's, three times in four
+        yoff, uoff, voff = [skew(16) for _ in range(nf)], [skew(cm) for _ in range(nf)], [skew(cm) for _ in range(nf)]
+        ooff = [16 * int(rng.integers(0, 4)) if rng.integers(0, 4) else 4 * int(rng.integers(0, 8)) for _ in range(nf)]   # multiples of 4
+        Y = rng.integers(0, int(rng.integers(2, 257)), (nf, h, w), dtype=np.uint8); U, V = (rng.integers(0, 256, (nf, h // 2, w // 2), dtype=np.uint8) for _ in range(2))
+        def plane(off, pitch, rows, data):
+            a = np.full(off + pitch * rows + 32, 0x5A, np.uint8); a[off: off + pitch * rows].reshape(rows, pitch)[:, : data.shape[1]] = data; return a
+        def uvrow(f):
+            r = np.empty((h // 2, w), np.uint8); r[:, 0::2] = U[f]; r[:, 1::2] = V[f]; return r
+        hy = [plane(yoff[f], ypi, h, Y[f]) for f in range(nf)]
+        hu = [plane(uoff[f], cpi, h // 2, U[f] if planar else uvrow(f)) for f in range(nf)]
+        hv = [plane(voff[f], cpi, h // 2, V[f]) for f in range(nf)] if planar else []
+        dy, du, dv = [dev(a) for a in hy], [dev(a) for a in hu], [dev(a) for a in hv]
+        d_outs = [torch.full((ooff[f] + opi * h + 32,), 0x5A, dtype=torch.uint8, device="cuda") for f in range(nf)]
+        perm = [int(v) for v in rng.permutation(nf)]                     # the list order is not the allocation order
+        junk = uvm == 0 and bool(rng.integers(0, 2))                     # MI_UV_FILL128: null chroma addresses, or the real ones (ignored either way)
+        ents = [mi_lumaeq.Yuv420Packed422FrameDev(dy[f].data_ptr() + yoff[f], None if junk else du[f].data_ptr() + uoff[f],
+                                                  None if junk or not planar else dv[f].data_ptr() + voff[f], d_outs[f].data_ptr() + ooff[f]) for f in perm]
+        shape = w % 16 == 0 and ypi % 16 == 0 and opi % 16 == 0 and (not uvm or cpi % cm == 0)
+        def cok(f): return not uvm or (uoff[f] % cm == 0 and (not planar or voff[f] % cm == 0))
+        one = op == 0 or (shape and w % tx == 0 and h % ty == 0 and (w // tx) % 16 == 0 and tx + 1 <= 15 and all(yoff[f] % 16 == 0 and ooff[f] % 16 == 0 and cok(f) for f in range(nf)))
+        nvec = sum(1 for f in range(nf) if shape and (yoff[f] % 16 == 0 or not one) and ooff[f] % 16 == 0 and cok(f))      # two-pass: the luma comes from aligned scratch
+        names = ("yuv420_packed422_onepass", "yuv420_packed422_twopass", "yuv420_packed422_list_frames_vec", "yuv420_packed422_list_frames_bytes",
+                 "yuv420_packed422_vec", "yuv420_packed422_bytes"); st0 = [ctx.get_stat(s) for s in names]
+        a = (ents, w, h, ypi, cpi if not junk else 0, mi_lumaeq.CHROMA_PLANAR if planar else mi_lumaeq.CHROMA_INTERLEAVED, fmt, uvm)
+        try:
+            if op == 0: ctx.equalize_hist_yuv420_to_packed422_frames_dev(*a, out_pitch=opi)
+            else: ctx.clahe_yuv420_to_packed422_frames_dev(*a, clip, tx, ty, out_pitch=opi)
+        except mi_lumaeq.MiError as e:
+            if e.status != 2: fail("yuv420_to_packed422_frames status", w, h, nf, op, tx, ty, e.status)
+            continue                                                   # a tile grid the planar forms refuse
+        ctx.synchronize()
+        if [ctx.get_stat(s) - v for s, v in zip(names, st0)] != [int(one), int(not one), nvec, nf - nvec, 0, 0]:
+            fail("yuv420_to_packed422_frames counters", w, h, nf, op, sfmt, uvm, tx, ty, ypi, cpi, opi, yoff, uoff, voff, ooff, one, nvec)
+        for f in range(nf):
+            fr = np.empty((h, 2 * w), np.uint8); fr[:, fmt - 2::2] = oracle.equalize_hist(Y[f]) if op == 0 else oracle.clahe(Y[f], clip, tx, ty)
+            fr[:, 3 - fmt::2] = np.repeat(uvrow(f), 2, axis=0) if uvm == 1 else 128          # chroma row r under output rows 2r and 2r + 1
+            want = np.full(d_outs[f].numel(), 0x5A, np.uint8); want[ooff[f]: ooff[f] + opi * h].reshape(h, opi)[:, : 2 * w] = fr
+            got = xfer.to_host(d_outs[f])
+            if not np.array_equal(got, want):
+                fail("yuv420_to_packed422_frames", w, h, nf, op, sfmt, fmt, uvm, clip, tx, ty, ypi, cpi, opi, yoff, uoff, voff, ooff, perm, f, np.flatnonzero(got != want)[:8])
+            if not np.array_equal(xfer.to_host(dy[f]), hy[f]) or not np.array_equal(xfer.to_host(du[f]), hu[f]) or (planar and not np.array_equal(xfer.to_host(dv[f]), hv[f])):
+                fail("yuv420_to_packed422_frames wrote its input", w, h, nf, op, f)
+        n["yuv420p422list"] += 1
     else:           # 4:2:0 codes
         w, h = int(rng.integers(1, 60)) * (16 if rng.integers(0, 2) else 2), int(rng.integers(1, 40)) * 2
         bgr = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)

@@ -16,7 +16,19 @@ No bar: (a) moves fewer bytes than (b) in fewer launches, so (a) is expected ahe
 spread is reported as a finding.  After the timed legs each row runs 30 profiled calls of (a), (ai), the library call of (b) and (c) and
 records every kernel's launches per call and p50 time, and the bytes per second of the new pixel-writing kernel (3.5 B/px: 1.5 read,
 2 written) from the same run.
-    python tools/yuv420_to_packed422_ab.py [--out DIR] [--calls N]   -> DIR/r29_yuv420_to_packed422_ab.json and .md (default DIR: profiles)"""
+    python tools/yuv420_to_packed422_ab.py [--out DIR] [--calls N]   -> DIR/r29_yuv420_to_packed422_ab.json and .md (default DIR: profiles)
+
+--list: the frame-list form (mi_*_yuv420_to_packed422_frames_dev) against the batch form, again in ONE process with the legs interleaved:
+    (b)  mi_*_yuv420_to_packed422_batch_dev on a tight batch: the yardstick of this run, never an earlier figure
+    (l)  the list form on the batch's own addresses (entry f = the batch's frame f: same memory, same pitches)
+    (lp) the list form on a POOL: every Y, U, V (or UV) plane and every packed frame its own allocation, pitches align(row, 256)
+    (p)  what a pool caller has without the list form: one n_frames = 1 batch call per frame of that pool
+    (b2) leg (b) a second time in the same rotation: |b / b2 - 1| is the run-to-run spread of this very run
+64 x 3840x2160 and 256 x 1920x1080 (the list form runs one resp. four 64-frame launch sequences against the batch form's one); NV12 and
+I420; YUY2; MI_UV_COPY; equalizeHist and CLAHE 8x8 clip 2.0.  (l), (lp) and (p) are checked byte for byte against (b) before anything is
+timed.  No bar.  A row at 64 x 4K in which (l) is behind (b) by more than the spread is reported as a finding; per-kernel p50 times of
+(b), (l) and (lp) from 30 profiled calls each are recorded next to every row to explain one.
+    python tools/yuv420_to_packed422_ab.py --list [--out DIR] [--calls N]   -> DIR/r30_yuv420_to_packed422_frames_ab.json and .md"""
 import argparse
 import json
 import sys
@@ -28,7 +40,7 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT / "opencv-opencl_amd" / "python"))
 sys.path.insert(0, str(ROOT))
 import mi_lumaeq  # noqa: E402
-from mi_lumaeq import UV_COPY, FMT_YUY2, FMT_UYVY, Yuv420Planes  # noqa: E402
+from mi_lumaeq import UV_COPY, FMT_YUY2, FMT_UYVY, CHROMA_INTERLEAVED, CHROMA_PLANAR, Yuv420Planes, Yuv420Packed422FrameDev  # noqa: E402
 
 CASES = [(3840, 2160, 64), (1920, 1080, 256)]
 FMTS = (("YUY2", FMT_YUY2), ("UYVY", FMT_UYVY))
@@ -45,13 +57,194 @@ def pct(v, q):
     return v[min(len(v) - 1, int(q * (len(v) - 1) + 0.5))]
 
 
+LIST_LEGS = ("b_batch", "l_list_same_addresses", "lp_list_pool", "p_batch_call_per_frame", "b2_batch_again")
+LIST_STATS = ("yuv420_packed422_onepass", "yuv420_packed422_twopass", "yuv420_packed422_list_frames_vec", "yuv420_packed422_list_frames_bytes")
+
+
+def align256(v):
+    return (v + 255) & ~255
+
+
+def main_list(args):
+    ctx = mi_lumaeq.Context(0)
+    stream = torch.cuda.current_stream()
+    s = stream.cuda_stream
+    fmt = FMT_YUY2
+    rows = []
+    for w, h, n in CASES:
+        ysz = w * h
+        for layout in ("nv12", "i420"):
+            planar = layout == "i420"
+            chroma = CHROMA_PLANAR if planar else CHROMA_INTERLEAVED
+            crow, cplanes = (w // 2, 2) if planar else (w, 1)
+            yp, cp, op = align256(w), align256(crow), align256(2 * w)
+            mk = Yuv420Planes.i420 if planar else Yuv420Planes.nv12
+            batch, b_planes, b_entries, pools, p_entries, p_planes = [], [], [], [], [], []
+            out_b = torch.empty((n, h, 2 * w), dtype=torch.uint8, device="cuda:0")
+            out_l = torch.empty_like(out_b)
+            out_p = [torch.empty((h, op), dtype=torch.uint8, device="cuda:0") for _ in range(n)]      # the pool's buffers, each its own
+            for k in range(2):
+                g = torch.Generator(device="cuda:0")
+                g.manual_seed(0x5EED3000 + w + k)
+                x = torch.randint(0, 256, (n, ysz * 3 // 2), dtype=torch.uint8, device="cuda:0", generator=g)
+                x[:, :ysz].copy_(x[:, :ysz] // 4 + 64 + 16 * k)  # low contrast: 64 populated luma bins; the chroma stays full range
+                batch.append(x)
+                d = mk(x, w, h)
+                b_planes.append(d)
+                fs = d.frame_stride
+                arr = (Yuv420Packed422FrameDev * n)()
+                for f in range(n):
+                    arr[f] = Yuv420Packed422FrameDev(d.y + f * fs, d.c0 + f * fs, d.c1 + f * fs if planar else None, out_l[f].data_ptr())
+                b_entries.append(arr)
+                # the pool: the same samples, every plane its own pitched allocation
+                ys = [torch.empty((h, yp), dtype=torch.uint8, device="cuda:0") for _ in range(n)]
+                cs = [[torch.empty((h // 2, cp), dtype=torch.uint8, device="cuda:0") for _ in range(n)] for _ in range(cplanes)]
+                for f in range(n):
+                    ys[f][:, :w].copy_(x[f, :ysz].view(h, w))
+                    for q in range(cplanes):
+                        lo = ysz + q * (ysz // 4)
+                        cs[q][f][:, :crow].copy_(x[f, lo: lo + (h // 2) * crow].view(h // 2, crow))
+                pools.append((ys, cs))
+                arr = (Yuv420Packed422FrameDev * n)()
+                one = []
+                for f in range(n):
+                    c0, c1 = cs[0][f].data_ptr(), cs[1][f].data_ptr() if planar else None
+                    arr[f] = Yuv420Packed422FrameDev(ys[f].data_ptr(), c0, c1, out_p[f].data_ptr())
+                    one.append(Yuv420Planes(ys[f].data_ptr(), yp, c0, c1, cp, 0, chroma))
+                p_entries.append(arr)
+                p_planes.append(one)
+            for opname in OPS:
+                eq = opname == "equalize"
+
+                def batch_call(planes, out, nf, **kw):
+                    if eq:
+                        ctx.equalize_hist_yuv420_to_packed422_batch_dev(planes, out, w, h, nf, fmt, UV_COPY, stream=s, **kw)
+                    else:
+                        ctx.clahe_yuv420_to_packed422_batch_dev(planes, out, w, h, nf, fmt, UV_COPY, *CLAHE, stream=s, **kw)
+
+                def list_call(entries, y_pitch, c_pitch, out_pitch):
+                    if eq:
+                        ctx.equalize_hist_yuv420_to_packed422_frames_dev(entries, w, h, y_pitch, c_pitch, chroma, fmt, UV_COPY,
+                                                                         out_pitch=out_pitch, stream=s)
+                    else:
+                        ctx.clahe_yuv420_to_packed422_frames_dev(entries, w, h, y_pitch, c_pitch, chroma, fmt, UV_COPY, *CLAHE,
+                                                                 out_pitch=out_pitch, stream=s)
+
+                def leg_b(k):
+                    batch_call(b_planes[k], out_b, n)
+
+                def leg_l(k):
+                    list_call(b_entries[k], w, crow, 2 * w)
+
+                def leg_lp(k):
+                    list_call(p_entries[k], yp, cp, op)
+
+                def leg_p(k):
+                    for f in range(n):
+                        batch_call(p_planes[k][f], out_p[f], 1, out_pitch=op, out_frame=op * h)
+
+                legs = {"b_batch": leg_b, "l_list_same_addresses": leg_l, "lp_list_pool": leg_lp, "p_batch_call_per_frame": leg_p,
+                        "b2_batch_again": leg_b}
+                names = list(LIST_LEGS)
+                # bytes against the batch form before anything is timed
+                leg_b(0)
+                before = [ctx.get_stat(k) for k in LIST_STATS]
+                leg_l(0)
+                leg_lp(0)
+                torch.cuda.synchronize()
+                assert [ctx.get_stat(k) - v for k, v in zip(LIST_STATS, before)] == [2, 0, 2 * n, 0], "the list form left the one-pass 16 x 2 groups"
+                assert torch.equal(out_l, out_b), ("(l) and (b) differ", w, layout, opname)
+                assert int(out_b.max()) > 0, "(b) wrote nothing"
+                for f in range(n):
+                    assert torch.equal(out_p[f][:, : 2 * w], out_b[f]), ("(lp) and (b) differ", w, layout, opname, f)
+                    out_p[f].zero_()
+                leg_p(0)
+                torch.cuda.synchronize()
+                for f in range(n):
+                    assert torch.equal(out_p[f][:, : 2 * w], out_b[f]), ("(p) and (b) differ", w, layout, opname, f)
+                times = {k: [] for k in names}
+                for it in range(args.warmup + args.calls):
+                    order = names[it % len(names):] + names[: it % len(names)]
+                    for name in order:
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record(stream)
+                        legs[name](it & 1)
+                        e1.record(stream)
+                        if it >= args.warmup:
+                            times[name].append((e0, e1))
+                    if it % 20 == 19:
+                        torch.cuda.synchronize()
+                torch.cuda.synchronize()
+                res = {"width": w, "height": h, "frames_per_call": n, "layout": layout, "format": "YUY2", "op": opname, "uv_mode": "COPY",
+                       "calls": args.calls, "pool_pitches": [yp, cp, op]}
+                for name, ev in times.items():
+                    ms = [a.elapsed_time(b) for a, b in ev]
+                    res[name] = {"median_us": pct(ms, 0.5) * 1e3, "p10_us": pct(ms, 0.1) * 1e3, "p90_us": pct(ms, 0.9) * 1e3,
+                                 "frames_per_s": n / (pct(ms, 0.5) * 1e-3)}
+                med = {k: res[k]["median_us"] for k in names}
+                res["spread"] = abs(med["b_batch"] / med["b2_batch_again"] - 1.0)
+                res["l_rate_over_b_rate"] = med["b_batch"] / med["l_list_same_addresses"]
+                res["lp_rate_over_b_rate"] = med["b_batch"] / med["lp_list_pool"]
+                res["lp_rate_over_p_rate"] = med["p_batch_call_per_frame"] / med["lp_list_pool"]
+                ctx.set_profiling(1)
+                kern = {}
+                for tag, fn in (("b_batch", leg_b), ("l_list_same_addresses", leg_l), ("lp_list_pool", leg_lp)):
+                    ctx.profile_read(reset=True)
+                    for it in range(30):
+                        fn(it & 1)
+                    torch.cuda.synchronize()
+                    kern[tag] = {k: {"launches_per_call": v["launches"] / 30, "p50_us": v["p50_ms"] * 1e3}
+                                 for k, v in ctx.profile_read(reset=True).items() if v["launches"]}
+                ctx.set_profiling(0)
+                res["kernels"] = kern
+                rows.append(res)
+                print(json.dumps(res), flush=True)
+            del batch, b_planes, b_entries, pools, p_entries, p_planes, out_b, out_l, out_p
+            torch.cuda.empty_cache()
+    meta = {"device": torch.cuda.get_device_name(0), "library": mi_lumaeq.version(), "clahe": {"clip": CLAHE[0], "tiles": list(CLAHE[1:])},
+            "uv_mode": "COPY", "format": "YUY2", "warmup": args.warmup, "bar": None}
+    ctx.close()
+    outdir = Path(args.out)
+    outdir.mkdir(parents=True, exist_ok=True)
+    (outdir / "r30_yuv420_to_packed422_frames_ab.json").write_text(json.dumps({"meta": meta, "rows": rows}, indent=1) + "\n")
+    md = ["# 4:2:0 in, packed 4:2:2 out on lists of device frames: the list form against the batch form", "",
+          f"{meta['device']}, {meta['library']}; {args.warmup} warm-up and {args.calls} timed calls per leg, legs interleaved in one process, "
+          "medians of per-call HIP event times; YUY2; CLAHE 8x8 clip 2.0; MI_UV_COPY.  Rates are frames per second.  (b): "
+          "mi_*_yuv420_to_packed422_batch_dev on a tight batch, the yardstick of the same run.  (l): mi_*_yuv420_to_packed422_frames_dev on "
+          "the batch's own addresses.  (lp): the list form on a pool of separately allocated planes and buffers at pitches "
+          "align(row, 256).  (p): one n_frames = 1 batch call per frame of that pool.  (l), (lp) and (p) are byte-equal to (b), checked "
+          "before timing.  Spread: the two (b) legs of the same rotation against each other.  The list form runs one 64-frame launch "
+          "sequence at 64 frames and four at 256, against the batch form's one.", "",
+          "| frames | layout | op | (b) batch | (l) list, same addresses | (lp) list, pool | (p) batch call per frame | l / b | lp / b | lp / p | spread |",
+          "|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        md.append(f"| {r['frames_per_call']} x {r['width']}x{r['height']} | {r['layout']} | {r['op']} | " +
+                  " | ".join(f"{r[k]['frames_per_s']:.0f} ({r[k]['median_us']:.0f} us)" for k in LIST_LEGS[:4]) +
+                  f" | {r['l_rate_over_b_rate']:.3f} | {r['lp_rate_over_b_rate']:.3f} | {r['lp_rate_over_p_rate']:.2f} | {r['spread']:.3f} |")
+    md += ["", "| frames | layout | op | leg | kernels: launches per call x p50 us |", "|---|---|---|---|---|"]
+    for r in rows:
+        for tag, kk in r["kernels"].items():
+            md.append(f"| {r['frames_per_call']} x {r['width']}x{r['height']} | {r['layout']} | {r['op']} | {tag} | " +
+                      ", ".join(f"{k} {v['launches_per_call']:g} x {v['p50_us']:.0f}" for k, v in kk.items()) + " |")
+    slow = [(r["layout"], r["op"], round(r["l_rate_over_b_rate"], 3), round(r["spread"], 3)) for r in rows
+            if r["frames_per_call"] == 64 and r["l_rate_over_b_rate"] < 1.0 - r["spread"]]
+    md += ["", "Rows at 64 x 4K in which the list form on the batch's own addresses is behind the batch form by more than the spread "
+           "(layout, op, l / b, spread): " + (str(slow) if slow else "none") + "."]
+    (outdir / "r30_yuv420_to_packed422_frames_ab.md").write_text("\n".join(md) + "\n")
+    if slow:
+        print("FINDING: the list form is behind the batch form on the same addresses in", slow)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=str(ROOT / "profiles"))
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--list", action="store_true", help="the frame-list form against the batch form (r30)")
     args = ap.parse_args()
     assert args.calls >= 200 and args.warmup >= 20, "the method wants >= 20 warm-up and >= 200 timed calls"
+    if args.list:
+        return main_list(args)
     ctx = mi_lumaeq.Context(0)
     stream = torch.cuda.current_stream()
     s = stream.cuda_stream
