@@ -1282,6 +1282,120 @@ mi_status mi_equalize_hist_yuv420_to_packed422_frames_dev(mi_ctx* ctx, const mi_
 mi_status mi_clahe_yuv420_to_packed422_frames_dev(mi_ctx* ctx, const mi_yuv420_packed422_frame_dev* frames, int n_frames,
         int width, int height, size_t y_pitch, size_t c_pitch, int chroma, size_t out_pitch, int format, mi_uv_mode uv_mode,
         double clip_limit, int tiles_x, int tiles_y, void* stream);
+/* mi_*_bgra_to_yuv420*: interleaved 8-bit FOUR-channel images (CV_8UC4: BGRA / BGRX, or RGBA / RGBX) in, 4:2:0 frames described by
+ * mi_yuv420_planes out with the luma equalized -- what render targets, swap-chain images, screen and window capture, compositor
+ * surfaces, browser canvases and GL / Vulkan / D3D interop buffers hold -> hardware encoder (NV12) or software encoder (I420 / YV12:
+ * data[0..2] / linesize[0..2]) in one pass over the 4 B/px surface, without a slice-and-copy to three channels outside the library.
+ * Per frame the bytes are what OpenCV 4.4 gives for
+ *     cv::cvtColor(bgra, i420, cv::COLOR_BGRA2YUV_I420);                                         (COLOR_RGBA2YUV_I420 for MI_ORDER_RGB)
+ *     cv::Mat y = i420(Rect(0, 0, W, H));  cv::equalizeHist(y, y)  /  clahe->apply(y, y);        (Y only)
+ * with the U plane going to out->c0 and the V plane to out->c1 (MI_UV_COPY) or every chroma byte 128 (MI_UV_FILL128).  Chroma comes
+ * from the top-left pixel of each 2 x 2 block, without averaging.  The fourth byte X (alpha or padding) takes no part in any output
+ * byte: the output is byte for byte what mi_*_bgr_to_yuv420* of the same kind writes for the image with X removed, at the same output
+ * layout.  c0 is always U and c1 always V: a YV12 caller passes the address of its second chroma plane as c0.  The same
+ * clahe_fp_contract option, the same REFLECT_101 padding when the tile grid does not divide the frame and the same limits on sizes and
+ * tile grids as the planar forms, with the same statuses.
+ *   input  : frame f at d_in + f * in_frame_stride, H rows of 4*W bytes at in_pitch >= 4*W: B, G, R, X per pixel (MI_ORDER_BGR) or
+ *            R, G, B, X (MI_ORDER_RGB).  The input is never written.
+ *   output : `out` is read only during the call.  Frame f has every plane at its pointer + f * out->frame_stride: Y, H rows of W bytes
+ *            at y_pitch >= W; PLANAR: c0 = U and c1 = V, each H/2 rows of W/2 bytes at c_pitch >= W/2; INTERLEAVED: c0 = the UV plane,
+ *            H/2 rows of W bytes at c_pitch >= W, c1 ignored.  Only the W bytes (Y, interleaved UV) or W/2 bytes (planar U, V) of each
+ *            output row are written: not the pitch padding, not the gaps between the planes, not the gaps between frames.
+ * Both chroma layouts are this form's own kernels: unlike mi_*_bgr_to_yuv420*, an MI_CHROMA_INTERLEAVED output is not handed to another
+ *   form, and the counters below count both layouts.
+ * Alignment: none is required of any pointer, pitch or stride.  A call moves 16 x 2 pixel groups per lane when W % 16 == 0; d_in,
+ *   in_pitch, in_frame_stride, out->y, out->y_pitch and out->frame_stride are multiples of 16; and the chroma terms are multiples of 16
+ *   for interleaved chroma (out->c0 and out->c_pitch: one 16-byte UV store) and of 8 for planar chroma (out->c0, out->c1 and
+ *   out->c_pitch: one 8-byte U store and one 8-byte V store).  A lane then makes eight 16-byte loads (every dword one pixel) and two
+ *   16-byte Y stores.  Otherwise the call processes 2 x 2 pixel blocks with byte accesses -- slower, the same bytes out.
+ * Two stages per chunk of 256 frames, as in mi_*_bgr_to_yuv420*.  Y is not in the input, so stage 1 converts: ONE kernel (charged to
+ *   MI_K_COLOR) reads the image once, writes Y and the chroma into the caller's planes and, for equalizeHist, counts the luma bytes it
+ *   has just produced.  Stage 2 maps the luma IN PLACE in out->y with the planar kernels: equalizeHist one MI_K_EQ_LUT and one
+ *   MI_K_LUT_APPLY launch (no MI_K_HIST launch; never the fused equalizeHist kernel nor the single-launch histogram + LUT kernel, option
+ *   two_kernel_max_frames does not apply); CLAHE exactly what mi_clahe_u8_batch_dev launches for that plane in place.  Bytes moved per
+ *   pixel: equalizeHist 4 + 1.5 + 1 + 1 = 7.5, CLAHE 5.5 + 3 = 8.5.  Between the stages out->y holds the unequalized luma.
+ * Counters (mi_ctx_get_stat): "bgra_yuv420_vec" / "bgra_yuv420_bytes", one count per call by the walk the conversion kernel took
+ *   (16 x 2 groups / 2 x 2 blocks).  A device or host call with work to do moves exactly one of them; a call that returns an error or
+ *   has a zero size moves neither.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of the
+ *   same shape as the other batched device forms.
+ * mi_equalize_hist_bgra_to_yuv420 / mi_clahe_bgra_to_yuv420: ONE CV_8UC4 image in host memory at in_step >= 4*W, at any address, in;
+ *   `out` holds HOST pointers at any address and pitch (frame_stride is ignored).  Synchronous; the image is staged in like
+ *   mi_*_bgr_to_yuv420's, with a row of 4*W bytes, and the planes come back like mi_*_yuv420's (planes in pinned memory that are tight
+ *   are DMA'd as they are, everything else goes through the context's pinned staging).  On the device the frame is tight with every
+ *   plane at a 16-byte aligned offset, so a W % 16 == 0 frame takes the 16 x 2 groups.  Whatever the call returns, no copy on the
+ *   caller's memory is in flight any more when it returns.  W*H > 0x7fffffff / 4: MI_ERR_UNSUPPORTED.
+ * Errors, MI_ERR_BAD_ARG: a null ctx, d_in or `out`; a null out->y or out->c0; a null out->c1 on a PLANAR output; a `chroma` other than
+ *   the two values; an `order` other than the two; a bad uv_mode; a negative size; an odd width or an odd height (refused even when
+ *   another size is 0, as in the sibling forms); in_pitch < 4*W; y_pitch < W; a c_pitch below its row (W interleaved, W/2 planar);
+ *   tiles <= 0; two output plane pointers of the call that are equal; an output plane pointer equal to d_in (there is no in-place
+ *   form).  Any other overlap: undefined, not checked; U and V rows side by side in one pitched plane (c1 = c0 + W/2, c_pitch = W) are
+ *   legal, as in mi_*_yuv420*.  width, height or n_frames of 0: MI_OK, nothing written (pointers and pitches are not looked at then).
+ *   Sizes and tile grids the planar forms refuse: the status they give (MI_ERR_UNSUPPORTED), nothing written.  Nothing is enqueued
+ *   unless every check passes.
+ * Not built: 4:2:0 or packed 4:2:2 in, BGRA out; BGRA in, packed 4:2:2 out; a four-channel mi_bgr_luma_op; a mi_pipe format. */
+mi_status mi_equalize_hist_bgra_to_yuv420_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        const mi_yuv420_planes* out, int width, int height, int n_frames, int order, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_bgra_to_yuv420_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        const mi_yuv420_planes* out, int width, int height, int n_frames, int order, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
+mi_status mi_equalize_hist_bgra_to_yuv420(mi_ctx* ctx, const uint8_t* in, size_t in_step, const mi_yuv420_planes* out,
+        int width, int height, int order, mi_uv_mode uv_mode);
+mi_status mi_clahe_bgra_to_yuv420(mi_ctx* ctx, const uint8_t* in, size_t in_step, const mi_yuv420_planes* out,
+        int width, int height, int order, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
+/* mi_*_bgra_to_yuv420_frames_dev: the same conversion on a LIST of device frames, each at its own addresses -- a pool of CV_8UC4
+ * surfaces in (a renderer, a compositor or a capture API hands over one surface per frame), an encoder's frame pool out (NV12: a
+ * pitched Y and a pitched UV plane per surface; x264, libvpx, SVT-AV1: three separately allocated, pitched planes).  The batch form
+ * needs both sides in one allocation each at a constant frame stride; one n_frames = 1 batch call per frame costs a launch sequence
+ * per frame with tiny grids, and repacking both pools into strided scratch moves 4 + 1.5 bytes per pixel more each way.
+ * `frames` is a host array of n_frames entries of the existing mi_bgr_yuv420_frame_dev {in, y, c0, c1}, read only during the call; the
+ * pointers in it are device pointers on the context's device.
+ * Shape: all frames of one call share width, height, order, uv_mode, chroma and the three pitches (bytes between rows); each has its
+ *   own addresses.  There are no per-frame pitches.
+ *   in : H rows of 4*W bytes at in_pitch >= 4*W -- B, G, R, X per pixel (MI_ORDER_BGR) or R, G, B, X (MI_ORDER_RGB); X takes no part
+ *   y  : H rows of W bytes at y_pitch >= W
+ *   chroma == MI_CHROMA_PLANAR: c0 is always U and c1 always V, each H/2 rows of W/2 bytes at c_pitch >= W/2 (both planes share the
+ *        pitch): a YV12 caller exchanges the two addresses.
+ *   chroma == MI_CHROMA_INTERLEAVED: c0 is the UV plane, H/2 rows of W bytes at c_pitch >= W; c1 is ignored and may be NULL.  The list is
+ *        not handed to another form: one pair of entry points and one set of counters serves both layouts.
+ * Bytes: per frame the output is byte for byte what mi_*_bgra_to_yuv420_batch_dev writes for that frame alone at the same pitches --
+ *   cvtColor(COLOR_BGRA2YUV_I420, or the RGBA code), then cv::equalizeHist / CLAHE::apply on Y, U and V of the conversion (MI_UV_COPY) or
+ *   every chroma byte 128 (MI_UV_FILL128); the clahe_fp_contract option is honoured, REFLECT_101 padding applies when the tile grid
+ *   does not divide the frame, the limits on sizes and tile grids are the batch form's, with the same statuses.
+ * Writes: only the W bytes of each Y and interleaved UV row and the W/2 bytes of each planar U and V row are written: not the pitch
+ *   padding, not the gaps between planes or frames.  The images are never written.
+ * Alignment: none is required of any address or pitch.  The shape decides what is allowed: 16 x 2 pixel groups when W % 16 == 0,
+ *   in_pitch and y_pitch are multiples of 16 and c_pitch is a multiple of 16 (interleaved) or 8 (planar).  Each frame then decides by
+ *   its own addresses: it takes the groups when its in and y are multiples of 16 and its c0 is a multiple of 16 (interleaved) or its
+ *   c0 and c1 are multiples of 8 (planar), and any other frame of the same call processes 2 x 2 pixel blocks with byte accesses while
+ *   its neighbours stay vectorised -- slower, the same bytes out.
+ * Stages, per chunk of 64 frames of the list (not the batch form's 256): stage 1 is ONE launch charged to MI_K_COLOR that converts
+ *   into the caller's planes and, for equalizeHist, counts the luma bytes it has just produced.  Stage 2 maps the luma IN PLACE on the
+ *   chunk's Y planes: equalizeHist one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch (no MI_K_HIST launch; never the fused equalizeHist
+ *   kernel nor the single-launch histogram + LUT kernel, option two_kernel_max_frames does not apply); CLAHE exactly what
+ *   mi_clahe_nv12_frames_dev launches in place on those Y planes.  Launches are charged to the same profiling slots as the batch form.
+ *   Between the stages a frame's y holds the unequalized luma.
+ * Counters (mi_ctx_get_stat): "bgra_yuv420_list_frames_vec" / "bgra_yuv420_list_frames_bytes" count the FRAMES (not calls) of list
+ *   calls by the walk their stage-1 kernel took: 16 x 2 groups / 2 x 2 blocks, n_frames in total per call.  "bgra_yuv420_vec" /
+ *   "bgra_yuv420_bytes" are not touched by list calls.  A call that returns an error or has nothing to do moves none.
+ * Overlap: there is no in-place form.  MI_ERR_BAD_ARG when the rows of a frame's image (4*W bytes each) meet the rows of a plane of
+ *   its own frame, or the rows of its Y plane meet the rows of a chroma plane of its own (compared as address ranges), and on a PLANAR
+ *   list when c0 == c1.  U and V are otherwise not compared with each other: the U and V rows may lie side by side in one pitched
+ *   plane (c1 = c0 + W/2, c_pitch = W), as in the batch form.  The same image may appear in several entries (inputs are only read).
+ *   Outputs that overlap ANOTHER frame's planes give undefined results and are not checked.
+ * Errors, MI_ERR_BAD_ARG: a null ctx; a null `frames` with n_frames > 0; a null in, y or c0 in any entry; a null c1 in any entry on a
+ *   PLANAR list; a `chroma` other than the two values; an `order` other than the two; a bad uv_mode; a negative size; an odd width or
+ *   an odd height (refused even when another size is 0, as in the batch form); in_pitch < 4*W; y_pitch < W; a c_pitch below its row
+ *   (W interleaved, W/2 planar); tiles <= 0; the overlap above.  Sizes and tile grids the planar forms refuse: the status they give
+ *   (MI_ERR_UNSUPPORTED).  width, height or n_frames of 0: MI_OK, nothing written (n_frames == 0 with a null list is MI_OK).  Nothing
+ *   is enqueued unless every frame passes the checks: a bad last entry leaves the first frames' outputs untouched.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of
+ *   the same shape as the other device list forms; a captured graph holds the addresses it was captured with. */
+mi_status mi_equalize_hist_bgra_to_yuv420_frames_dev(mi_ctx* ctx, const mi_bgr_yuv420_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t y_pitch, size_t c_pitch, int chroma, int order, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_bgra_to_yuv420_frames_dev(mi_ctx* ctx, const mi_bgr_yuv420_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t y_pitch, size_t c_pitch, int chroma, int order, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
 
 /* ---- optional: pin caller-owned host buffers----------------------------------------------------------------
  * Video pipelines recycle a small pool of frame buffers (GstBufferPool; the reference maps such buffers at

@@ -361,6 +361,12 @@ mi_status mi_ctx_synchronize(mi_ctx* c, void* stream)
 // "bgr_yuv420_list_frames_vec" / "bgr_yuv420_list_frames_bytes" (FRAMES of PLANAR mi_*_bgr_to_yuv420_frames_dev calls whose conversion
 // kernel walked 16 x 2 pixel groups / 2 x 2 blocks, each by its own addresses; list calls do not touch "bgr_yuv420_vec" /
 // "bgr_yuv420_bytes", and an INTERLEAVED list is the NV12 list form's call and moves none of the four),
+// "bgra_yuv420_vec" / "bgra_yuv420_bytes" (mi_*_bgra_to_yuv420* calls, device and host forms, PLANAR and INTERLEAVED output alike -- both
+// layouts are that form's own kernels -- whose conversion kernel walked 16 x 2 pixel groups / 2 x 2 blocks with byte accesses: one count
+// per call with work to do; a refused or empty call moves neither),
+// "bgra_yuv420_list_frames_vec" / "bgra_yuv420_list_frames_bytes" (FRAMES of mi_*_bgra_to_yuv420_frames_dev calls, either chroma layout,
+// whose conversion kernel walked 16 x 2 pixel groups / 2 x 2 blocks, each by its own addresses; n_frames in total per call, counted
+// once the whole call is enqueued; list calls do not touch "bgra_yuv420_vec" / "bgra_yuv420_bytes"),
 // "packed422_bgr_list_frames_wide" / "packed422_bgr_list_frames_bytes" (FRAMES of mi_*_packed422_to_bgr_frames_dev calls whose image was
 // stored 16 bytes per access / byte by byte: out_pitch and the frame's own `out` multiples of 4, or not; counted once the whole call is
 // enqueued, never for a refused call or one with nothing to do),
@@ -420,6 +426,10 @@ mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
     if (!strcmp(name, "bgr_yuv420_bytes")) { *out = c->bgr_yuv420_bytes; return MI_OK; }
     if (!strcmp(name, "bgr_yuv420_list_frames_vec")) { *out = c->bgr_yuv420_list_frames_vec; return MI_OK; }
     if (!strcmp(name, "bgr_yuv420_list_frames_bytes")) { *out = c->bgr_yuv420_list_frames_bytes; return MI_OK; }
+    if (!strcmp(name, "bgra_yuv420_vec")) { *out = c->bgra_yuv420_vec; return MI_OK; }
+    if (!strcmp(name, "bgra_yuv420_bytes")) { *out = c->bgra_yuv420_bytes; return MI_OK; }
+    if (!strcmp(name, "bgra_yuv420_list_frames_vec")) { *out = c->bgra_yuv420_list_frames_vec; return MI_OK; }
+    if (!strcmp(name, "bgra_yuv420_list_frames_bytes")) { *out = c->bgra_yuv420_list_frames_bytes; return MI_OK; }
     if (!strcmp(name, "packed422_bgr_list_frames_wide")) { *out = c->packed422_bgr_list_frames_wide; return MI_OK; }
     if (!strcmp(name, "packed422_bgr_list_frames_bytes")) { *out = c->packed422_bgr_list_frames_bytes; return MI_OK; }
     if (!strcmp(name, "bgr_packed422_vec")) { *out = c->bgr_packed422_vec; return MI_OK; }

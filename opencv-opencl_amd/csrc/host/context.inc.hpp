@@ -174,6 +174,10 @@ struct mi_ctx {
                                                                         // walk their conversion kernel took (16 x 2 pixel groups / 2 x 2 blocks with byte accesses)
     unsigned long long bgr_yuv420_list_frames_vec = 0, bgr_yuv420_list_frames_bytes = 0;   // statistics "bgr_yuv420_list_frames_vec" / "bgr_yuv420_list_frames_bytes":
                                                                         // FRAMES of PLANAR mi_*_bgr_to_yuv420_frames_dev calls by that walk, each by its own addresses
+    uint64_t bgra_yuv420_vec = 0, bgra_yuv420_bytes = 0;                // statistics "bgra_yuv420_vec" / "bgra_yuv420_bytes": mi_*_bgra_to_yuv420* calls (device and host
+                                                                        // forms, either chroma layout) by the walk their conversion kernel took (16 x 2 groups / 2 x 2 blocks)
+    unsigned long long bgra_yuv420_list_frames_vec = 0, bgra_yuv420_list_frames_bytes = 0;   // statistics "bgra_yuv420_list_frames_vec" / "bgra_yuv420_list_frames_bytes":
+                                                                        // FRAMES of mi_*_bgra_to_yuv420_frames_dev calls by that walk, each by its own addresses
     unsigned long long packed422_bgr_list_frames_wide = 0, packed422_bgr_list_frames_bytes = 0;   // statistics "packed422_bgr_list_frames_wide" /
                                                                         // "packed422_bgr_list_frames_bytes": FRAMES of mi_*_packed422_to_bgr_frames_dev calls whose image
                                                                         // left as 16-byte / as byte stores, each by its own address

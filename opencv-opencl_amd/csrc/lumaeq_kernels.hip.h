@@ -45,6 +45,8 @@
 //                                  list of {y, u, v, out} addresses
 //   kernels/packed422_bgr.hip.h    the pixel-writing stages of packed 4:2:2 in, interleaved BGR / RGB out: LUT apply / CLAHE blend + decode,
 //                                  every row with its own chroma
+//   kernels/bgra_yuv420.hip.h      stage 1 of four-channel BGRA / RGBA (CV_8UC4) in, 4:2:0 out: one body for NV12 and planar chroma, for a
+//                                  strided batch and a list of {in, y, c0, c1} addresses; the fourth byte takes part in nothing
 #pragma once
 #include "kernels/common.hip.h"
 #include "kernels/equalize.hip.h"
@@ -65,3 +67,4 @@
 #include "kernels/yuv420.hip.h"
 #include "kernels/yuv420_bgr.hip.h"
 #include "kernels/packed422_bgr.hip.h"
+#include "kernels/bgra_yuv420.hip.h"

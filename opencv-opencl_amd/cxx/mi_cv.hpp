@@ -591,6 +591,26 @@ inline void claheBGRToYUV420(const unsigned char* in, size_t inStep, const YUV42
     detail::check(c, mi_clahe_bgr_to_yuv420(c, in, inStep, &b, width, height, (int)order, (mi_uv_mode)uv, clipLimit, tiles.width,
                                             tiles.height), "mi_clahe_bgr_to_yuv420");
 }
+// The same edge for four-byte pixels: one interleaved CV_8UC4 host image (BGRA / BGRX, or RGBA / RGBX) at inStep >= 4*W in, the planes
+// of the view out: cv::cvtColor(COLOR_BGRA2YUV_I420) + cv::equalizeHist / CLAHE::apply on the Y plane; the fourth byte takes no part.
+// A render target's or a screen capture's surface -> an encoder's planes, without a three-channel copy in between.  Planar and
+// interleaved views alike.
+inline void equalizeHistBGRAToYUV420(const unsigned char* in, size_t inStep, const YUV420View& out, int width, int height,
+                                     ChannelOrder order = ORDER_BGR, UVMode uv = UV_COPY)
+{
+    mi_ctx* c = detail::thread_ctx();
+    const mi_yuv420_planes b = out.planes();
+    detail::check(c, mi_equalize_hist_bgra_to_yuv420(c, in, inStep, &b, width, height, (int)order, (mi_uv_mode)uv),
+                  "mi_equalize_hist_bgra_to_yuv420");
+}
+inline void claheBGRAToYUV420(const unsigned char* in, size_t inStep, const YUV420View& out, int width, int height, double clipLimit,
+                              Size tiles, ChannelOrder order = ORDER_BGR, UVMode uv = UV_COPY)
+{
+    mi_ctx* c = detail::thread_ctx();
+    const mi_yuv420_planes b = out.planes();
+    detail::check(c, mi_clahe_bgra_to_yuv420(c, in, inStep, &b, width, height, (int)order, (mi_uv_mode)uv, clipLimit, tiles.width,
+                                             tiles.height), "mi_clahe_bgra_to_yuv420");
+}
 // The playout edge: one interleaved CV_8UC3 host image (BGR, or RGB) at inStep >= 3*W in, one packed 4:2:2 frame (FMT_YUY2 / FMT_UYVY) at
 // outPitch >= 2*W out: the luma of cv::cvtColor(COLOR_BGR2YUV_I420) equalized, every row with the chroma of its own pixels (the left pixel
 // of each macropixel, UV_COPY) or chroma 128 (UV_FILL128): a renderer's or a model's image -> a playout card, a v4l2 output or loopback

@@ -73,6 +73,8 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_yuv420_to_packed422_batch_dev", "mi_clahe_yuv420_to_packed422_batch_dev",
     "mi_equalize_hist_yuv420_to_packed422", "mi_clahe_yuv420_to_packed422",
     "mi_equalize_hist_yuv420_to_packed422_frames_dev", "mi_clahe_yuv420_to_packed422_frames_dev",
+    "mi_equalize_hist_bgra_to_yuv420_batch_dev", "mi_clahe_bgra_to_yuv420_batch_dev", "mi_equalize_hist_bgra_to_yuv420", "mi_clahe_bgra_to_yuv420",
+    "mi_equalize_hist_bgra_to_yuv420_frames_dev", "mi_clahe_bgra_to_yuv420_frames_dev",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -336,6 +338,12 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_bgr_to_yuv420.argtypes = [vp, vp, sz, yp, i, i, i, i, d, i, i]
     L.mi_equalize_hist_bgr_to_yuv420_frames_dev.argtypes = [vp, C.POINTER(BgrYuv420FrameDev), i, i, i, sz, sz, sz, i, i, i, vp]
     L.mi_clahe_bgr_to_yuv420_frames_dev.argtypes = [vp, C.POINTER(BgrYuv420FrameDev), i, i, i, sz, sz, sz, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_bgra_to_yuv420_batch_dev.argtypes = [vp, vp, sz, sz, yp, i, i, i, i, i, vp]
+    L.mi_clahe_bgra_to_yuv420_batch_dev.argtypes = [vp, vp, sz, sz, yp, i, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_bgra_to_yuv420.argtypes = [vp, vp, sz, yp, i, i, i, i]
+    L.mi_clahe_bgra_to_yuv420.argtypes = [vp, vp, sz, yp, i, i, i, i, d, i, i]
+    L.mi_equalize_hist_bgra_to_yuv420_frames_dev.argtypes = [vp, C.POINTER(BgrYuv420FrameDev), i, i, i, sz, sz, sz, i, i, i, vp]
+    L.mi_clahe_bgra_to_yuv420_frames_dev.argtypes = [vp, C.POINTER(BgrYuv420FrameDev), i, i, i, sz, sz, sz, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_bgr_to_packed422_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, i, vp]
     L.mi_clahe_bgr_to_packed422_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_bgr_to_packed422.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, i]
@@ -1423,6 +1431,77 @@ class Context:
         self._chk(self._L.mi_clahe_bgr_to_yuv420_frames_dev(self._h, arr, n, int(width), int(height), int(in_pitch), int(y_pitch),
                                                           int(c_pitch), int(chroma), int(order), int(uv_mode), float(clip_limit),
                                                           int(tiles_x), int(tiles_y), stream), "mi_clahe_bgr_to_yuv420_frames_dev")
+
+    # ---- four-channel BGRA / RGBA (CV_8UC4) in, 4:2:0 frames (I420 / YV12 planes, or NV12) out: the fourth byte takes no part ----
+    def equalize_hist_bgra_to_yuv420_batch_dev(self, d_in, dst, width, height, n_frames, order=ORDER_BGR, uv_mode=UV_COPY, in_pitch=None,
+                                               in_frame=None, stream=0):
+        """mi_equalize_hist_bgra_to_yuv420_batch_dev.  d_in: the four-byte-per-pixel images (a torch tensor or a raw address); dst: a
+        Yuv420Planes holding device addresses (Yuv420Planes.i420 / .yv12 / .nv12 for tight batches, the fields themselves for pitched or
+        separately allocated planes).  The tight input is the default: in_pitch 4*W, in_frame = in_pitch * H."""
+        ip = 4 * int(width) if in_pitch is None else int(in_pitch)
+        fi = ip * int(height) if in_frame is None else int(in_frame)
+        self._chk(self._L.mi_equalize_hist_bgra_to_yuv420_batch_dev(self._h, _dptr(d_in), ip, fi, C.byref(dst), int(width), int(height),
+                                                                  int(n_frames), int(order), int(uv_mode), stream),
+                  "mi_equalize_hist_bgra_to_yuv420_batch_dev")
+
+    def clahe_bgra_to_yuv420_batch_dev(self, d_in, dst, width, height, n_frames, order=ORDER_BGR, uv_mode=UV_COPY, clip_limit=2.0,
+                                       tiles_x=8, tiles_y=8, in_pitch=None, in_frame=None, stream=0):
+        """mi_clahe_bgra_to_yuv420_batch_dev; arguments as equalize_hist_bgra_to_yuv420_batch_dev, plus the CLAHE parameters."""
+        ip = 4 * int(width) if in_pitch is None else int(in_pitch)
+        fi = ip * int(height) if in_frame is None else int(in_frame)
+        self._chk(self._L.mi_clahe_bgra_to_yuv420_batch_dev(self._h, _dptr(d_in), ip, fi, C.byref(dst), int(width), int(height),
+                                                          int(n_frames), int(order), int(uv_mode), float(clip_limit), int(tiles_x),
+                                                          int(tiles_y), stream), "mi_clahe_bgra_to_yuv420_batch_dev")
+
+    def _bgra_yuv420_host(self, img, dst_fmt, out, name):
+        if dst_fmt not in _YUV420_FMTS:
+            raise MiError(1, name, 'dst_fmt must be "nv12", "i420" or "yv12"')
+        if not isinstance(img, np.ndarray) or img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 4:
+            raise MiError(2, name, "expected an HxWx4 uint8 ndarray (CV_8UC4)")
+        if img.size and (img.strides[2] != 1 or img.strides[1] != 4):
+            raise MiError(1, name, "pixels must be interleaved")
+        h, w = img.shape[:2]
+        if out is None:
+            out = np.empty(w * h * 3 // 2, np.uint8)
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous or out.size != w * h * 3 // 2:
+            raise MiError(1, name, "out must be a contiguous uint8 array of width*height*3/2 bytes")
+        step = int(img.strides[0]) if h > 1 else max(int(img.strides[0]), 4 * w)
+        return img, h, w, step, out, _YUV420_FMTS[dst_fmt](out.ctypes.data, w, h)
+
+    def equalize_hist_bgra_to_yuv420(self, img: np.ndarray, dst_fmt: str = "i420", order: int = ORDER_BGR, uv_mode: int = UV_COPY,
+                                     out: np.ndarray | None = None) -> np.ndarray:
+        """mi_equalize_hist_bgra_to_yuv420 on a host image: an H x W x 4 uint8 array in (a view with padded rows included), the tight
+        frame of W*H*3/2 bytes out, its chroma laid out as dst_fmt in {"nv12", "i420", "yv12"} says -- `out` when given, else a new array."""
+        img, h, w, step, out, b = self._bgra_yuv420_host(img, dst_fmt, out, "equalize_hist_bgra_to_yuv420")
+        self._chk(self._L.mi_equalize_hist_bgra_to_yuv420(self._h, img.ctypes.data, step, C.byref(b), w, h, int(order), int(uv_mode)),
+                  "mi_equalize_hist_bgra_to_yuv420")
+        return out
+
+    def clahe_bgra_to_yuv420(self, img: np.ndarray, dst_fmt: str = "i420", order: int = ORDER_BGR, uv_mode: int = UV_COPY,
+                             clip_limit: float = 2.0, tiles_x: int = 8, tiles_y: int = 8, out: np.ndarray | None = None) -> np.ndarray:
+        """mi_clahe_bgra_to_yuv420; arguments as equalize_hist_bgra_to_yuv420, plus the CLAHE parameters."""
+        img, h, w, step, out, b = self._bgra_yuv420_host(img, dst_fmt, out, "clahe_bgra_to_yuv420")
+        self._chk(self._L.mi_clahe_bgra_to_yuv420(self._h, img.ctypes.data, step, C.byref(b), w, h, int(order), int(uv_mode),
+                                                float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_bgra_to_yuv420")
+        return out
+
+    def equalize_hist_bgra_to_yuv420_frames_dev(self, frames, width, height, in_pitch, y_pitch, c_pitch, chroma, order=ORDER_BGR,
+                                                uv_mode=UV_COPY, stream=0):
+        """mi_equalize_hist_bgra_to_yuv420_frames_dev.  frames: BgrYuv420FrameDev entries, one per frame, every four-byte-per-pixel image
+        and every plane at its own device address (a surface pool in, an encoder's frame pool out); one shape, one set of pitches and
+        one chroma layout for the call (c1 is ignored on an interleaved list)."""
+        arr, n = self._bgr_yuv420_list(frames)
+        self._chk(self._L.mi_equalize_hist_bgra_to_yuv420_frames_dev(self._h, arr, n, int(width), int(height), int(in_pitch), int(y_pitch),
+                                                                   int(c_pitch), int(chroma), int(order), int(uv_mode), stream),
+                  "mi_equalize_hist_bgra_to_yuv420_frames_dev")
+
+    def clahe_bgra_to_yuv420_frames_dev(self, frames, width, height, in_pitch, y_pitch, c_pitch, chroma, order=ORDER_BGR, uv_mode=UV_COPY,
+                                        clip_limit=2.0, tiles_x=8, tiles_y=8, stream=0):
+        """mi_clahe_bgra_to_yuv420_frames_dev; arguments as equalize_hist_bgra_to_yuv420_frames_dev, plus the CLAHE parameters."""
+        arr, n = self._bgr_yuv420_list(frames)
+        self._chk(self._L.mi_clahe_bgra_to_yuv420_frames_dev(self._h, arr, n, int(width), int(height), int(in_pitch), int(y_pitch),
+                                                           int(c_pitch), int(chroma), int(order), int(uv_mode), float(clip_limit),
+                                                           int(tiles_x), int(tiles_y), stream), "mi_clahe_bgra_to_yuv420_frames_dev")
 
     # ---- interleaved BGR / RGB in, packed 4:2:2 (YUY2 / UYVY) out: convert and count in one pass, then map the luma in place ----
     def equalize_hist_bgr_to_packed422_batch_dev(self, d_in, d_out, width, height, n_frames, order=ORDER_BGR, fmt=FMT_YUY2,
