@@ -1333,7 +1333,7 @@ mi_status mi_clahe_yuv420_to_packed422_frames_dev(mi_ctx* ctx, const mi_yuv420_p
  *   legal, as in mi_*_yuv420*.  width, height or n_frames of 0: MI_OK, nothing written (pointers and pitches are not looked at then).
  *   Sizes and tile grids the planar forms refuse: the status they give (MI_ERR_UNSUPPORTED), nothing written.  Nothing is enqueued
  *   unless every check passes.
- * Not built: 4:2:0 or packed 4:2:2 in, BGRA out; BGRA in, packed 4:2:2 out; a four-channel mi_bgr_luma_op; a mi_pipe format. */
+ * 4:2:0 in, BGRA out is mi_*_yuv420_to_bgra* below.  Not built: packed 4:2:2 in, BGRA out; BGRA in, packed 4:2:2 out; a four-channel mi_bgr_luma_op; a mi_pipe format. */
 mi_status mi_equalize_hist_bgra_to_yuv420_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
         const mi_yuv420_planes* out, int width, int height, int n_frames, int order, mi_uv_mode uv_mode, void* stream);
 mi_status mi_clahe_bgra_to_yuv420_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
@@ -1395,6 +1395,113 @@ mi_status mi_equalize_hist_bgra_to_yuv420_frames_dev(mi_ctx* ctx, const mi_bgr_y
         int width, int height, size_t in_pitch, size_t y_pitch, size_t c_pitch, int chroma, int order, mi_uv_mode uv_mode, void* stream);
 mi_status mi_clahe_bgra_to_yuv420_frames_dev(mi_ctx* ctx, const mi_bgr_yuv420_frame_dev* frames, int n_frames,
         int width, int height, size_t in_pitch, size_t y_pitch, size_t c_pitch, int chroma, int order, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
+/* mi_*_yuv420_to_bgra*: 4:2:0 frames described by mi_yuv420_planes in -- interleaved chroma (NV12: a hardware decoder's surfaces) or
+ * planar chroma (I420 / YV12: ffmpeg yuv420p, libvpx, dav1d) -- interleaved 8-bit FOUR-channel images (CV_8UC4: BGRA, or RGBA) out, in
+ * the pass that equalizes: decoder -> display surface, swap-chain image, GL / Vulkan / interop texture, Qt / SDL / Wayland buffer or
+ * GUI image, without a three-channel image in scratch and a widen to four channels outside the library.  In OpenCV terms
+ * cv::equalizeHist / CLAHE::apply on the Y plane, then cv::cvtColor with COLOR_YUV2BGRA_NV12, COLOR_YUV2BGRA_I420 or
+ * COLOR_YUV2BGRA_YV12 (MI_ORDER_BGR), or with COLOR_YUV2RGBA_NV12, COLOR_YUV2RGBA_I420 or COLOR_YUV2RGBA_YV12 (MI_ORDER_RGB).  Y is
+ * read twice (histograms, then map), the chroma once, 4 bytes per pixel are written: 6.5 B/px, where mi_*_yuv420_to_bgr_batch_dev into
+ * scratch plus a widen outside the library moves about 12.5.
+ *   input  : as in mi_*_yuv420_to_bgr*: `in` is read only during the call.  Frame f has every plane at pointer + f * in->frame_stride:
+ *            Y, H rows of W bytes at y_pitch >= W; MI_CHROMA_PLANAR: c0 is always U and c1 always V, each H/2 rows of W/2 bytes at
+ *            c_pitch >= W/2 (a YV12 caller passes its second chroma plane as c0); MI_CHROMA_INTERLEAVED: c0 is the UV plane, H/2 rows of
+ *            W bytes at c_pitch >= W, c1 is ignored and may be NULL.  Width and height must be even.  The input is never written.
+ *   output : frame f at d_out + f * out_frame_stride, H rows of 4*W bytes at out_pitch >= 4*W: B, G, R, A per pixel (MI_ORDER_BGR) or
+ *            R, G, B, A (MI_ORDER_RGB) with A = 255 in every pixel, what OpenCV's four-channel YUV decodes write.  Only the 4*W bytes
+ *            of each output row are written: not the pitch padding, not the gap between frames.  There is no in-place form.
+ * Bytes: the first three bytes of every pixel are byte for byte what mi_*_yuv420_to_bgr_batch_dev writes for the same call with the
+ *   same `order`, and the rest of the arithmetic contract is that form's: the clahe_fp_contract option is honoured (by the fallback),
+ *   REFLECT_101 padding applies when the tile grid does not divide the frame, the limits on sizes and tile grids are the planar
+ *   forms', with their statuses.  Never the fused equalizeHist kernel nor the single-launch histogram + LUT kernel.
+ * Both chroma layouts are this form's own kernels: unlike mi_*_yuv420_to_bgr*, an MI_CHROMA_INTERLEAVED input is not handed to the NV12
+ *   form, mi_*_nv12_to_bgr* is unchanged, and the counters below count both layouts.
+ * Alignment: none is required of any pointer, pitch or stride.  A call moves 16 x 2 pixel groups per lane when W % 16 == 0; in->y,
+ *   in->y_pitch, in->frame_stride, d_out, out_pitch and out_frame_stride are multiples of 16; and the chroma terms in->c0, in->c1 and
+ *   in->c_pitch are multiples of 16 for interleaved chroma (c1 not looked at) and of 8 for planar chroma.  A lane then makes two
+ *   16-byte Y loads, one 16-byte UV load or one 8-byte U load plus one 8-byte V load, and eight 16-byte stores (every dword one
+ *   pixel).  Otherwise the call processes 2 x 2 pixel blocks with byte accesses -- slower, the same bytes out.
+ * CLAHE maps and converts in one kernel (one pass) when that alignment rule holds and the shape is the NV12 form's one-pass shape
+ *   (the tile grid divides the frame, tile width a multiple of 16, tiles_x <= 14, clahe_fp_contract off); any other call runs the
+ *   planar CLAHE into scratch Y planes of the context and then the conversion alone: the same bytes in one more pass (two-pass).
+ *   equalizeHist always counts as one-pass.
+ * Counters (mi_ctx_get_stat): "yuv420_bgra_onepass" / "yuv420_bgra_twopass", one count per call; "yuv420_bgra_vec" /
+ *   "yuv420_bgra_bytes", one count per batch or host call by the walk the pixel-writing kernel took (16 x 2 groups / 2 x 2 blocks).
+ *   Every batch or host call with work to do moves exactly one counter of each pair; a call that returns an error or has a zero size
+ *   moves none.  No existing counter moves: not the "nv12_bgr_*" pair on an interleaved input, not the "yuv420_bgr_*" ones.
+ * Launches run in chunks of 256 frames and are charged to the existing profiling slots by role: MI_K_HIST, MI_K_EQ_LUT and
+ *   MI_K_LUT_APPLY (map + decode) for equalizeHist; the tile-LUT slots and MI_K_CLAHE_INTERP (blend + decode) for one-pass CLAHE;
+ *   MI_K_COLOR for the decode alone behind the planar CLAHE.  Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has
+ *   frames pending and hipGraph capture after one eager call of the same shape as the other batched device forms.
+ * mi_equalize_hist_yuv420_to_bgra / mi_clahe_yuv420_to_bgra: ONE frame with `in` holding HOST pointers at any address and pitch
+ *   (frame_stride is ignored), a CV_8UC4 image at out_step >= 4*W out.  Synchronous; the planes are staged like
+ *   mi_*_yuv420_to_bgr's (planes in pinned memory that are tight are DMA'd as they are, everything else goes through the context's
+ *   pinned staging) and the image comes back like that form's, at a row of 4*W bytes.  On the device the frame is tight with every
+ *   plane at a 16-byte aligned offset, so a W % 16 == 0 frame takes the 16 x 2 groups.  Whatever the call returns, no copy on the
+ *   caller's memory is in flight any more when it returns.  W*H > 0x7fffffff / 4: MI_ERR_UNSUPPORTED.
+ * Errors, MI_ERR_BAD_ARG: a null ctx or `in`; a `chroma` other than the two values; an `order` other than the two; a negative size; an
+ *   odd width or an odd height (refused even when another size is 0, as in the sibling forms); tiles <= 0; a null in->y, in->c0 or
+ *   d_out; a null in->c1 on a PLANAR input; y_pitch < W; a c_pitch below its row (W interleaved, W/2 planar); out_pitch < 4*W; d_out
+ *   equal to any input plane pointer of the call.  Any other overlap: undefined, not checked.  width, height or n_frames of 0: MI_OK,
+ *   nothing written.  Sizes and tile grids the planar forms refuse: the status they give (MI_ERR_UNSUPPORTED), nothing written.
+ *   Nothing is enqueued unless every check passes. */
+mi_status mi_equalize_hist_yuv420_to_bgra_batch_dev(mi_ctx* ctx, const mi_yuv420_planes* in, void* d_out, size_t out_pitch,
+        size_t out_frame_stride, int width, int height, int n_frames, int order, void* stream);
+mi_status mi_clahe_yuv420_to_bgra_batch_dev(mi_ctx* ctx, const mi_yuv420_planes* in, void* d_out, size_t out_pitch,
+        size_t out_frame_stride, int width, int height, int n_frames, int order,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
+mi_status mi_equalize_hist_yuv420_to_bgra(mi_ctx* ctx, const mi_yuv420_planes* in, uint8_t* out, size_t out_step,
+        int width, int height, int order);
+mi_status mi_clahe_yuv420_to_bgra(mi_ctx* ctx, const mi_yuv420_planes* in, uint8_t* out, size_t out_step,
+        int width, int height, int order, double clip_limit, int tiles_x, int tiles_y);
+/* mi_*_yuv420_to_bgra_frames_dev: the same conversion on a LIST of device frames, each at its own addresses -- a decoder's frame pool
+ * in (a software decoder: three separately allocated, pitched planes a frame, data[0..2] / linesize[0..2]; a hardware decoder: a Y
+ * and a UV plane a surface), a pool of CV_8UC4 surfaces or textures out.  `frames` is a host array of n_frames entries of the existing
+ * mi_yuv420_bgr_frame_dev {y, c0, c1, out}, read only during the call; the pointers in it are device pointers on the context's device.
+ * Shape: all frames of one call share width, height, order, chroma and the three pitches (bytes between rows); each has its own
+ *   addresses.  There are no per-frame pitches.
+ *   y  : H rows of W bytes at y_pitch >= W
+ *   chroma == MI_CHROMA_PLANAR: c0 is always U and c1 always V, each H/2 rows of W/2 bytes at c_pitch >= W/2 (both planes share the
+ *        pitch): a YV12 caller exchanges the two addresses.
+ *   chroma == MI_CHROMA_INTERLEAVED: c0 is the UV plane, H/2 rows of W bytes at c_pitch >= W; c1 is ignored and may be NULL.  The list is
+ *        not handed to another form: one pair of entry points and one set of counters serves both layouts.
+ *   out: H rows of 4*W bytes at out_pitch >= 4*W -- B, G, R, A per pixel (MI_ORDER_BGR) or R, G, B, A (MI_ORDER_RGB), A = 255
+ * Bytes: per frame the output is byte for byte what mi_*_yuv420_to_bgra_batch_dev writes for that frame alone at the same pitches; the
+ *   clahe_fp_contract option is honoured, REFLECT_101 padding applies when the tile grid does not divide the frame, the limits on
+ *   sizes and tile grids are the batch form's, with the same statuses.
+ * Writes: only the 4*W bytes of each output row are written, not the pitch padding; the input planes are never written.
+ * Alignment: none is required of any address or pitch.  The shape decides what is allowed: 16 x 2 pixel groups when W % 16 == 0,
+ *   y_pitch and out_pitch are multiples of 16 and c_pitch is a multiple of 16 (interleaved) or 8 (planar).  Each frame then decides by
+ *   its own addresses: it takes the groups when its y and out are multiples of 16 and its c0 is a multiple of 16 (interleaved) or its
+ *   c0 and c1 are multiples of 8 (planar), and any other frame of the same call processes 2 x 2 pixel blocks with byte accesses while
+ *   its neighbours stay vectorised -- slower, the same bytes out.  equalizeHist always maps the luma and converts in one kernel.
+ *   CLAHE does so when the shape is the batch form's one-pass shape, the shape rule above holds and every frame of the call satisfies
+ *   the address rule; otherwise the whole call runs the planar CLAHE into scratch Y planes of the context and converts from there:
+ *   the same bytes in one more pass.  (In that fallback the Y address the rule sees is the scratch plane's, which is aligned; the
+ *   pitches are still the caller's.)
+ * Counters (mi_ctx_get_stat): "yuv420_bgra_onepass" / "yuv420_bgra_twopass" count the calls of the list form too, one count a call
+ *   (equalizeHist always counts as one-pass).  "yuv420_bgra_list_frames_vec" / "yuv420_bgra_list_frames_bytes" count the FRAMES (not
+ *   calls) of list calls by the walk their pixel-writing kernel took: 16 x 2 groups / 2 x 2 blocks, n_frames in total per call.
+ *   "yuv420_bgra_vec" / "yuv420_bgra_bytes" are not touched by list calls.  A call that returns an error or has nothing to do moves
+ *   none; no existing counter moves.
+ * Launches are charged to the same profiling slots as the batch form, per chunk of 64 frames of the list (not the batch form's 256).
+ * Overlap: there is no in-place form.  MI_ERR_BAD_ARG when the rows of a frame's image (4*W bytes each) meet the rows of its own Y, U
+ *   or V plane (or UV plane; compared as address ranges).  Input planes are not compared with each other: the U and V rows may lie
+ *   side by side in one pitched plane (c1 = c0 + W/2, c_pitch = W).  The same input planes may appear in several entries (inputs are
+ *   only read).  Outputs that overlap each other or ANOTHER frame's planes give undefined results and are not checked.
+ * Errors, MI_ERR_BAD_ARG: a null ctx; a null `frames` with n_frames > 0; a null y, c0 or out in any entry; a null c1 in any entry on a
+ *   PLANAR list; a `chroma` other than the two values; an `order` other than the two; a negative size; an odd width or an odd height
+ *   (refused even when another size is 0, as in the batch form); y_pitch < W; a c_pitch below its row (W interleaved, W/2 planar);
+ *   out_pitch < 4*W; tiles <= 0; the overlap above.  Sizes and tile grids the planar forms refuse: the status they give
+ *   (MI_ERR_UNSUPPORTED).  width, height or n_frames of 0: MI_OK, nothing written.  Nothing is enqueued unless every frame passes the
+ *   checks: a bad last entry leaves the first frames' outputs untouched.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of
+ *   the same shape as the other device list forms; a captured graph holds the addresses it was captured with. */
+mi_status mi_equalize_hist_yuv420_to_bgra_frames_dev(mi_ctx* ctx, const mi_yuv420_bgr_frame_dev* frames, int n_frames,
+        int width, int height, size_t y_pitch, size_t c_pitch, int chroma, size_t out_pitch, int order, void* stream);
+mi_status mi_clahe_yuv420_to_bgra_frames_dev(mi_ctx* ctx, const mi_yuv420_bgr_frame_dev* frames, int n_frames,
+        int width, int height, size_t y_pitch, size_t c_pitch, int chroma, size_t out_pitch, int order,
         double clip_limit, int tiles_x, int tiles_y, void* stream);
 
 /* ---- optional: pin caller-owned host buffers----------------------------------------------------------------

@@ -367,6 +367,13 @@ mi_status mi_ctx_synchronize(mi_ctx* c, void* stream)
 // "bgra_yuv420_list_frames_vec" / "bgra_yuv420_list_frames_bytes" (FRAMES of mi_*_bgra_to_yuv420_frames_dev calls, either chroma layout,
 // whose conversion kernel walked 16 x 2 pixel groups / 2 x 2 blocks, each by its own addresses; n_frames in total per call, counted
 // once the whole call is enqueued; list calls do not touch "bgra_yuv420_vec" / "bgra_yuv420_bytes"),
+// "yuv420_bgra_onepass" / "yuv420_bgra_twopass" (mi_*_yuv420_to_bgra* calls, batch, host and list forms, PLANAR and INTERLEAVED input
+// alike -- both layouts are that form's own kernels: mapped and decoded in one kernel / planar CLAHE into scratch first; one count per
+// call with work to do, equalizeHist always one-pass), "yuv420_bgra_vec" / "yuv420_bgra_bytes" (the batch and host calls by the walk
+// their pixel-writing kernel took: 16 x 2 pixel groups / 2 x 2 blocks with byte accesses; list calls do not touch them),
+// "yuv420_bgra_list_frames_vec" / "yuv420_bgra_list_frames_bytes" (FRAMES of mi_*_yuv420_to_bgra_frames_dev calls by that walk, each
+// by its own addresses; n_frames in total per call, counted once the whole call is enqueued; a refused or empty call moves none of the
+// six, and no new call moves an nv12_bgr_* or yuv420_bgr_* counter),
 // "packed422_bgr_list_frames_wide" / "packed422_bgr_list_frames_bytes" (FRAMES of mi_*_packed422_to_bgr_frames_dev calls whose image was
 // stored 16 bytes per access / byte by byte: out_pitch and the frame's own `out` multiples of 4, or not; counted once the whole call is
 // enqueued, never for a refused call or one with nothing to do),
@@ -430,6 +437,12 @@ mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
     if (!strcmp(name, "bgra_yuv420_bytes")) { *out = c->bgra_yuv420_bytes; return MI_OK; }
     if (!strcmp(name, "bgra_yuv420_list_frames_vec")) { *out = c->bgra_yuv420_list_frames_vec; return MI_OK; }
     if (!strcmp(name, "bgra_yuv420_list_frames_bytes")) { *out = c->bgra_yuv420_list_frames_bytes; return MI_OK; }
+    if (!strcmp(name, "yuv420_bgra_onepass")) { *out = c->yuv420_bgra_onepass; return MI_OK; }
+    if (!strcmp(name, "yuv420_bgra_twopass")) { *out = c->yuv420_bgra_twopass; return MI_OK; }
+    if (!strcmp(name, "yuv420_bgra_vec")) { *out = c->yuv420_bgra_vec; return MI_OK; }
+    if (!strcmp(name, "yuv420_bgra_bytes")) { *out = c->yuv420_bgra_bytes; return MI_OK; }
+    if (!strcmp(name, "yuv420_bgra_list_frames_vec")) { *out = c->yuv420_bgra_list_frames_vec; return MI_OK; }
+    if (!strcmp(name, "yuv420_bgra_list_frames_bytes")) { *out = c->yuv420_bgra_list_frames_bytes; return MI_OK; }
     if (!strcmp(name, "packed422_bgr_list_frames_wide")) { *out = c->packed422_bgr_list_frames_wide; return MI_OK; }
     if (!strcmp(name, "packed422_bgr_list_frames_bytes")) { *out = c->packed422_bgr_list_frames_bytes; return MI_OK; }
     if (!strcmp(name, "bgr_packed422_vec")) { *out = c->bgr_packed422_vec; return MI_OK; }

@@ -178,6 +178,12 @@ struct mi_ctx {
                                                                         // forms, either chroma layout) by the walk their conversion kernel took (16 x 2 groups / 2 x 2 blocks)
     unsigned long long bgra_yuv420_list_frames_vec = 0, bgra_yuv420_list_frames_bytes = 0;   // statistics "bgra_yuv420_list_frames_vec" / "bgra_yuv420_list_frames_bytes":
                                                                         // FRAMES of mi_*_bgra_to_yuv420_frames_dev calls by that walk, each by its own addresses
+    unsigned long long yuv420_bgra_onepass = 0, yuv420_bgra_twopass = 0;   // statistics "yuv420_bgra_onepass" / "yuv420_bgra_twopass": mi_*_yuv420_to_bgra* calls (batch,
+                                                                        // host and list forms, either chroma layout): mapped and decoded in one kernel / planar CLAHE first
+    unsigned long long yuv420_bgra_vec = 0, yuv420_bgra_bytes = 0;      // statistics "yuv420_bgra_vec" / "yuv420_bgra_bytes": batch and host calls by the walk their
+                                                                        // pixel-writing kernel took (16 x 2 pixel groups / 2 x 2 blocks with byte accesses)
+    unsigned long long yuv420_bgra_list_frames_vec = 0, yuv420_bgra_list_frames_bytes = 0;   // statistics "yuv420_bgra_list_frames_vec" / "yuv420_bgra_list_frames_bytes":
+                                                                        // FRAMES of mi_*_yuv420_to_bgra_frames_dev calls by that walk, each by its own addresses
     unsigned long long packed422_bgr_list_frames_wide = 0, packed422_bgr_list_frames_bytes = 0;   // statistics "packed422_bgr_list_frames_wide" /
                                                                         // "packed422_bgr_list_frames_bytes": FRAMES of mi_*_packed422_to_bgr_frames_dev calls whose image
                                                                         // left as 16-byte / as byte stores, each by its own address

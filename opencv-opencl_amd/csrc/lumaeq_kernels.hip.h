@@ -47,6 +47,9 @@
 //                                  every row with its own chroma
 //   kernels/bgra_yuv420.hip.h      stage 1 of four-channel BGRA / RGBA (CV_8UC4) in, 4:2:0 out: one body for NV12 and planar chroma, for a
 //                                  strided batch and a list of {in, y, c0, c1} addresses; the fourth byte takes part in nothing
+//   kernels/yuv420_bgra.hip.h      the pixel-writing stages of 4:2:0 in, four-channel BGRA / RGBA (CV_8UC4, A = 255) out: LUT apply / CLAHE
+//                                  blend + decode, one body each for NV12 and planar chroma, for a strided batch and a list of
+//                                  {y, c0, c1, out} addresses; every pixel one dword, a 16-pixel group four 16-byte stores
 #pragma once
 #include "kernels/common.hip.h"
 #include "kernels/equalize.hip.h"
@@ -68,3 +71,4 @@
 #include "kernels/yuv420_bgr.hip.h"
 #include "kernels/packed422_bgr.hip.h"
 #include "kernels/bgra_yuv420.hip.h"
+#include "kernels/yuv420_bgra.hip.h"

@@ -65,5 +65,7 @@ using namespace mi;
 #include "host/yuv420_packed422_frames.inc.hpp"  // the same on a list of frames, each at its own four addresses (decoder surface pool -> playout / v4l2 output buffer pool)
 #include "host/bgra_yuv420.inc.hpp"    // four-channel BGRA / RGBA (CV_8UC4) in, planar 4:2:0 (I420 / YV12) or NV12 out: convert and count, then map the luma in place (render target / capture -> encoder)
 #include "host/bgra_yuv420_frames.inc.hpp"  // ... as a list of pitched device frames (a surface pool in, an encoder's frame pool out)
+#include "host/yuv420_bgra.inc.hpp"    // planar 4:2:0 (I420 / YV12) or NV12 in, four-channel BGRA / RGBA (CV_8UC4, A = 255) out in the pass that maps the luma (decoder -> display surface / texture)
+#include "host/yuv420_bgra_frames.inc.hpp"  // ... as a list of pitched device frames (a decoder's frame pool in, a surface pool out)
 #include "host/pipe.inc.hpp"
 #include "host/diff.inc.hpp"

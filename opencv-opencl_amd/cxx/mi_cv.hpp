@@ -571,6 +571,24 @@ inline void claheYUV420ToBGR(const YUV420View& in, unsigned char* out, size_t ou
     detail::check(c, mi_clahe_yuv420_to_bgr(c, &a, out, outStep, width, height, (int)order, clipLimit, tiles.width, tiles.height),
                   "mi_clahe_yuv420_to_bgr");
 }
+// The same frame views in, an interleaved CV_8UC4 image (BGRA, or RGBA; A = 255) out: cv::equalizeHist / CLAHE::apply on the Y plane +
+// cv::cvtColor(COLOR_YUV2BGRA_I420 / _YV12 / _NV12): a decoder's frame -> a display surface, a texture or a GUI image without a
+// three-channel image in between.  `out`: H rows of 4*W bytes at outStep >= 4*W.
+inline void equalizeHistYUV420ToBGRA(const YUV420View& in, unsigned char* out, size_t outStep, int width, int height,
+                                     ChannelOrder order = ORDER_BGR)
+{
+    mi_ctx* c = detail::thread_ctx();
+    const mi_yuv420_planes a = in.planes();
+    detail::check(c, mi_equalize_hist_yuv420_to_bgra(c, &a, out, outStep, width, height, (int)order), "mi_equalize_hist_yuv420_to_bgra");
+}
+inline void claheYUV420ToBGRA(const YUV420View& in, unsigned char* out, size_t outStep, int width, int height, double clipLimit,
+                              Size tiles, ChannelOrder order = ORDER_BGR)
+{
+    mi_ctx* c = detail::thread_ctx();
+    const mi_yuv420_planes a = in.planes();
+    detail::check(c, mi_clahe_yuv420_to_bgra(c, &a, out, outStep, width, height, (int)order, clipLimit, tiles.width, tiles.height),
+                  "mi_clahe_yuv420_to_bgra");
+}
 // The opposite edge: one interleaved CV_8UC3 host image (BGR, or RGB) at inStep >= 3*W in, the planes of the view out:
 // cv::cvtColor(COLOR_BGR2YUV_I420) + cv::equalizeHist / CLAHE::apply on the Y plane, U into out.c0 and V into out.c1 (UV_COPY) or chroma
 // 128 (UV_FILL128): a renderer's or a model's image -> the three pitched planes a software encoder takes, without an NV12 frame in

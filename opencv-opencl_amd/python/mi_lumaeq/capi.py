@@ -75,6 +75,8 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_yuv420_to_packed422_frames_dev", "mi_clahe_yuv420_to_packed422_frames_dev",
     "mi_equalize_hist_bgra_to_yuv420_batch_dev", "mi_clahe_bgra_to_yuv420_batch_dev", "mi_equalize_hist_bgra_to_yuv420", "mi_clahe_bgra_to_yuv420",
     "mi_equalize_hist_bgra_to_yuv420_frames_dev", "mi_clahe_bgra_to_yuv420_frames_dev",
+    "mi_equalize_hist_yuv420_to_bgra_batch_dev", "mi_clahe_yuv420_to_bgra_batch_dev", "mi_equalize_hist_yuv420_to_bgra", "mi_clahe_yuv420_to_bgra",
+    "mi_equalize_hist_yuv420_to_bgra_frames_dev", "mi_clahe_yuv420_to_bgra_frames_dev",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -344,6 +346,12 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_bgra_to_yuv420.argtypes = [vp, vp, sz, yp, i, i, i, i, d, i, i]
     L.mi_equalize_hist_bgra_to_yuv420_frames_dev.argtypes = [vp, C.POINTER(BgrYuv420FrameDev), i, i, i, sz, sz, sz, i, i, i, vp]
     L.mi_clahe_bgra_to_yuv420_frames_dev.argtypes = [vp, C.POINTER(BgrYuv420FrameDev), i, i, i, sz, sz, sz, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_yuv420_to_bgra_batch_dev.argtypes = [vp, yp, vp, sz, sz, i, i, i, i, vp]
+    L.mi_clahe_yuv420_to_bgra_batch_dev.argtypes = [vp, yp, vp, sz, sz, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_yuv420_to_bgra.argtypes = [vp, yp, vp, sz, i, i, i]
+    L.mi_clahe_yuv420_to_bgra.argtypes = [vp, yp, vp, sz, i, i, i, d, i, i]
+    L.mi_equalize_hist_yuv420_to_bgra_frames_dev.argtypes = [vp, C.POINTER(Yuv420BgrFrameDev), i, i, i, sz, sz, i, sz, i, vp]
+    L.mi_clahe_yuv420_to_bgra_frames_dev.argtypes = [vp, C.POINTER(Yuv420BgrFrameDev), i, i, i, sz, sz, i, sz, i, d, i, i, vp]
     L.mi_equalize_hist_bgr_to_packed422_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, i, vp]
     L.mi_clahe_bgr_to_packed422_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_bgr_to_packed422.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, i]
@@ -1502,6 +1510,82 @@ class Context:
         self._chk(self._L.mi_clahe_bgra_to_yuv420_frames_dev(self._h, arr, n, int(width), int(height), int(in_pitch), int(y_pitch),
                                                            int(c_pitch), int(chroma), int(order), int(uv_mode), float(clip_limit),
                                                            int(tiles_x), int(tiles_y), stream), "mi_clahe_bgra_to_yuv420_frames_dev")
+
+    # ---- 4:2:0 frames (I420 / YV12 planes, or NV12) in, four-channel BGRA / RGBA (CV_8UC4, A = 255) out in the pass that maps the luma ----
+    def equalize_hist_yuv420_to_bgra_batch_dev(self, src, d_out, width, height, n_frames, order=ORDER_BGR, out_pitch=None, out_frame=None,
+                                               stream=0):
+        """mi_equalize_hist_yuv420_to_bgra_batch_dev.  src: a Yuv420Planes holding device addresses (Yuv420Planes.i420 / .yv12 / .nv12 for
+        tight batches, the fields themselves for pitched or separately allocated planes); d_out: the four-byte-per-pixel images (a torch
+        tensor or a raw address).  The tight output is the default: out_pitch 4*W, out_frame = out_pitch * H."""
+        op = 4 * int(width) if out_pitch is None else int(out_pitch)
+        fo = op * int(height) if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_equalize_hist_yuv420_to_bgra_batch_dev(self._h, C.byref(src), _dptr(d_out), op, fo, int(width), int(height),
+                                                                  int(n_frames), int(order), stream),
+                  "mi_equalize_hist_yuv420_to_bgra_batch_dev")
+
+    def clahe_yuv420_to_bgra_batch_dev(self, src, d_out, width, height, n_frames, order=ORDER_BGR, clip_limit=2.0, tiles_x=8, tiles_y=8,
+                                       out_pitch=None, out_frame=None, stream=0):
+        """mi_clahe_yuv420_to_bgra_batch_dev; arguments as equalize_hist_yuv420_to_bgra_batch_dev, plus the CLAHE parameters."""
+        op = 4 * int(width) if out_pitch is None else int(out_pitch)
+        fo = op * int(height) if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_clahe_yuv420_to_bgra_batch_dev(self._h, C.byref(src), _dptr(d_out), op, fo, int(width), int(height),
+                                                          int(n_frames), int(order), float(clip_limit), int(tiles_x), int(tiles_y), stream),
+                  "mi_clahe_yuv420_to_bgra_batch_dev")
+
+    def equalize_hist_yuv420_to_bgra_frames_dev(self, frames, width, height, y_pitch, c_pitch, chroma, order=ORDER_BGR, out_pitch=None,
+                                                stream=0):
+        """mi_equalize_hist_yuv420_to_bgra_frames_dev.  frames: Yuv420BgrFrameDev entries, one per frame, every plane and every
+        four-byte-per-pixel image at its own device address (a decoder's frame pool in, a surface pool out; c1 None on an interleaved
+        list); one shape, one set of pitches and one chroma layout for the call.  The tight image is the default: out_pitch 4*W."""
+        arr, n = self._yuv420_bgr_list(frames)
+        op = 4 * int(width) if out_pitch is None else int(out_pitch)
+        self._chk(self._L.mi_equalize_hist_yuv420_to_bgra_frames_dev(self._h, arr, n, int(width), int(height), int(y_pitch), int(c_pitch),
+                                                                   int(chroma), op, int(order), stream),
+                  "mi_equalize_hist_yuv420_to_bgra_frames_dev")
+
+    def clahe_yuv420_to_bgra_frames_dev(self, frames, width, height, y_pitch, c_pitch, chroma, order=ORDER_BGR, clip_limit=2.0, tiles_x=8,
+                                        tiles_y=8, out_pitch=None, stream=0):
+        """mi_clahe_yuv420_to_bgra_frames_dev; arguments as equalize_hist_yuv420_to_bgra_frames_dev, plus the CLAHE parameters."""
+        arr, n = self._yuv420_bgr_list(frames)
+        op = 4 * int(width) if out_pitch is None else int(out_pitch)
+        self._chk(self._L.mi_clahe_yuv420_to_bgra_frames_dev(self._h, arr, n, int(width), int(height), int(y_pitch), int(c_pitch),
+                                                           int(chroma), op, int(order), float(clip_limit), int(tiles_x), int(tiles_y),
+                                                           stream), "mi_clahe_yuv420_to_bgra_frames_dev")
+
+    def _yuv420_bgra_host(self, frame, width, height, src_fmt, out, name):
+        if src_fmt not in _YUV420_FMTS:
+            raise MiError(1, name, 'src_fmt must be "nv12", "i420" or "yv12"')
+        if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or not frame.flags.c_contiguous:
+            raise MiError(2, name, "expected a contiguous uint8 ndarray")
+        if width >= 0 and height >= 0 and frame.size != width * height * 3 // 2:
+            raise MiError(1, name, "4:2:0 frame must hold width*height*3/2 bytes")
+        if out is None:
+            out = np.empty((max(height, 0), max(width, 0), 4), np.uint8)
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.ndim != 3 or out.shape[2] != 4:
+            raise MiError(2, name, "expected an HxWx4 uint8 ndarray (CV_8UC4)")
+        if out.size and (out.strides[2] != 1 or out.strides[1] != 4):
+            raise MiError(1, name, "pixels must be interleaved")
+        if out.shape[:2] != (height, width):
+            raise MiError(1, name, "out must be an H x W x 4 uint8 array (rows may be padded)")
+        step = int(out.strides[0]) if height > 1 else max(int(out.strides[0]), 4 * width)
+        return _YUV420_FMTS[src_fmt](frame.ctypes.data, width, height), out, step
+
+    def equalize_hist_yuv420_to_bgra(self, frame: np.ndarray, width: int, height: int, src_fmt: str, order: int = ORDER_BGR,
+                                     out: np.ndarray | None = None) -> np.ndarray:
+        """mi_equalize_hist_yuv420_to_bgra on a tight host frame of W*H*3/2 bytes whose chroma lies as src_fmt in {"nv12", "i420", "yv12"}
+        says: the H x W x 4 image out, A = 255 -- `out` when given (a view with padded rows included), else a new tight array."""
+        a, out, step = self._yuv420_bgra_host(frame, int(width), int(height), src_fmt, out, "equalize_hist_yuv420_to_bgra")
+        self._chk(self._L.mi_equalize_hist_yuv420_to_bgra(self._h, C.byref(a), out.ctypes.data, step, int(width), int(height), int(order)),
+                  "mi_equalize_hist_yuv420_to_bgra")
+        return out
+
+    def clahe_yuv420_to_bgra(self, frame: np.ndarray, width: int, height: int, src_fmt: str, order: int = ORDER_BGR,
+                             clip_limit: float = 2.0, tiles_x: int = 8, tiles_y: int = 8, out: np.ndarray | None = None) -> np.ndarray:
+        """mi_clahe_yuv420_to_bgra; arguments as equalize_hist_yuv420_to_bgra, plus the CLAHE parameters."""
+        a, out, step = self._yuv420_bgra_host(frame, int(width), int(height), src_fmt, out, "clahe_yuv420_to_bgra")
+        self._chk(self._L.mi_clahe_yuv420_to_bgra(self._h, C.byref(a), out.ctypes.data, step, int(width), int(height), int(order),
+                                                float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_yuv420_to_bgra")
+        return out
 
     # ---- interleaved BGR / RGB in, packed 4:2:2 (YUY2 / UYVY) out: convert and count in one pass, then map the luma in place ----
     def equalize_hist_bgr_to_packed422_batch_dev(self, d_in, d_out, width, height, n_frames, order=ORDER_BGR, fmt=FMT_YUY2,
