@@ -617,6 +617,95 @@ mi_status mi_equalize_hist_packed422_to_bgr_frames_dev(mi_ctx* ctx, const mi_pac
 mi_status mi_clahe_packed422_to_bgr_frames_dev(mi_ctx* ctx, const mi_packed422_bgr_frame_dev* frames, int n_frames,
         int width, int height, size_t in_pitch, size_t out_pitch, int format, int order,
         double clip_limit, int tiles_x, int tiles_y, void* stream);
+/* mi_*_packed422_to_bgra*: packed 4:2:2 frames in (YUY2 / UYVY), interleaved 8-bit FOUR-channel images (CV_8UC4: BGRA, or RGBA) out, in
+ * the pass that equalizes -- capture card -> display surface, swap-chain image, GL / Vulkan / interop texture or GUI image, without a
+ * three-channel image in scratch and a widen to four channels outside the library.  Per frame the result is what OpenCV 4.4 gives for
+ *     cv::extractChannel(frame, y, off);  cv::equalizeHist(y, y)  /  clahe->apply(y, y);  cv::insertChannel(y, frame, off);
+ *     cv::cvtColor(frame, bgra, cv::COLOR_YUV2BGRA_YUY2);            (_UYVY for MI_FMT_UYVY; COLOR_YUV2RGBA_* for MI_ORDER_RGB)
+ * The packed frame is read twice (histograms, then map) and 4 bytes per pixel are written: 8 bytes per pixel, where
+ * mi_*_packed422_to_bgr_batch_dev into scratch plus a widen outside the library moves about 14.  The names, the argument order and
+ * everything not said here are those of mi_*_packed422_to_bgr* above.
+ *   pixels : the first three bytes of every pixel are byte for byte what mi_*_packed422_to_bgr* writes for the same call with the same
+ *            `format` and `order`; the fourth byte is 255 (A), what OpenCV's four-channel YUV decodes write.  Every row is decoded with
+ *            its own chroma.  THE CHROMA ORDER MATTERS as in that form: MI_FMT_YUY2 means exactly Y0 U Y1 V, MI_FMT_UYVY exactly
+ *            U Y0 V Y1; YVYU and VYUY are not supported.
+ *   input  : exactly the packed forms': frame f at d_in + f * in_frame_stride, H rows of 2*W bytes at in_pitch >= 2*W; the pointer, the
+ *            pitch and the frame stride are multiples of 4; `width` is even, `height` any value >= 1 (odd heights are legal).  The input
+ *            is never written.
+ *   output : frame f at d_out + f * out_frame_stride, H rows of 4*W bytes at out_pitch >= 4*W: B, G, R, A per pixel (MI_ORDER_BGR) or
+ *            R, G, B, A (MI_ORDER_RGB).  Only the 4*W bytes of each output row are written: not the pitch padding, not the gap between
+ *            frames.  No alignment is required of d_out, out_pitch or out_frame_stride: an odd address and an odd pitch are legal.
+ *   stores : a frame is WIDE when its image address is a multiple of 4 and so are out_pitch and, for a batch, out_frame_stride.  A wide
+ *            frame stores a 16-column group as four 16-byte stores (every dword one pixel: no pixel straddles a dword) and the ragged
+ *            last group of a row (W % 16 != 0) as dword stores.  Any other frame stores bytes -- slower, the same bytes out.
+ *   CLAHE  : every shape runs in one pass: there is no scratch Y plane and no two-pass fallback.  REFLECT_101 padding applies when the
+ *            tile grid does not divide the frame; the clahe_fp_contract and clahe_float_tables options apply as in the three-channel
+ *            form, as does the global-memory fallback for tile grids too wide for the LDS pair table.
+ * Never the fused equalizeHist kernel nor the single-launch histogram + LUT kernel; launches are charged to the existing profiling
+ * slots by role, as in the three-channel form.  Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and
+ * hipGraph capture after one eager call of the same shape as the other batched device forms.
+ * Counters (mi_ctx_get_stat): "packed422_bgra_wide" / "packed422_bgra_bytes" count the batch and host CALLS by the store path of their
+ * launch; a call that returns an error or has nothing to do moves neither.  No existing counter moves on a call of this form.
+ * mi_equalize_hist_packed422_to_bgra / mi_clahe_packed422_to_bgra: ONE packed host frame in, one CV_8UC4 image out, synchronous.  The
+ *   input side follows the rules of mi_*_packed422 (`in` and in_pitch multiples of 4, in_pitch >= 2*W; only the 2*W bytes of each row are
+ *   read); the output is host memory at any address and any out_step >= 4*W, only the 4*W bytes of each row are written.  Tight buffers
+ *   in pinned memory (mi_host_register) are DMA'd as they are, everything else goes through the context's pinned staging; the device
+ *   image is tight and aligned, so the call counts as wide.  Whatever the call returns, no copy on in / out is in flight any more when
+ *   it returns.  MI_ERR_BAD_ARG when the rows of the image meet the rows of the input; W*H > 0x7fffffff / 4: MI_ERR_UNSUPPORTED.
+ * Errors, MI_ERR_BAD_ARG: a null ctx or frame pointer, an odd width (refused even when another size is 0, as in the packed forms), a
+ * negative size, in_pitch < 2*W or out_pitch < 4*W, an input pointer / pitch / frame stride that is not a multiple of 4, a `format` or
+ * an `order` other than the two, tiles <= 0, d_out == d_in (there is no in-place form).  Any other overlap of input and output:
+ * undefined, not checked.  width, height or n_frames of 0: MI_OK, nothing written.  Sizes and tile grids the three-channel form refuses
+ * (more than 65535 tiles, a height above 65535 with tiles_x > 62, what the planar forms refuse): the status it gives
+ * (MI_ERR_UNSUPPORTED), nothing written.  Nothing is enqueued unless all checks pass. */
+mi_status mi_equalize_hist_packed422_to_bgra_batch_dev(mi_ctx* ctx,
+        const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        void* d_out, size_t out_pitch, size_t out_frame_stride,
+        int width, int height, int n_frames, int format, int order, void* stream);
+mi_status mi_clahe_packed422_to_bgra_batch_dev(mi_ctx* ctx,
+        const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        void* d_out, size_t out_pitch, size_t out_frame_stride,
+        int width, int height, int n_frames, int format, int order,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
+mi_status mi_equalize_hist_packed422_to_bgra(mi_ctx* ctx, const uint8_t* in, size_t in_pitch, uint8_t* out, size_t out_step,
+        int width, int height, int format, int order);
+mi_status mi_clahe_packed422_to_bgra(mi_ctx* ctx, const uint8_t* in, size_t in_pitch, uint8_t* out, size_t out_step,
+        int width, int height, int format, int order, double clip_limit, int tiles_x, int tiles_y);
+/* mi_*_packed422_to_bgra_frames_dev: the same conversion on a LIST of device frames, each at its own two addresses -- a capture
+ * device's buffer pool in, a swap chain or a pool of CV_8UC4 surfaces, textures or cv::Mats out.  `frames` is a host array of n_frames
+ * entries of the existing mi_packed422_bgr_frame_dev {in, out}, read only during the call; the pointers in it are device pointers on the
+ * context's device.
+ * Shape: all frames of one call share width, height, format, order and the two pitches (bytes between rows); each has its own addresses:
+ *   in : H rows of 2*W bytes at in_pitch >= 2*W     out: H rows of 4*W bytes at out_pitch >= 4*W -- B, G, R, A per pixel (MI_ORDER_BGR)
+ *                                                        or R, G, B, A (MI_ORDER_RGB), A = 255
+ * Bytes: per frame exactly what mi_*_packed422_to_bgra_batch_dev writes for that frame alone at the same pitches; the clahe_fp_contract
+ * and clahe_float_tables options, REFLECT_101 padding and the fallback for tile grids too wide for the LDS pair table apply as in the
+ * batch form.  Every CLAHE shape runs in one pass: there is no scratch Y plane and no two-pass fallback.
+ * Input side: the rules of mi_*_packed422_frames_dev.  Width is even, height any value >= 1; in_pitch is a multiple of 4; every `in` is
+ * a multiple of 4, at its own alignment modulo 16.  The same input may appear in several entries.  The inputs are never written.
+ * Output side: NO alignment rule -- any `out`, odd addresses included, any out_pitch >= 4*W.  Only the 4*W bytes of each output row are
+ * written, not the pitch padding.  The store-path rule of the batch form is applied PER FRAME: when out_pitch is a multiple of 4, a
+ * frame whose `out` is a multiple of 4 is wide and any other frame of the same call stores bytes, while its neighbours stay wide --
+ * slower, the same bytes out.  mi_ctx_get_stat "packed422_bgra_list_frames_wide" / "packed422_bgra_list_frames_bytes" count the FRAMES
+ * (not calls) of each kind, n_frames in total per call, for calls that were enqueued; list calls do not touch "packed422_bgra_wide" /
+ * "packed422_bgra_bytes", and no existing counter moves.
+ * Overlap: there is no in-place form.  MI_ERR_BAD_ARG when the rows of a frame's image (4*W bytes each) meet the rows of its own input
+ * (compared as address ranges).  Images that overlap each other or ANOTHER frame's input give undefined results and are not checked.
+ * Launches are charged to the same profiling slots as the batch form, per chunk of 128 frames of the list (equalizeHist: one MI_K_HIST,
+ * one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch per chunk).  Never the fused equalizeHist kernel nor the single-launch histogram + LUT
+ * kernel.  Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call
+ * of the same shape as the other device list forms; a captured graph holds the addresses it was captured with.
+ * Errors, MI_ERR_BAD_ARG: a null ctx, a null `frames` with n_frames > 0, a null in / out in any entry, an `in` that is not a multiple
+ * of 4, an odd width (refused even when another size is 0), a negative size, in_pitch < 2*W or not a multiple of 4, out_pitch < 4*W, a
+ * `format` or an `order` other than the two, tiles <= 0, the overlap above.  Sizes and tile grids the batch form refuses (more than 65535
+ * tiles, a height above 65535 with tiles_x > 62, what the planar forms refuse): the status it gives (MI_ERR_UNSUPPORTED).  width,
+ * height or n_frames of 0: MI_OK, nothing written.  Nothing is enqueued unless every frame passes the checks: a bad last entry leaves
+ * the first frames' images untouched. */
+mi_status mi_equalize_hist_packed422_to_bgra_frames_dev(mi_ctx* ctx, const mi_packed422_bgr_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t out_pitch, int format, int order, void* stream);
+mi_status mi_clahe_packed422_to_bgra_frames_dev(mi_ctx* ctx, const mi_packed422_bgr_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t out_pitch, int format, int order,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
 
 /* mi_*_bgr_to_nv12*: interleaved 8-bit BGR (or RGB) images in, pitched NV12 frames out with the luma equalized -- renderer, model output
  * or image reader -> hardware encoder without an I420 intermediate and without an interleave of U and V outside the library.  Per frame
@@ -1333,7 +1422,7 @@ mi_status mi_clahe_yuv420_to_packed422_frames_dev(mi_ctx* ctx, const mi_yuv420_p
  *   legal, as in mi_*_yuv420*.  width, height or n_frames of 0: MI_OK, nothing written (pointers and pitches are not looked at then).
  *   Sizes and tile grids the planar forms refuse: the status they give (MI_ERR_UNSUPPORTED), nothing written.  Nothing is enqueued
  *   unless every check passes.
- * 4:2:0 in, BGRA out is mi_*_yuv420_to_bgra* below.  Not built: packed 4:2:2 in, BGRA out; BGRA in, packed 4:2:2 out; a four-channel mi_bgr_luma_op; a mi_pipe format. */
+ * 4:2:0 in, BGRA out is mi_*_yuv420_to_bgra* below, packed 4:2:2 in, BGRA out mi_*_packed422_to_bgra* above.  Not built: BGRA in, packed 4:2:2 out; a four-channel mi_bgr_luma_op; a mi_pipe format. */
 mi_status mi_equalize_hist_bgra_to_yuv420_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
         const mi_yuv420_planes* out, int width, int height, int n_frames, int order, mi_uv_mode uv_mode, void* stream);
 mi_status mi_clahe_bgra_to_yuv420_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,

@@ -377,6 +377,13 @@ mi_status mi_ctx_synchronize(mi_ctx* c, void* stream)
 // "packed422_bgr_list_frames_wide" / "packed422_bgr_list_frames_bytes" (FRAMES of mi_*_packed422_to_bgr_frames_dev calls whose image was
 // stored 16 bytes per access / byte by byte: out_pitch and the frame's own `out` multiples of 4, or not; counted once the whole call is
 // enqueued, never for a refused call or one with nothing to do),
+// "packed422_bgra_wide" / "packed422_bgra_bytes" (batch and host mi_*_packed422_to_bgra* CALLS whose image was stored 16 bytes per access /
+// byte by byte: the image address, out_pitch and out_frame_stride multiples of 4, or not -- the host form's device image always is; one
+// count per call with work to do, a refused or empty call moves neither),
+// "packed422_bgra_list_frames_wide" / "packed422_bgra_list_frames_bytes" (FRAMES of mi_*_packed422_to_bgra_frames_dev calls by that rule:
+// out_pitch and the frame's own `out` multiples of 4, or not; n_frames in total per call, counted once the whole call is enqueued, never
+// for a refused call or one with nothing to do; list calls do not touch the two per-call counters, and no call of this form moves a
+// packed422_bgr_* or yuv420_bgra_* counter),
 // "bgr_packed422_vec" / "bgr_packed422_bytes" (mi_*_bgr_to_packed422* calls, device and host forms, whose conversion kernel walked 16 x 1
 // pixel groups with 16-byte accesses / macropixels with byte loads: one count per call with work to do, by the walk stage 1 took; a
 // refused or empty call moves neither),
@@ -445,6 +452,10 @@ mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
     if (!strcmp(name, "yuv420_bgra_list_frames_bytes")) { *out = c->yuv420_bgra_list_frames_bytes; return MI_OK; }
     if (!strcmp(name, "packed422_bgr_list_frames_wide")) { *out = c->packed422_bgr_list_frames_wide; return MI_OK; }
     if (!strcmp(name, "packed422_bgr_list_frames_bytes")) { *out = c->packed422_bgr_list_frames_bytes; return MI_OK; }
+    if (!strcmp(name, "packed422_bgra_wide")) { *out = c->packed422_bgra_wide; return MI_OK; }
+    if (!strcmp(name, "packed422_bgra_bytes")) { *out = c->packed422_bgra_bytes; return MI_OK; }
+    if (!strcmp(name, "packed422_bgra_list_frames_wide")) { *out = c->packed422_bgra_list_frames_wide; return MI_OK; }
+    if (!strcmp(name, "packed422_bgra_list_frames_bytes")) { *out = c->packed422_bgra_list_frames_bytes; return MI_OK; }
     if (!strcmp(name, "bgr_packed422_vec")) { *out = c->bgr_packed422_vec; return MI_OK; }
     if (!strcmp(name, "bgr_packed422_bytes")) { *out = c->bgr_packed422_bytes; return MI_OK; }
     if (!strcmp(name, "yuv420_packed422_onepass")) { *out = c->yuv420_packed422_onepass; return MI_OK; }

@@ -187,6 +187,11 @@ struct mi_ctx {
     unsigned long long packed422_bgr_list_frames_wide = 0, packed422_bgr_list_frames_bytes = 0;   // statistics "packed422_bgr_list_frames_wide" /
                                                                         // "packed422_bgr_list_frames_bytes": FRAMES of mi_*_packed422_to_bgr_frames_dev calls whose image
                                                                         // left as 16-byte / as byte stores, each by its own address
+    unsigned long long packed422_bgra_wide = 0, packed422_bgra_bytes = 0;   // statistics "packed422_bgra_wide" / "packed422_bgra_bytes": batch and host
+                                                                        // mi_*_packed422_to_bgra* CALLS by the store path of their launch (packed422_bgra_frame_wide)
+    unsigned long long packed422_bgra_list_frames_wide = 0, packed422_bgra_list_frames_bytes = 0;   // statistics "packed422_bgra_list_frames_wide" /
+                                                                        // "packed422_bgra_list_frames_bytes": FRAMES of mi_*_packed422_to_bgra_frames_dev calls by that
+                                                                        // rule, each by its own address
     uint64_t bgr_packed422_vec = 0, bgr_packed422_bytes = 0;            // statistics "bgr_packed422_vec" / "bgr_packed422_bytes": mi_*_bgr_to_packed422* calls by the
                                                                         // walk their conversion kernel took (16 x 1 pixel groups / macropixels with byte loads)
     uint64_t yuv420_packed422_onepass = 0, yuv420_packed422_twopass = 0;   // statistics "yuv420_packed422_onepass" / "yuv420_packed422_twopass": mi_*_yuv420_to_packed422*

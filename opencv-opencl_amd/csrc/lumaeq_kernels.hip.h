@@ -50,6 +50,8 @@
 //   kernels/yuv420_bgra.hip.h      the pixel-writing stages of 4:2:0 in, four-channel BGRA / RGBA (CV_8UC4, A = 255) out: LUT apply / CLAHE
 //                                  blend + decode, one body each for NV12 and planar chroma, for a strided batch and a list of
 //                                  {y, c0, c1, out} addresses; every pixel one dword, a 16-pixel group four 16-byte stores
+//   kernels/packed422_bgra.hip.h   the pixel-writing stages of packed 4:2:2 in, four-channel BGRA / RGBA (CV_8UC4, A = 255) out: the bodies of
+//                                  packed422_bgr.hip.h with that dword-per-pixel store, every row with its own chroma
 #pragma once
 #include "kernels/common.hip.h"
 #include "kernels/equalize.hip.h"
@@ -72,3 +74,4 @@
 #include "kernels/packed422_bgr.hip.h"
 #include "kernels/bgra_yuv420.hip.h"
 #include "kernels/yuv420_bgra.hip.h"
+#include "kernels/packed422_bgra.hip.h"

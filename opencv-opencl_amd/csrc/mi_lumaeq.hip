@@ -67,5 +67,7 @@ using namespace mi;
 #include "host/bgra_yuv420_frames.inc.hpp"  // ... as a list of pitched device frames (a surface pool in, an encoder's frame pool out)
 #include "host/yuv420_bgra.inc.hpp"    // planar 4:2:0 (I420 / YV12) or NV12 in, four-channel BGRA / RGBA (CV_8UC4, A = 255) out in the pass that maps the luma (decoder -> display surface / texture)
 #include "host/yuv420_bgra_frames.inc.hpp"  // ... as a list of pitched device frames (a decoder's frame pool in, a surface pool out)
+#include "host/packed422_bgra.inc.hpp"  // packed 4:2:2 (YUY2 / UYVY) in, four-channel BGRA / RGBA (CV_8UC4, A = 255) out, every row with its own chroma (capture card -> display surface / texture)
+#include "host/packed422_bgra_frames.inc.hpp"  // ... as a list of pitched device frames (a capture device's buffer pool in, a surface pool out)
 #include "host/pipe.inc.hpp"
 #include "host/diff.inc.hpp"

@@ -589,6 +589,24 @@ inline void claheYUV420ToBGRA(const YUV420View& in, unsigned char* out, size_t o
     detail::check(c, mi_clahe_yuv420_to_bgra(c, &a, out, outStep, width, height, (int)order, clipLimit, tiles.width, tiles.height),
                   "mi_clahe_yuv420_to_bgra");
 }
+// The capture edge of the same image: one packed 4:2:2 host frame (FMT_YUY2 exactly Y0 U Y1 V, FMT_UYVY exactly U Y0 V Y1; rows of 2*W
+// bytes at inPitch, a multiple of 4) in, an interleaved CV_8UC4 image (BGRA, or RGBA; A = 255) out: cv::extractChannel +
+// cv::equalizeHist / CLAHE::apply + cv::insertChannel + cv::cvtColor(COLOR_YUV2BGRA_YUY2 / _UYVY), every row with its own chroma: a
+// capture card's frame -> a display surface, a texture or a GUI image.  `out`: H rows of 4*W bytes at outStep >= 4*W, any address.
+inline void equalizeHistPacked422ToBGRA(const unsigned char* in, size_t inPitch, unsigned char* out, size_t outStep, int width, int height,
+                                        PackedFormat format = FMT_YUY2, ChannelOrder order = ORDER_BGR)
+{
+    mi_ctx* c = detail::thread_ctx();
+    detail::check(c, mi_equalize_hist_packed422_to_bgra(c, in, inPitch, out, outStep, width, height, (int)format, (int)order),
+                  "mi_equalize_hist_packed422_to_bgra");
+}
+inline void clahePacked422ToBGRA(const unsigned char* in, size_t inPitch, unsigned char* out, size_t outStep, int width, int height,
+                                 double clipLimit, Size tiles, PackedFormat format = FMT_YUY2, ChannelOrder order = ORDER_BGR)
+{
+    mi_ctx* c = detail::thread_ctx();
+    detail::check(c, mi_clahe_packed422_to_bgra(c, in, inPitch, out, outStep, width, height, (int)format, (int)order, clipLimit,
+                                                tiles.width, tiles.height), "mi_clahe_packed422_to_bgra");
+}
 // The opposite edge: one interleaved CV_8UC3 host image (BGR, or RGB) at inStep >= 3*W in, the planes of the view out:
 // cv::cvtColor(COLOR_BGR2YUV_I420) + cv::equalizeHist / CLAHE::apply on the Y plane, U into out.c0 and V into out.c1 (UV_COPY) or chroma
 // 128 (UV_FILL128): a renderer's or a model's image -> the three pitched planes a software encoder takes, without an NV12 frame in

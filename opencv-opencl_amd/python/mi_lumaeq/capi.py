@@ -57,6 +57,9 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_packed422_to_bgr_batch_dev", "mi_clahe_packed422_to_bgr_batch_dev",
     "mi_equalize_hist_packed422_to_bgr", "mi_clahe_packed422_to_bgr",
     "mi_equalize_hist_packed422_to_bgr_frames_dev", "mi_clahe_packed422_to_bgr_frames_dev",
+    "mi_equalize_hist_packed422_to_bgra_batch_dev", "mi_clahe_packed422_to_bgra_batch_dev",
+    "mi_equalize_hist_packed422_to_bgra", "mi_clahe_packed422_to_bgra",
+    "mi_equalize_hist_packed422_to_bgra_frames_dev", "mi_clahe_packed422_to_bgra_frames_dev",
     "mi_equalize_hist_nv12_to_bgr_batch_dev", "mi_clahe_nv12_to_bgr_batch_dev", "mi_equalize_hist_nv12_to_bgr", "mi_clahe_nv12_to_bgr",
     "mi_equalize_hist_nv12_to_bgr_frames_dev", "mi_clahe_nv12_to_bgr_frames_dev",
     "mi_equalize_hist_bgr_to_nv12_batch_dev", "mi_clahe_bgr_to_nv12_batch_dev", "mi_equalize_hist_bgr_to_nv12", "mi_clahe_bgr_to_nv12",
@@ -309,6 +312,12 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_packed422_to_bgr.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, d, i, i]
     L.mi_equalize_hist_packed422_to_bgr_frames_dev.argtypes = [vp, C.POINTER(Packed422BgrFrameDev), i, i, i, sz, sz, i, i, vp]
     L.mi_clahe_packed422_to_bgr_frames_dev.argtypes = [vp, C.POINTER(Packed422BgrFrameDev), i, i, i, sz, sz, i, i, d, i, i, vp]
+    L.mi_equalize_hist_packed422_to_bgra_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, vp]
+    L.mi_clahe_packed422_to_bgra_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_packed422_to_bgra.argtypes = [vp, vp, sz, vp, sz, i, i, i, i]
+    L.mi_clahe_packed422_to_bgra.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, d, i, i]
+    L.mi_equalize_hist_packed422_to_bgra_frames_dev.argtypes = [vp, C.POINTER(Packed422BgrFrameDev), i, i, i, sz, sz, i, i, vp]
+    L.mi_clahe_packed422_to_bgra_frames_dev.argtypes = [vp, C.POINTER(Packed422BgrFrameDev), i, i, i, sz, sz, i, i, d, i, i, vp]
     L.mi_equalize_hist_nv12_to_bgr_batch_dev.argtypes = [vp, vp, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, vp]
     L.mi_clahe_nv12_to_bgr_batch_dev.argtypes = [vp, vp, sz, vp, sz, sz, vp, sz, sz, i, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_nv12_to_bgr.argtypes = [vp, vp, vp, sz, i, i, i]
@@ -509,17 +518,17 @@ def _packed422_nv12_list(inputs, y_outputs, uv_outputs, width, in_pitch, y_pitch
     return arr, len(inputs), ip, yp, up
 
 
-def _packed422_bgr_list(inputs, outs, width, in_pitch, out_pitch, what):
+def _packed422_bgr_list(inputs, outs, width, in_pitch, out_pitch, what, px=3):
     """inputs / outs: sequences of equal length (torch CUDA tensors or raw device addresses).  Returns the mi_packed422_bgr_frame_dev
     array, its length and the two pitches (given, else the row stride of the tensors -- H x pitch frames, H x 3W or H x W x 3 images --
-    else 2 * width for the frames and 3 * width for the images)."""
+    else 2 * width for the frames and 3 * width for the images).  px = 4: four-channel images (H x 4W or H x W x 4, 4 * width)."""
     inputs, outs = list(inputs), list(outs)
     if len(inputs) != len(outs):
         raise MiError(1, what, f"{len(inputs)} inputs but {len(outs)} images")
     ip = _plane_pitch(inputs, in_pitch, 2 * int(width), what)
     # an H x W x 3 image's rows are its first axis: seen as H x 3W for the pitch
     rows = [o if isinstance(o, int) or o is None or o.dim() != 3 else o[:, :, 0] for o in outs]
-    op = int(out_pitch) if out_pitch is not None else _plane_pitch(rows, None, 3 * int(width), what)
+    op = int(out_pitch) if out_pitch is not None else _plane_pitch(rows, None, px * int(width), what)
     arr = (Packed422BgrFrameDev * max(1, len(inputs)))()
     for k in range(len(inputs)):
         arr[k] = Packed422BgrFrameDev(_dptr(inputs[k]), _dptr(outs[k]))
@@ -1073,6 +1082,80 @@ class Context:
         self._chk(self._L.mi_clahe_packed422_to_bgr(self._h, frame.ctypes.data, _step(frame), out.ctypes.data, step, int(width),
                                                   int(frame.shape[0]), int(fmt), int(order), float(clip_limit), int(tiles_x),
                                                   int(tiles_y)), "mi_clahe_packed422_to_bgr")
+        return out
+
+    # ---- packed 4:2:2 in, four-channel BGRA / RGBA (CV_8UC4, A = 255) out: the methods above with a pixel of four bytes ----
+    def equalize_hist_packed422_to_bgra_batch_dev(self, d_in, d_out, width, height, n_frames, fmt=FMT_YUY2, order=ORDER_BGR,
+                                                  in_pitch=None, in_frame=None, out_pitch=None, out_frame=None, stream=0):
+        """mi_equalize_hist_packed422_to_bgra_batch_dev: n_frames packed frames in, interleaved BGRA / RGBA images out (torch tensors or
+        raw addresses).  fmt says the chroma order too: FMT_YUY2 is Y0 U Y1 V, FMT_UYVY is U Y0 V Y1.  Tight layouts are the defaults:
+        in_pitch 2*W, in_frame in_pitch * H, out_pitch 4*W, out_frame out_pitch * H."""
+        ip = 2 * int(width) if in_pitch is None else int(in_pitch)
+        fi = ip * int(height) if in_frame is None else int(in_frame)
+        op = 4 * int(width) if out_pitch is None else int(out_pitch)
+        fo = op * int(height) if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_equalize_hist_packed422_to_bgra_batch_dev(self._h, _dptr(d_in), ip, fi, _dptr(d_out), op, fo, int(width),
+                                                                     int(height), int(n_frames), int(fmt), int(order), stream),
+                  "mi_equalize_hist_packed422_to_bgra_batch_dev")
+
+    def clahe_packed422_to_bgra_batch_dev(self, d_in, d_out, width, height, n_frames, fmt=FMT_YUY2, order=ORDER_BGR, clip_limit=2.0,
+                                          tiles_x=8, tiles_y=8, in_pitch=None, in_frame=None, out_pitch=None, out_frame=None, stream=0):
+        """mi_clahe_packed422_to_bgra_batch_dev; arguments as equalize_hist_packed422_to_bgra_batch_dev, plus the CLAHE parameters."""
+        ip = 2 * int(width) if in_pitch is None else int(in_pitch)
+        fi = ip * int(height) if in_frame is None else int(in_frame)
+        op = 4 * int(width) if out_pitch is None else int(out_pitch)
+        fo = op * int(height) if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_clahe_packed422_to_bgra_batch_dev(self._h, _dptr(d_in), ip, fi, _dptr(d_out), op, fo, int(width), int(height),
+                                                             int(n_frames), int(fmt), int(order), float(clip_limit), int(tiles_x),
+                                                             int(tiles_y), stream), "mi_clahe_packed422_to_bgra_batch_dev")
+
+    def equalize_hist_packed422_to_bgra_frames(self, inputs, outs, width, height, fmt=FMT_YUY2, order=ORDER_BGR, in_pitch=None,
+                                               out_pitch=None, stream=0):
+        """mi_equalize_hist_packed422_to_bgra_frames_dev.  inputs: the packed frames, outs: the images, each its own buffer -- lists of
+        torch CUDA tensors or raw device addresses, one entry per frame.  A pitch left at None is the row stride of the 2-D tensors of
+        that list (H x W x 4 images: of their first axis), or the tight one (2 * width; 4 * width)."""
+        arr, n, ip, op = _packed422_bgr_list(inputs, outs, width, in_pitch, out_pitch, "equalize_hist_packed422_to_bgra_frames", px=4)
+        self._chk(self._L.mi_equalize_hist_packed422_to_bgra_frames_dev(self._h, arr, n, int(width), int(height), ip, op, int(fmt),
+                                                                      int(order), stream),
+                  "mi_equalize_hist_packed422_to_bgra_frames_dev")
+
+    def clahe_packed422_to_bgra_frames(self, inputs, outs, width, height, fmt=FMT_YUY2, order=ORDER_BGR, clip_limit=2.0, tiles_x=8,
+                                       tiles_y=8, in_pitch=None, out_pitch=None, stream=0):
+        """mi_clahe_packed422_to_bgra_frames_dev; arguments as equalize_hist_packed422_to_bgra_frames, plus the CLAHE parameters."""
+        arr, n, ip, op = _packed422_bgr_list(inputs, outs, width, in_pitch, out_pitch, "clahe_packed422_to_bgra_frames", px=4)
+        self._chk(self._L.mi_clahe_packed422_to_bgra_frames_dev(self._h, arr, n, int(width), int(height), ip, op, int(fmt), int(order),
+                                                              float(clip_limit), int(tiles_x), int(tiles_y), stream),
+                  "mi_clahe_packed422_to_bgra_frames_dev")
+
+    def _packed_bgra_host(self, frame, width, out, name):
+        frame = self._packed_host(frame, width, name)
+        h = frame.shape[0]
+        if out is None:
+            out = np.empty((h, max(int(width), 0), 4), np.uint8)
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.ndim != 3 or out.shape[2] != 4:
+            raise MiError(2, name, "expected an HxWx4 uint8 ndarray (CV_8UC4)")
+        if out.size and (out.strides[2] != 1 or out.strides[1] != 4):
+            raise MiError(1, name, "pixels must be interleaved")
+        if out.shape[:2] != (h, width):
+            raise MiError(1, name, "out must be an H x W x 4 uint8 array (rows may be padded)")
+        return frame, out, (int(out.strides[0]) if h > 1 else max(int(out.strides[0]), 4 * int(width)))
+
+    def equalize_hist_packed422_to_bgra(self, frame: np.ndarray, width: int, fmt: int = FMT_YUY2, order: int = ORDER_BGR,
+                                        out: np.ndarray | None = None) -> np.ndarray:
+        """mi_equalize_hist_packed422_to_bgra on a host frame: an H x pitch-bytes uint8 array (pitch >= 2*W) in, the H x W x 4 image
+        out -- `out` when given (a view with padded rows or at an odd address included), else a new tight array."""
+        frame, out, step = self._packed_bgra_host(frame, int(width), out, "equalize_hist_packed422_to_bgra")
+        self._chk(self._L.mi_equalize_hist_packed422_to_bgra(self._h, frame.ctypes.data, _step(frame), out.ctypes.data, step, int(width),
+                                                           int(frame.shape[0]), int(fmt), int(order)), "mi_equalize_hist_packed422_to_bgra")
+        return out
+
+    def clahe_packed422_to_bgra(self, frame: np.ndarray, width: int, fmt: int = FMT_YUY2, order: int = ORDER_BGR,
+                                clip_limit: float = 2.0, tiles_x: int = 8, tiles_y: int = 8, out: np.ndarray | None = None) -> np.ndarray:
+        """mi_clahe_packed422_to_bgra; arguments as equalize_hist_packed422_to_bgra, plus the CLAHE parameters."""
+        frame, out, step = self._packed_bgra_host(frame, int(width), out, "clahe_packed422_to_bgra")
+        self._chk(self._L.mi_clahe_packed422_to_bgra(self._h, frame.ctypes.data, _step(frame), out.ctypes.data, step, int(width),
+                                                   int(frame.shape[0]), int(fmt), int(order), float(clip_limit), int(tiles_x),
+                                                   int(tiles_y)), "mi_clahe_packed422_to_bgra")
         return out
 
     # ---- NV12 in, interleaved BGR / RGB out in the pass that maps the luma ----
