@@ -1183,7 +1183,8 @@ mi_status mi_clahe_bgr_to_yuv420_frames_dev(mi_ctx* ctx, const mi_bgr_yuv420_fra
  *   of 4; an `order` other than the two; a `format` other than the two; a bad uv_mode; tiles <= 0.  width, height or n_frames of 0:
  *   MI_OK, nothing written (pointers and pitches are not looked at then).  Sizes and tile grids the packed or planar forms refuse:
  *   MI_ERR_UNSUPPORTED, nothing written.  Nothing is enqueued unless every check passes.
- * The frame-list form mi_*_bgr_to_packed422_frames_dev is described below.  Not built: YVYU / VYUY, BGRA input, chroma averaging. */
+ * The frame-list form mi_*_bgr_to_packed422_frames_dev is described below; four-channel (BGRA / RGBA, CV_8UC4) input is
+ * mi_*_bgra_to_packed422* further below.  Not built: YVYU / VYUY, chroma averaging. */
 mi_status mi_equalize_hist_bgr_to_packed422_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
         void* d_out, size_t out_pitch, size_t out_frame_stride,
         int width, int height, int n_frames, int order, int format, mi_uv_mode uv_mode, void* stream);
@@ -1422,7 +1423,7 @@ mi_status mi_clahe_yuv420_to_packed422_frames_dev(mi_ctx* ctx, const mi_yuv420_p
  *   legal, as in mi_*_yuv420*.  width, height or n_frames of 0: MI_OK, nothing written (pointers and pitches are not looked at then).
  *   Sizes and tile grids the planar forms refuse: the status they give (MI_ERR_UNSUPPORTED), nothing written.  Nothing is enqueued
  *   unless every check passes.
- * 4:2:0 in, BGRA out is mi_*_yuv420_to_bgra* below, packed 4:2:2 in, BGRA out mi_*_packed422_to_bgra* above.  Not built: BGRA in, packed 4:2:2 out; a four-channel mi_bgr_luma_op; a mi_pipe format. */
+ * 4:2:0 in, BGRA out is mi_*_yuv420_to_bgra* below, packed 4:2:2 in, BGRA out mi_*_packed422_to_bgra* above, BGRA in, packed 4:2:2 out mi_*_bgra_to_packed422* below.  Not built: a four-channel mi_bgr_luma_op; a mi_pipe format. */
 mi_status mi_equalize_hist_bgra_to_yuv420_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
         const mi_yuv420_planes* out, int width, int height, int n_frames, int order, mi_uv_mode uv_mode, void* stream);
 mi_status mi_clahe_bgra_to_yuv420_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
@@ -1484,6 +1485,109 @@ mi_status mi_equalize_hist_bgra_to_yuv420_frames_dev(mi_ctx* ctx, const mi_bgr_y
         int width, int height, size_t in_pitch, size_t y_pitch, size_t c_pitch, int chroma, int order, mi_uv_mode uv_mode, void* stream);
 mi_status mi_clahe_bgra_to_yuv420_frames_dev(mi_ctx* ctx, const mi_bgr_yuv420_frame_dev* frames, int n_frames,
         int width, int height, size_t in_pitch, size_t y_pitch, size_t c_pitch, int chroma, int order, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
+/* mi_*_bgra_to_packed422*: interleaved 8-bit FOUR-channel images (CV_8UC4: BGRA / BGRX, or RGBA / RGBX) in, packed 4:2:2 frames
+ * (YUY2 / UYVY) out with the luma equalized -- render target, swap-chain image, screen or window capture, GL / Vulkan interop buffer
+ * -> SDI / HDMI playout card, v4l2 output or loopback device, virtual camera, in one pass over the 4 B/px surface: without slicing the
+ * first three channels into a contiguous scratch batch outside the library for mi_*_bgr_to_packed422_batch_dev, and without an NV12
+ * intermediate (which has dropped every second chroma row).  The signatures are those of mi_*_bgr_to_packed422*.
+ * Bytes: the output is byte for byte what mi_*_bgr_to_packed422* writes for the image with its fourth byte removed:
+ *   luma   : Y = bt601_y(b, g, r) of every pixel, then cv::equalizeHist / CLAHE::apply on the W x H luma plane; the clahe_fp_contract
+ *            option is honoured and REFLECT_101 padding applies when the tile grid does not divide the frame.
+ *   chroma : MI_UV_COPY: U and V of macropixel (k, y) are bt601_uv of the LEFT pixel (2k, y) of that row, without averaging.
+ *            MI_UV_FILL128: every chroma byte 128, the chroma arithmetic is skipped.
+ *   MI_FMT_YUY2 writes exactly Y0 U Y1 V, MI_FMT_UYVY exactly U Y0 V Y1.  MI_ORDER_BGR reads B, G, R, X per pixel, MI_ORDER_RGB reads
+ *   R, G, B, X.  The fourth byte X (alpha or padding) is read with its pixel and takes part in nothing.
+ *   input  : frame f at d_in + f * in_frame_stride, H rows of 4*W bytes at in_pitch >= 4*W, at any address.  The input is never written.
+ *   output : frame f at d_out + f * out_frame_stride, H rows of 2*W bytes at out_pitch >= 2*W; d_out, out_pitch and out_frame_stride
+ *            are multiples of 4 (the packed forms' rule).  Only the 2*W bytes of each output row are written: not the pitch padding,
+ *            not the gaps between frames.
+ * Width is even; height is any value >= 1, odd heights are legal.  Every CLAHE shape runs in one pass.  The limits on sizes and tile
+ *   grids are those of mi_*_bgr_to_packed422*, with the same statuses.
+ * Alignment: a call moves 16 pixels of one row per lane (four 16-byte loads, every dword one pixel, and two 16-byte stores) when
+ *   W % 16 == 0 and d_in, in_pitch, in_frame_stride, d_out, out_pitch and out_frame_stride are all multiples of 16.  Otherwise it
+ *   processes one macropixel per lane with byte loads at 8*mx + {0,1,2} and 8*mx + 4 + {0,1,2} and one aligned dword store -- slower,
+ *   the same bytes out.
+ * Two stages per chunk of 256 frames, as in mi_*_bgr_to_packed422_batch_dev.  Stage 1 converts: ONE kernel (charged to MI_K_COLOR)
+ *   reads the image once, writes the packed frame with unequalized luma into d_out and, for equalizeHist, counts the luma bytes it has
+ *   just produced.  Stage 2 is exactly that form's: the packed form's own kernels IN PLACE on the output frame, the chroma bytes kept
+ *   whatever uv_mode is: equalizeHist one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch (no MI_K_HIST launch); CLAHE exactly what
+ *   mi_clahe_packed422_batch_dev launches for those frames in place.  Never the fused equalizeHist kernel nor the single-launch
+ *   histogram + LUT kernel: option two_kernel_max_frames does not apply.  Bytes moved per pixel: equalizeHist 4 + 2 + 2 + 2 = 10,
+ *   CLAHE 6 + 2 + 4 = 12.  Between the stages d_out holds the unequalized luma.
+ * Counters (mi_ctx_get_stat): "bgra_packed422_vec" / "bgra_packed422_bytes", one count per call by the walk stage 1 took (16-pixel
+ *   groups / macropixels).  A device or host call with work to do moves exactly one of them; a call that returns an error or has a
+ *   zero size moves neither.  No call of this form moves a bgr_packed422* counter.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of the
+ *   same shape as the other batched device forms.
+ * mi_equalize_hist_bgra_to_packed422 / mi_clahe_bgra_to_packed422: ONE CV_8UC4 image in host memory at in_step >= 4*W, at any address,
+ *   in; one packed frame in host memory at any address and any out_pitch >= 2*W out.  Synchronous; the image is staged in like
+ *   mi_*_bgra_to_yuv420's, with a row of 4*W bytes, and the frame comes back like mi_*_bgr_to_packed422's (frames in pinned memory that
+ *   are tight are DMA'd as they are, everything else goes through the context's pinned staging).  On the device the frame is tight and
+ *   16-byte aligned, so a W % 16 == 0 image takes the 16-pixel groups.  Whatever the call returns, no copy on the caller's memory is in
+ *   flight any more when it returns.  W*H > 0x7fffffff / 4: MI_ERR_UNSUPPORTED.
+ * There is no in-place form: d_out == d_in is MI_ERR_BAD_ARG; any other overlap of input and output is undefined, not checked.
+ * Errors, MI_ERR_BAD_ARG: a null ctx, d_in or d_out; an odd width (refused even when another size is 0, as in the packed forms); a
+ *   negative size; in_pitch < 4*W; out_pitch < 2*W; a d_out, out_pitch or out_frame_stride of the device form that is not a multiple
+ *   of 4; an `order` other than the two; a `format` other than the two; a bad uv_mode; tiles <= 0.  width, height or n_frames of 0:
+ *   MI_OK, nothing written (pointers and pitches are not looked at then).  Sizes and tile grids the packed or planar forms refuse:
+ *   MI_ERR_UNSUPPORTED, nothing written.  Nothing is enqueued unless every check passes.
+ * The frame-list form mi_*_bgra_to_packed422_frames_dev is described below.  Out of scope, not built: YVYU / VYUY, chroma averaging,
+ * a use for the alpha byte, P010 / 16-bit. */
+mi_status mi_equalize_hist_bgra_to_packed422_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        void* d_out, size_t out_pitch, size_t out_frame_stride,
+        int width, int height, int n_frames, int order, int format, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_bgra_to_packed422_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        void* d_out, size_t out_pitch, size_t out_frame_stride,
+        int width, int height, int n_frames, int order, int format, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
+mi_status mi_equalize_hist_bgra_to_packed422(mi_ctx* ctx, const uint8_t* in, size_t in_step, uint8_t* out, size_t out_pitch,
+        int width, int height, int order, int format, mi_uv_mode uv_mode);
+mi_status mi_clahe_bgra_to_packed422(mi_ctx* ctx, const uint8_t* in, size_t in_step, uint8_t* out, size_t out_pitch,
+        int width, int height, int order, int format, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
+/* mi_*_bgra_to_packed422_frames_dev: the same conversion on a LIST of device frames, each at its own two addresses -- a pool of CV_8UC4
+ * surfaces in (a renderer, a compositor or a capture API hands over one surface per frame), a playout card's, a v4l2 output queue's or
+ * a virtual camera's buffer pool out.  `frames` is a host array of n_frames entries of the existing mi_bgr_packed422_frame_dev
+ * {in, out}, read only during the call; the pointers in it are device pointers on the context's device.  No new struct, enum or
+ * version.
+ * Shape: all frames of one call share width, height, the pair of pitches (bytes between rows), order, format and uv_mode; each has its
+ *   own two addresses.  There are no per-frame pitches.
+ *   in  : H rows of 4*W bytes at in_pitch >= 4*W, at any address -- B, G, R, X per pixel (MI_ORDER_BGR) or R, G, B, X (MI_ORDER_RGB);
+ *         X takes no part.  The images are never written.
+ *   out : H rows of 2*W bytes at out_pitch >= 2*W; every `out` and out_pitch are multiples of 4 (the packed forms' rule).  Only the
+ *         2*W bytes of each output row are written: not the pitch padding, nothing before or behind a frame.
+ * Bytes: per frame the output is byte for byte exactly what mi_*_bgra_to_packed422_batch_dev writes for that frame alone at the same
+ *   pitches; width is even, odd heights are legal, and the limits on sizes and tile grids are the batch form's, with the same statuses.
+ * Alignment: beyond the multiples of 4 above, none is required.  The shape allows 16-pixel groups (four 16-byte loads, two 16-byte
+ *   stores per lane) when W % 16 == 0 and in_pitch and out_pitch are multiples of 16; a frame then takes the groups when its own `in`
+ *   and `out` are both multiples of 16, and any other frame of the same call processes one macropixel per lane with byte loads and one
+ *   aligned dword store while its neighbours stay vectorised -- slower, the same bytes out.  One rule, which the kernel decides by and
+ *   the host counts by.
+ * Stages, per chunk of 128 frames of the list (not the batch form's 256): stage 1 is ONE launch charged to MI_K_COLOR that converts
+ *   into the caller's frames and, for equalizeHist, counts the luma bytes it has just produced.  Stage 2 maps the luma IN PLACE on the
+ *   chunk's output frames, the chroma bytes kept whatever uv_mode is: equalizeHist one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch (no
+ *   MI_K_HIST launch; never the fused equalizeHist kernel nor the single-launch histogram + LUT kernel, option two_kernel_max_frames
+ *   does not apply); CLAHE exactly what mi_clahe_packed422_frames_dev launches in place on those frames, every shape in one pass.
+ *   Between the stages a frame's `out` holds the unequalized luma.
+ * Counters (mi_ctx_get_stat): "bgra_packed422_list_frames_vec" / "bgra_packed422_list_frames_bytes" count the FRAMES (not calls) of
+ *   list calls by the walk their stage-1 kernel took: 16-pixel groups / macropixels.  A list call moves the two by n_frames in total
+ *   and does not touch "bgra_packed422_vec" / "bgra_packed422_bytes" nor any bgr_packed422* counter.  A call that returns an error or
+ *   has nothing to do moves none.
+ * Overlap: there is no in-place form.  MI_ERR_BAD_ARG when the rows of a frame's image (4*W bytes each) meet the rows of its own
+ *   output frame (compared as address ranges).  The same image may appear in several entries (inputs are only read).  Outputs that
+ *   overlap ANOTHER frame's image or output give undefined results and are not checked.
+ * Errors, MI_ERR_BAD_ARG: a null ctx; a null `frames` with n_frames > 0; a null `in` or `out` in any entry; an `out` in any entry or
+ *   an out_pitch that is not a multiple of 4; an `order` other than the two; a `format` other than the two; a bad uv_mode; a negative
+ *   size; an odd width (refused even when another size is 0, as in the batch form); in_pitch < 4*W; out_pitch < 2*W; tiles <= 0; the
+ *   overlap above.  Sizes and tile grids the packed or planar forms refuse: MI_ERR_UNSUPPORTED.  width, height or n_frames of 0: MI_OK,
+ *   nothing written (the entries and the pitches are not looked at then; n_frames == 0 with a null list is MI_OK).  Nothing is enqueued
+ *   unless every frame passes the checks: a bad last entry leaves the earlier frames' outputs untouched.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of
+ *   the same shape as the other device list forms; a captured graph holds the addresses it was captured with. */
+mi_status mi_equalize_hist_bgra_to_packed422_frames_dev(mi_ctx* ctx, const mi_bgr_packed422_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t out_pitch, int order, int format, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_bgra_to_packed422_frames_dev(mi_ctx* ctx, const mi_bgr_packed422_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t out_pitch, int order, int format, mi_uv_mode uv_mode,
         double clip_limit, int tiles_x, int tiles_y, void* stream);
 /* mi_*_yuv420_to_bgra*: 4:2:0 frames described by mi_yuv420_planes in -- interleaved chroma (NV12: a hardware decoder's surfaces) or
  * planar chroma (I420 / YV12: ffmpeg yuv420p, libvpx, dav1d) -- interleaved 8-bit FOUR-channel images (CV_8UC4: BGRA, or RGBA) out, in

@@ -400,7 +400,14 @@ mi_status mi_ctx_synchronize(mi_ctx* c, void* stream)
 // `y` -- the caller's, or the scratch plane's in the two-pass CLAHE fallback -- and `out` are multiples of 16 and, under MI_UV_COPY, its
 // c0 a multiple of 16 (interleaved) or its c0 and c1 multiples of 8 (planar), or not; n_frames in total per call, counted once the whole
 // call is enqueued, never for a refused call or one with nothing to do.  A list call moves one of "yuv420_packed422_onepass" /
-// "yuv420_packed422_twopass" and does not touch "yuv420_packed422_vec" / "yuv420_packed422_bytes").
+// "yuv420_packed422_twopass" and does not touch "yuv420_packed422_vec" / "yuv420_packed422_bytes"),
+// "bgra_packed422_vec" / "bgra_packed422_bytes" (mi_*_bgra_to_packed422* calls, batch and host forms, whose conversion kernel walked
+// 16 x 1 pixel groups with 16-byte accesses / macropixels with byte loads: one count per call with work to do; a refused or empty call
+// moves neither),
+// "bgra_packed422_list_frames_vec" / "bgra_packed422_list_frames_bytes" (FRAMES of mi_*_bgra_to_packed422_frames_dev calls by that walk,
+// each by its own two addresses: the shape allows the groups and the frame's `in` and `out` are multiples of 16, or not; n_frames in
+// total per call, counted once the whole call is enqueued, never for a refused call or one with nothing to do; list calls do not touch
+// the two per-call counters, and no call of this form moves a bgr_packed422* counter).
 mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
 {
     ENTER(c);
@@ -466,6 +473,10 @@ mi_status mi_ctx_get_stat(mi_ctx* c, const char* name, uint64_t* out)
     if (!strcmp(name, "bgr_packed422_list_frames_bytes")) { *out = c->bgr_packed422_list_frames_bytes; return MI_OK; }
     if (!strcmp(name, "yuv420_packed422_list_frames_vec")) { *out = c->yuv420_packed422_list_frames_vec; return MI_OK; }
     if (!strcmp(name, "yuv420_packed422_list_frames_bytes")) { *out = c->yuv420_packed422_list_frames_bytes; return MI_OK; }
+    if (!strcmp(name, "bgra_packed422_vec")) { *out = c->bgra_packed422_vec; return MI_OK; }
+    if (!strcmp(name, "bgra_packed422_bytes")) { *out = c->bgra_packed422_bytes; return MI_OK; }
+    if (!strcmp(name, "bgra_packed422_list_frames_vec")) { *out = c->bgra_packed422_list_frames_vec; return MI_OK; }
+    if (!strcmp(name, "bgra_packed422_list_frames_bytes")) { *out = c->bgra_packed422_list_frames_bytes; return MI_OK; }
     return fail(c, MI_ERR_BAD_ARG, "unknown stat");
 }
 

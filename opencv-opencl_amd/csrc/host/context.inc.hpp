@@ -204,6 +204,11 @@ struct mi_ctx {
     unsigned long long yuv420_packed422_list_frames_vec = 0, yuv420_packed422_list_frames_bytes = 0;   // statistics "yuv420_packed422_list_frames_vec" /
                                                                         // "yuv420_packed422_list_frames_bytes": FRAMES of mi_*_yuv420_to_packed422_frames_dev calls by
                                                                         // the walk their pixel-writing kernel took (16 x 2 groups / 2 x 2 blocks), each by its own addresses
+    unsigned long long bgra_packed422_vec = 0, bgra_packed422_bytes = 0;   // statistics "bgra_packed422_vec" / "bgra_packed422_bytes": batch and host
+                                                                        // mi_*_bgra_to_packed422* calls by the walk their conversion kernel took (16 x 1 groups / macropixels)
+    unsigned long long bgra_packed422_list_frames_vec = 0, bgra_packed422_list_frames_bytes = 0;   // statistics "bgra_packed422_list_frames_vec" /
+                                                                        // "bgra_packed422_list_frames_bytes": FRAMES of mi_*_bgra_to_packed422_frames_dev calls by that
+                                                                        // walk, each by its own two addresses
 };
 
 namespace {

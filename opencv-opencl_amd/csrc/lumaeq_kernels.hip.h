@@ -52,6 +52,8 @@
 //                                  {y, c0, c1, out} addresses; every pixel one dword, a 16-pixel group four 16-byte stores
 //   kernels/packed422_bgra.hip.h   the pixel-writing stages of packed 4:2:2 in, four-channel BGRA / RGBA (CV_8UC4, A = 255) out: the bodies of
 //                                  packed422_bgr.hip.h with that dword-per-pixel store, every row with its own chroma
+//   kernels/bgra_packed422.hip.h   stage 1 of four-channel BGRA / RGBA (CV_8UC4) in, packed 4:2:2 (YUY2 / UYVY) out: one body for a strided
+//                                  batch and a list of {in, out} addresses; 16 pixel dwords in, eight macropixel dwords out per lane
 #pragma once
 #include "kernels/common.hip.h"
 #include "kernels/equalize.hip.h"
@@ -75,3 +77,4 @@
 #include "kernels/bgra_yuv420.hip.h"
 #include "kernels/yuv420_bgra.hip.h"
 #include "kernels/packed422_bgra.hip.h"
+#include "kernels/bgra_packed422.hip.h"

@@ -69,5 +69,7 @@ using namespace mi;
 #include "host/yuv420_bgra_frames.inc.hpp"  // ... as a list of pitched device frames (a decoder's frame pool in, a surface pool out)
 #include "host/packed422_bgra.inc.hpp"  // packed 4:2:2 (YUY2 / UYVY) in, four-channel BGRA / RGBA (CV_8UC4, A = 255) out, every row with its own chroma (capture card -> display surface / texture)
 #include "host/packed422_bgra_frames.inc.hpp"  // ... as a list of pitched device frames (a capture device's buffer pool in, a surface pool out)
+#include "host/bgra_packed422.inc.hpp"  // four-channel BGRA / RGBA (CV_8UC4) in, packed 4:2:2 (YUY2 / UYVY) out: convert and count, then map the luma in place in the packed frame (render target / capture -> playout / virtual camera)
+#include "host/bgra_packed422_frames.inc.hpp"  // ... as a list of frames, each at its own two addresses (a surface pool in, a playout / v4l2 output buffer pool out)
 #include "host/pipe.inc.hpp"
 #include "host/diff.inc.hpp"

@@ -666,6 +666,25 @@ inline void claheBGRToPacked422(const unsigned char* in, size_t inStep, unsigned
     detail::check(c, mi_clahe_bgr_to_packed422(c, in, inStep, out, outPitch, width, height, (int)order, (int)format, (mi_uv_mode)uv, clipLimit,
                                                tiles.width, tiles.height), "mi_clahe_bgr_to_packed422");
 }
+// The same edge for four-byte pixels: one interleaved CV_8UC4 host image (BGRA / BGRX, or RGBA / RGBX) at inStep >= 4*W in, one packed
+// 4:2:2 frame at outPitch >= 2*W out: the bytes of the three-channel call on the image with its fourth byte removed.  A render
+// target's or a screen capture's surface -> a playout card, a v4l2 output or loopback device, a virtual camera, without a three-channel
+// copy in between.  Width is even; any height.
+inline void equalizeHistBGRAToPacked422(const unsigned char* in, size_t inStep, unsigned char* out, size_t outPitch, int width, int height,
+                                        PackedFormat format = FMT_YUY2, ChannelOrder order = ORDER_BGR, UVMode uv = UV_COPY)
+{
+    mi_ctx* c = detail::thread_ctx();
+    detail::check(c, mi_equalize_hist_bgra_to_packed422(c, in, inStep, out, outPitch, width, height, (int)order, (int)format, (mi_uv_mode)uv),
+                  "mi_equalize_hist_bgra_to_packed422");
+}
+inline void claheBGRAToPacked422(const unsigned char* in, size_t inStep, unsigned char* out, size_t outPitch, int width, int height,
+                                 double clipLimit, Size tiles, PackedFormat format = FMT_YUY2, ChannelOrder order = ORDER_BGR,
+                                 UVMode uv = UV_COPY)
+{
+    mi_ctx* c = detail::thread_ctx();
+    detail::check(c, mi_clahe_bgra_to_packed422(c, in, inStep, out, outPitch, width, height, (int)order, (int)format, (mi_uv_mode)uv, clipLimit,
+                                                tiles.width, tiles.height), "mi_clahe_bgra_to_packed422");
+}
 // The decoder-to-playout edge: the planes of the view (NV12, I420 or YV12 in host memory) in, one packed 4:2:2 frame (FMT_YUY2 /
 // FMT_UYVY) at outPitch >= 2*W out: cv::equalizeHist / CLAHE::apply on the Y plane, output rows 2r and 2r+1 both with input chroma row r
 // unchanged (UV_COPY) or chroma 128 (UV_FILL128, the view's chroma is not read).  Width and height are even.

@@ -80,6 +80,9 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_bgra_to_yuv420_frames_dev", "mi_clahe_bgra_to_yuv420_frames_dev",
     "mi_equalize_hist_yuv420_to_bgra_batch_dev", "mi_clahe_yuv420_to_bgra_batch_dev", "mi_equalize_hist_yuv420_to_bgra", "mi_clahe_yuv420_to_bgra",
     "mi_equalize_hist_yuv420_to_bgra_frames_dev", "mi_clahe_yuv420_to_bgra_frames_dev",
+    "mi_equalize_hist_bgra_to_packed422_batch_dev", "mi_clahe_bgra_to_packed422_batch_dev",
+    "mi_equalize_hist_bgra_to_packed422", "mi_clahe_bgra_to_packed422",
+    "mi_equalize_hist_bgra_to_packed422_frames_dev", "mi_clahe_bgra_to_packed422_frames_dev",
 ]
 
 _K = len(KERNEL_NAMES)
@@ -367,6 +370,12 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_bgr_to_packed422.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, i, d, i, i]
     L.mi_equalize_hist_bgr_to_packed422_frames_dev.argtypes = [vp, C.POINTER(BgrPacked422FrameDev), i, i, i, sz, sz, i, i, i, vp]
     L.mi_clahe_bgr_to_packed422_frames_dev.argtypes = [vp, C.POINTER(BgrPacked422FrameDev), i, i, i, sz, sz, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_bgra_to_packed422_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, i, vp]
+    L.mi_clahe_bgra_to_packed422_batch_dev.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_bgra_to_packed422.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, i]
+    L.mi_clahe_bgra_to_packed422.argtypes = [vp, vp, sz, vp, sz, i, i, i, i, i, d, i, i]
+    L.mi_equalize_hist_bgra_to_packed422_frames_dev.argtypes = [vp, C.POINTER(BgrPacked422FrameDev), i, i, i, sz, sz, i, i, i, vp]
+    L.mi_clahe_bgra_to_packed422_frames_dev.argtypes = [vp, C.POINTER(BgrPacked422FrameDev), i, i, i, sz, sz, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_yuv420_to_packed422_batch_dev.argtypes = [vp, yp, vp, sz, sz, i, i, i, i, i, vp]
     L.mi_clahe_yuv420_to_packed422_batch_dev.argtypes = [vp, yp, vp, sz, sz, i, i, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_yuv420_to_packed422.argtypes = [vp, yp, vp, sz, i, i, i, i]
@@ -571,16 +580,16 @@ def _bgr_nv12_list(ins, ys, uvs, width, in_pitch, y_pitch, uv_pitch, what):
     return arr, len(ins), ip, yp, up
 
 
-def _bgr_packed422_list(ins, outs, width, in_pitch, out_pitch, what):
+def _bgr_packed422_list(ins, outs, width, in_pitch, out_pitch, what, ch=3):
     """ins / outs: sequences of equal length (torch CUDA tensors or raw device addresses).  Returns the mi_bgr_packed422_frame_dev
     array, its length and the two pitches (given, else the row stride of the tensors -- H x 3W or H x W x 3 images, H x pitch frames --
-    else 3 * width for the images and 2 * width for the frames)."""
+    else 3 * width for the images and 2 * width for the frames).  ch = 4: four-channel images (H x 4W or H x W x 4, 4 * width)."""
     ins, outs = list(ins), list(outs)
     if len(ins) != len(outs):
         raise MiError(1, what, f"{len(ins)} images but {len(outs)} frames")
     # an H x W x 3 image's rows are its first axis: seen as H x 3W for the pitch
     rows = [o if isinstance(o, int) or o is None or o.dim() != 3 else o[:, :, 0] for o in ins]
-    ip = int(in_pitch) if in_pitch is not None else _plane_pitch(rows, None, 3 * int(width), what)
+    ip = int(in_pitch) if in_pitch is not None else _plane_pitch(rows, None, ch * int(width), what)
     op = _plane_pitch(outs, out_pitch, 2 * int(width), what)
     arr = (BgrPacked422FrameDev * max(1, len(ins)))()
     for k in range(len(ins)):
@@ -1740,6 +1749,81 @@ class Context:
         img, h, w, step, out = self._bgr_packed422_host(img, out, "clahe_bgr_to_packed422")
         self._chk(self._L.mi_clahe_bgr_to_packed422(self._h, img.ctypes.data, step, out.ctypes.data, _step(out), w, h, int(order), int(fmt),
                                                   int(uv_mode), float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_bgr_to_packed422")
+        return out
+
+    # ---- four-channel BGRA / RGBA (CV_8UC4) in, packed 4:2:2 (YUY2 / UYVY) out: the fourth byte ignored, stage 2 as above ----
+    def equalize_hist_bgra_to_packed422_batch_dev(self, d_in, d_out, width, height, n_frames, order=ORDER_BGR, fmt=FMT_YUY2,
+                                                 uv_mode=UV_COPY, in_pitch=None, in_frame=None, out_pitch=None, out_frame=None, stream=0):
+        """mi_equalize_hist_bgra_to_packed422_batch_dev: n_frames four-channel BGRA / RGBA (CV_8UC4) images in, packed 4:2:2 frames out (torch tensors
+        or raw addresses).  Tight layouts are the defaults: in_pitch 4*W, in_frame = in_pitch * H, out_pitch 2*W, out_frame =
+        out_pitch * H."""
+        ip = 4 * int(width) if in_pitch is None else int(in_pitch)
+        fi = ip * int(height) if in_frame is None else int(in_frame)
+        op = 2 * int(width) if out_pitch is None else int(out_pitch)
+        fo = op * int(height) if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_equalize_hist_bgra_to_packed422_batch_dev(self._h, _dptr(d_in), ip, fi, _dptr(d_out), op, fo, int(width),
+                                                                    int(height), int(n_frames), int(order), int(fmt), int(uv_mode),
+                                                                    stream), "mi_equalize_hist_bgra_to_packed422_batch_dev")
+
+    def clahe_bgra_to_packed422_batch_dev(self, d_in, d_out, width, height, n_frames, order=ORDER_BGR, fmt=FMT_YUY2, uv_mode=UV_COPY,
+                                         clip_limit=2.0, tiles_x=8, tiles_y=8, in_pitch=None, in_frame=None, out_pitch=None,
+                                         out_frame=None, stream=0):
+        """mi_clahe_bgra_to_packed422_batch_dev; arguments as equalize_hist_bgra_to_packed422_batch_dev, plus the CLAHE parameters."""
+        ip = 4 * int(width) if in_pitch is None else int(in_pitch)
+        fi = ip * int(height) if in_frame is None else int(in_frame)
+        op = 2 * int(width) if out_pitch is None else int(out_pitch)
+        fo = op * int(height) if out_frame is None else int(out_frame)
+        self._chk(self._L.mi_clahe_bgra_to_packed422_batch_dev(self._h, _dptr(d_in), ip, fi, _dptr(d_out), op, fo, int(width), int(height),
+                                                            int(n_frames), int(order), int(fmt), int(uv_mode), float(clip_limit),
+                                                            int(tiles_x), int(tiles_y), stream), "mi_clahe_bgra_to_packed422_batch_dev")
+
+    def equalize_hist_bgra_to_packed422_frames(self, ins, outs, width, height, order=ORDER_BGR, fmt=FMT_YUY2, uv_mode=UV_COPY, in_pitch=None,
+                                              out_pitch=None, stream=0):
+        """mi_equalize_hist_bgra_to_packed422_frames_dev.  ins: the images, outs: the packed frames, each its own buffer -- lists of torch
+        CUDA tensors or raw device addresses, one entry per frame.  A pitch left at None is the row stride of the 2-D tensors of that
+        list (H x W x 4 images: of their rows), or the tight one (4 * width; 2 * width)."""
+        arr, n, ip, op = _bgr_packed422_list(ins, outs, width, in_pitch, out_pitch, "equalize_hist_bgra_to_packed422_frames", ch=4)
+        self._chk(self._L.mi_equalize_hist_bgra_to_packed422_frames_dev(self._h, arr, n, int(width), int(height), ip, op, int(order),
+                                                                     int(fmt), int(uv_mode), stream),
+                  "mi_equalize_hist_bgra_to_packed422_frames_dev")
+
+    def clahe_bgra_to_packed422_frames(self, ins, outs, width, height, order=ORDER_BGR, fmt=FMT_YUY2, uv_mode=UV_COPY, clip_limit=2.0,
+                                      tiles_x=8, tiles_y=8, in_pitch=None, out_pitch=None, stream=0):
+        """mi_clahe_bgra_to_packed422_frames_dev; arguments as equalize_hist_bgra_to_packed422_frames, plus the CLAHE parameters."""
+        arr, n, ip, op = _bgr_packed422_list(ins, outs, width, in_pitch, out_pitch, "clahe_bgra_to_packed422_frames", ch=4)
+        self._chk(self._L.mi_clahe_bgra_to_packed422_frames_dev(self._h, arr, n, int(width), int(height), ip, op, int(order), int(fmt),
+                                                             int(uv_mode), float(clip_limit), int(tiles_x), int(tiles_y), stream),
+                  "mi_clahe_bgra_to_packed422_frames_dev")
+
+    def _bgra_packed422_host(self, img, out, name):
+        if not isinstance(img, np.ndarray) or img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 4:
+            raise MiError(2, name, "expected an HxWx4 uint8 ndarray (CV_8UC4)")
+        if img.size and (img.strides[2] != 1 or img.strides[1] != 4):
+            raise MiError(1, name, "pixels must be interleaved")
+        h, w = img.shape[:2]
+        if out is None:
+            out = np.empty((h, 2 * w), np.uint8)
+        out = self._packed_host(out, w, name)
+        if out.shape[0] != h:
+            raise MiError(1, name, "out must have one row per image row")
+        return img, h, w, (int(img.strides[0]) if h > 1 else max(int(img.strides[0]), 4 * w)), out
+
+    def equalize_hist_bgra_to_packed422(self, img: np.ndarray, order: int = ORDER_BGR, fmt: int = FMT_YUY2, uv_mode: int = UV_COPY,
+                                       out: np.ndarray | None = None) -> np.ndarray:
+        """mi_equalize_hist_bgra_to_packed422 on a host image: an H x W x 4 uint8 array in (a view with padded rows included), the packed
+        frame out -- `out` when given (an H x pitch-bytes uint8 array, pitch >= 2*W; a view with padded rows is fine), else a new tight
+        H x 2W array."""
+        img, h, w, step, out = self._bgra_packed422_host(img, out, "equalize_hist_bgra_to_packed422")
+        self._chk(self._L.mi_equalize_hist_bgra_to_packed422(self._h, img.ctypes.data, step, out.ctypes.data, _step(out), w, h, int(order),
+                                                          int(fmt), int(uv_mode)), "mi_equalize_hist_bgra_to_packed422")
+        return out
+
+    def clahe_bgra_to_packed422(self, img: np.ndarray, order: int = ORDER_BGR, fmt: int = FMT_YUY2, uv_mode: int = UV_COPY,
+                               clip_limit: float = 2.0, tiles_x: int = 8, tiles_y: int = 8, out: np.ndarray | None = None) -> np.ndarray:
+        """mi_clahe_bgra_to_packed422; arguments as equalize_hist_bgra_to_packed422, plus the CLAHE parameters."""
+        img, h, w, step, out = self._bgra_packed422_host(img, out, "clahe_bgra_to_packed422")
+        self._chk(self._L.mi_clahe_bgra_to_packed422(self._h, img.ctypes.data, step, out.ctypes.data, _step(out), w, h, int(order), int(fmt),
+                                                  int(uv_mode), float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_bgra_to_packed422")
         return out
 
     # ---- 4:2:0 frames (NV12, or I420 / YV12 planes) in, packed 4:2:2 (YUY2 / UYVY) out in the pass that maps the luma ----
