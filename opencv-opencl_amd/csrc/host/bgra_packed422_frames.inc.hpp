@@ -1,98 +1,13 @@
 // bgra_packed422_frames.inc.hpp -- four-channel BGRA / RGBA (CV_8UC4) in, packed 4:2:2 (YUY2 / UYVY) out on frames given as a LIST of
-// addresses (mi_*_bgra_to_packed422_frames_dev): checks, chunking, extern "C"
+// addresses (mi_*_bgra_to_packed422_frames_dev): extern "C"
 // Included by ../mi_lumaeq.hip after bgra_packed422.inc.hpp (one translation unit; not a stand-alone header).
 //
 // A renderer, a compositor or a capture API hands out a pool of four-byte surfaces; a playout card, a v4l2 output queue or a virtual
 // camera hands out a buffer pool: every packed frame its own allocation, padded to bytesperline, at whatever alignment the driver
-// chose.  The structure is bgr_packed422_frames.inc.hpp's, whose entry struct (mi_bgr_packed422_frame_dev) and shape this form
-// reuses: the call is cut into chunks of kPacked422FramesPerLaunch frames -- the capacity of stage 2's table, so one chunk size serves
-// both stages.  A chunk's {image, frame} pairs travel to stage 1 as a Packed422List, its output frames to stage 2 as a second
-// Packed422List with in == out, both by value in the kernel arguments, through launch_bgra_to_packed422 and the packed form's own
-// launchers -- same grids, same partials, same bytes as the batch form.  Each frame takes the 16 x 1 groups or the macropixels of
-// stage 1 by its own two addresses (bgra_packed422_frame_vec, the kernel's own rule); stage 2 has always decided per row.
-
-namespace {
-
-// Everything is checked before anything is enqueued: a refused call writes nothing.  *work = false: MI_OK with nothing to do.
-mi_status check_bgra_packed422_frames(mi_ctx* c, const mi_bgr_packed422_frame_dev* frames, int n_frames, const BgrP422FramesShape& s,
-                                      bool is_clahe, int tiles_x, int tiles_y, bool* work)
-{
-    *work = false;
-    if (n_frames > 0 && !frames) return fail(c, MI_ERR_BAD_ARG, "null frame list");
-    // the shape: check_bgra_packed422's own answers (order, format, uv_mode, sizes, even width, tiles, the pitches, the limits of the
-    // packed and planar forms)
-    bool any = false;
-    const mi_status st = check_bgra_packed422(c, bgr_packed422_frames_shape_args(s, n_frames), false, is_clahe, tiles_x, tiles_y, &any);
-    if (st || !any) return st;
-    const size_t w = (size_t)s.width, rows = (size_t)s.height;
-    for (int k = 0; k < n_frames; ++k) {
-        const mi_bgr_packed422_frame_dev& f = frames[k];
-        if (!f.in || !f.out) return fail(c, MI_ERR_BAD_ARG, "null image or frame pointer");
-        if ((uintptr_t)f.out & 3) return fail(c, MI_ERR_BAD_ARG, "packed 4:2:2 frame addresses are multiples of 4");
-        // there is no in-place form (4 bytes per pixel in, 2 out): the image's rows may not meet the rows of its own output frame
-        if (Span(f.in, s.in_pitch, 4 * w, rows).meets(Span(f.out, s.out_pitch, 2 * w, rows)))
-            return fail(c, MI_ERR_BAD_ARG, "BGRA in, packed 4:2:2 out has no in-place form: an image overlaps its own output frame");
-    }
-    *work = true;
-    return MI_OK;
-}
-
-// Per chunk: one MI_K_COLOR (convert, and count for equalizeHist), then one MI_K_EQ_LUT and one MI_K_LUT_APPLY, or what
-// mi_clahe_packed422_frames_dev launches in place on the same output frames.  No MI_K_HIST.
-template <int OFF>
-mi_status bgra_packed422_frames_dev(mi_ctx* c, hipStream_t s, const mi_bgr_packed422_frame_dev* frames, int n_frames,
-                                    const BgrP422FramesShape& sh, bool is_clahe, double clip_limit, int tiles_x, int tiles_y)
-{
-    mi_status st;
-    unsigned long long n_vec = 0;
-    const long long frame_bytes = 2LL * sh.width * sh.height;
-    for (int f0 = 0; f0 < n_frames; f0 += kPacked422FramesPerLaunch) {
-        const int nf = std::min(kPacked422FramesPerLaunch, n_frames - f0);
-        Packed422List io{};                                          // this chunk's {image, frame} pairs for stage 1, from index 0
-        Packed422List fr{};                                          // its output frames for stage 2, in place
-        for (int k = 0; k < nf; ++k) {
-            const mi_bgr_packed422_frame_dev& f = frames[f0 + k];
-            io.f[k] = Packed422Frame{(const uint8_t*)f.in, (uint8_t*)f.out};
-            fr.f[k] = Packed422Frame{(const uint8_t*)f.out, (uint8_t*)f.out};
-        }
-        const BgrP422Args shape = bgr_packed422_frames_shape_args(sh, nf);
-        // the frames as the packed form's stages take them with a list: the chunk's first frame, frame strides 0, the chroma kept
-        const P422Args pa{fr.f[0].in, sh.out_pitch, 0, fr.f[0].out, sh.out_pitch, 0, sh.width, sh.height, nf, sh.format, MI_UV_COPY};
-        bool shape_vec = false;
-        if (!is_clahe) {
-            int nparts = 0;
-            if ((st = launch_bgra_to_packed422(c, s, shape, 0, nf, true, &nparts, &shape_vec, &io))) return st;
-            if ((st = grow_dev(c, &c->d_luts, &c->luts_bytes, (size_t)nf * 256))) return st;
-            LAUNCH(c, s, MI_K_EQ_LUT, equalize_lut_kernel, dim3(nf), dim3(kThreads), 0,
-                   (const uint32_t*)c->d_partial, nparts, (int)((long long)sh.width * sh.height), c->d_luts, (int32_t*)nullptr);
-            const int BA = blocks_per_frame(c, frame_bytes, PackedOut::apply_rows(sh.height), nf, 2048);
-            if ((st = launch_pair(c, s, MI_K_LUT_APPLY, PackedOut::K<OFF>::apply, &fr, dim3(BA, nf), dim3(kThreads), 0,
-                                  PackedOut::cut(pa, 0), (const uint8_t*)c->d_luts))) return st;
-        } else {
-            if ((st = launch_bgra_to_packed422(c, s, shape, 0, nf, false, nullptr, &shape_vec, &io))) return st;
-            if ((st = clahe422_dev<PackedOut, OFF>(c, s, pa, clip_limit, tiles_x, tiles_y, &fr, &fr))) return st;
-        }
-        // the walk of each frame: the kernel's own rule (kernels/bgra_packed422.hip.h), shape_vec being the launch's j.vec
-        for (int k = 0; k < nf; ++k) n_vec += bgra_packed422_frame_vec(shape_vec, io.f[k].in, io.f[k].out);
-    }
-    // the FRAMES by the walk their stage-1 kernel took, once the whole call is enqueued
-    c->bgra_packed422_list_frames_vec += n_vec;
-    c->bgra_packed422_list_frames_bytes += (unsigned long long)n_frames - n_vec;
-    return MI_OK;
-}
-
-mi_status bgra_packed422_frames_entry(mi_ctx* c, const mi_bgr_packed422_frame_dev* frames, int n_frames, const BgrP422FramesShape& sh,
-                                      bool is_clahe, double clip_limit, int tiles_x, int tiles_y, void* stream)
-{
-    bool work = false;
-    const mi_status st = check_bgra_packed422_frames(c, frames, n_frames, sh, is_clahe, tiles_x, tiles_y, &work);
-    if (st || !work) return st;
-    hipStream_t s = pick_stream(c, stream);
-    return sh.format == MI_FMT_UYVY ? bgra_packed422_frames_dev<1>(c, s, frames, n_frames, sh, is_clahe, clip_limit, tiles_x, tiles_y)
-                                    : bgra_packed422_frames_dev<0>(c, s, frames, n_frames, sh, is_clahe, clip_limit, tiles_x, tiles_y);
-}
-
-}  // namespace
+// chose.  The checks, the chunk loop (kPacked422FramesPerLaunch frames a chunk) and the entry are bgr_packed422_frames.inc.hpp's
+// templates on BgraTo422; the entry struct (mi_bgr_packed422_frame_dev) and the shape (BgrP422FramesShape) are the three-channel
+// form's.  Each frame takes the 16 x 1 groups or the macropixels of stage 1 by its own two addresses (bgra_packed422_frame_vec, the
+// kernel's own rule, through BgraTo422::frame_vec) and is counted by it in BgraTo422::count_list; stage 2 has always decided per row.
 
 extern "C" {
 
@@ -102,7 +17,7 @@ mi_status mi_equalize_hist_bgra_to_packed422_frames_dev(mi_ctx* c, const mi_bgr_
 {
     ENTER_COMPUTE(c);
     const BgrP422FramesShape sh{width, height, in_pitch, out_pitch, order, format, uv_mode};
-    return bgra_packed422_frames_entry(c, frames, n_frames, sh, false, 0.0, 0, 0, stream);
+    return bgr_packed422_frames_entry<BgraTo422>(c, frames, n_frames, sh, false, 0.0, 0, 0, stream);
 }
 
 mi_status mi_clahe_bgra_to_packed422_frames_dev(mi_ctx* c, const mi_bgr_packed422_frame_dev* frames, int n_frames,
@@ -111,7 +26,7 @@ mi_status mi_clahe_bgra_to_packed422_frames_dev(mi_ctx* c, const mi_bgr_packed42
 {
     ENTER_COMPUTE(c);
     const BgrP422FramesShape sh{width, height, in_pitch, out_pitch, order, format, uv_mode};
-    return bgra_packed422_frames_entry(c, frames, n_frames, sh, true, clip_limit, tiles_x, tiles_y, stream);
+    return bgr_packed422_frames_entry<BgraTo422>(c, frames, n_frames, sh, true, clip_limit, tiles_x, tiles_y, stream);
 }
 
 }  // extern "C"

@@ -1,123 +1,39 @@
 // packed422_bgra.inc.hpp -- packed 4:2:2 frames in (YUY2 / UYVY), interleaved 8-bit four-channel images out (BGRA / RGBA: CV_8UC4,
-// A = 255): checks, writer, host frame, extern "C" entry points
+// A = 255): the four-channel pixel form and the extern "C" entry points
 // Included by ../mi_lumaeq.hip after yuv420_bgra_frames.inc.hpp (one translation unit; not a stand-alone header).
 //
 // capture -> equalize -> display surface / swap-chain image / interop texture / GUI image without a three-channel image in scratch and
-// a widen to four channels outside the library.  This is packed422_bgr.inc.hpp with one more writer: the stage sequences are
-// packed422.inc.hpp's own (one MI_K_HIST, one MI_K_EQ_LUT and one MI_K_LUT_APPLY launch per chunk; tile histograms -> interpolation):
-// same scratch, same chunks, same grids and splits, every shape in one pass.  The pixel-writing kernels of
-// kernels/packed422_bgra.hip.h decode the new luma with the row's own chroma and write 4 bytes per pixel.  Never the fused kernel and
-// never hist_lut_kernel, as the packed forms.  The frame-list form is packed422_bgra_frames.inc.hpp's.
+// a widen to four channels outside the library.  The checks, the block, the writer of packed422_dev<W>, the host frame and the list
+// form are packed422_bgr.inc.hpp's and packed422_bgr_frames.inc.hpp's templates, instantiated here on Bgra422Image: the arguments
+// (P422BgrArgs), the stage sequences, scratch, chunks, grids and splits are the three-channel form's, the pixel-writing kernels are
+// those of kernels/packed422_bgra.hip.h (4 bytes per pixel).  The frame-list entry points are packed422_bgra_frames.inc.hpp's.
 
 namespace {
 
-// The arguments are the three-channel form's (P422BgrArgs, p422_bgr_args): an input side, an image, an order.
-
-// Everything is checked before anything is enqueued: check_packed422_bgr's rules in its order, with a row of 4 * W bytes.  No
-// alignment rule on the image side.  *work = false: MI_OK with nothing to do.
-mi_status check_packed422_bgra(mi_ctx* c, const P422BgrArgs& a, bool is_clahe, int tiles_x, int tiles_y, bool* work)
-{
-    *work = false;
-    if (a.order != MI_ORDER_BGR && a.order != MI_ORDER_RGB) return fail(c, MI_ERR_BAD_ARG, "order must be MI_ORDER_BGR or MI_ORDER_RGB");
-    bool in_work = false;
-    const mi_status st = check_packed422(c, a.in, is_clahe, tiles_x, tiles_y, &in_work);
-    if (st || !in_work) return st;
-    if (!a.out) return fail(c, MI_ERR_BAD_ARG, "null frame pointer");
-    if (a.out_pitch < 4 * (size_t)a.in.width) return fail(c, MI_ERR_BAD_ARG, "out_pitch < 4 * width");
-    if (a.out == a.in.in) return fail(c, MI_ERR_BAD_ARG, "packed in, BGRA out has no in-place form");
-    if (is_clahe) {
-        ClaheGeom g;
-        if (mi_status gs = clahe_geometry(c, a.in.width, a.in.height, 0.0, tiles_x, tiles_y, &g)) return gs;
-        if (tiles_x * tiles_y > kMaxGridY) return fail(c, MI_ERR_UNSUPPORTED, "more than 65535 tiles per frame");
-        if (tiles_x + 1 > kMaxPairsLds && a.in.height > kMaxGridY) return fail(c, MI_ERR_UNSUPPORTED, "height > 65535 with tiles_x > 62");
-    }
-    *work = true;
-    return MI_OK;
-}
-
-Packed422Bgra packed422_bgra_batch(const P422BgrArgs& a, int f0)
-{
-    Packed422Bgra p;
-    p.src = a.in.in + (size_t)f0 * a.in.in_frame; p.out = a.out + (size_t)f0 * a.out_frame;
-    p.src_step = (long long)a.in.in_pitch; p.out_step = (long long)a.out_pitch;
-    p.src_frame = (long long)a.in.in_frame; p.out_frame = (long long)a.out_frame;
-    p.dwords = a.in.width / 2; p.rows = a.in.height;
-    p.wide = packed422_bgra_frame_wide(a.out, p.out_step, p.out_frame) ? 1 : 0;
-    return p;
-}
-
-// The writer of the stage sequences of packed422.inc.hpp that decodes the new luma with the row's own chroma into B, G, R, 255
-// (ORDER 0) or R, G, B, 255 (ORDER 1).  Its frame list is the packed forms' own {in, out} table (packed422_bgra_frames.inc.hpp fills it).
-template <int ORDER> struct BgraOut422 {
-    using Args = P422BgrArgs;
+// The four-channel form: B, G, R, 255 or R, G, B, 255, 4 bytes per pixel.  The store-path rule both forms' blocks and counts go by is
+// packed422_bgra_frame_wide's (kernels/packed422_bgra.hip.h forwards to packed422_image_wide).  It counts batch and host calls
+// ("packed422_bgra_wide" / "packed422_bgra_bytes") and, apart from them, the frames of list calls.
+struct Bgra422Image {
+    static constexpr int kPx = 4;
     using Block = Packed422Bgra;
-    using List = Packed422List;
-    static const P422Args& input(const Args& a) { return a.in; }
-    static Block cut(const Args& a, int f0) { return packed422_bgra_batch(a, f0); }
-    static int apply_rows(int height) { return height; }
-    template <int OFF> struct K {
+    template <int OFF, int ORDER> struct K {
         static constexpr KernelPair apply{lut_apply422_bgra_frames_kernel<OFF, ORDER>, lut_apply422_bgra_kernel<OFF, ORDER>};
         static constexpr KernelPair interp_global{clahe_interp422_bgra_global_frames_kernel<OFF, ORDER>, clahe_interp422_bgra_global_kernel<OFF, ORDER>};
         template <bool FT, bool FMA>
         static constexpr KernelPair interp{clahe_interp422_bgra_frames_kernel<FT, FMA, OFF, ORDER>, clahe_interp422_bgra_kernel<FT, FMA, OFF, ORDER>};
     };
+    static constexpr const char* kOutPitch = "out_pitch < 4 * width";
+    static constexpr const char* kOutStep = "out_step < 4 * width";
+    static constexpr const char* kInPlace = "packed in, BGRA out has no in-place form";
+    static constexpr const char* kHostOverlap = "packed in, BGRA out has no in-place form: the image overlaps the input frame";
+    static constexpr const char* kListOverlap = "packed in, BGRA out has no in-place form: an image overlaps its own input frame";
+    static void count_call(mi_ctx* c, bool wide) { ++(wide ? c->packed422_bgra_wide : c->packed422_bgra_bytes); }
+    static void count_list(mi_ctx* c, int n_frames, unsigned long long n_wide)
+    {
+        c->packed422_bgra_list_frames_wide += n_wide;
+        c->packed422_bgra_list_frames_bytes += (unsigned long long)n_frames - n_wide;
+    }
 };
-
-// fl_in / fl_out: a chunk of a frame list (both or neither, see packed422.inc.hpp)
-mi_status packed422_bgra_dev(mi_ctx* c, hipStream_t s, const P422BgrArgs& a, int op, double clip_limit, int tiles_x, int tiles_y,
-                             const Packed422List* fl_in = nullptr, const Packed422List* fl_out = nullptr)
-{
-    return a.order == MI_ORDER_RGB ? packed422_dev<BgraOut422<1>>(c, s, a, op, clip_limit, tiles_x, tiles_y, fl_in, fl_out)
-                                   : packed422_dev<BgraOut422<0>>(c, s, a, op, clip_limit, tiles_x, tiles_y, fl_in, fl_out);
-}
-
-// A batch (or the host form's device frame): enqueue, then one count per call by the store path of its launches
-mi_status packed422_bgra_call(mi_ctx* c, hipStream_t s, const P422BgrArgs& a, int op, double clip_limit, int tiles_x, int tiles_y)
-{
-    const mi_status st = packed422_bgra_dev(c, s, a, op, clip_limit, tiles_x, tiles_y);
-    if (st) return st;
-    ++(packed422_bgra_frame_wide(a.out, (long long)a.out_pitch, (long long)a.out_frame) ? c->packed422_bgra_wide : c->packed422_bgra_bytes);
-    return MI_OK;
-}
-
-// The host form's checks: the input side and the shape are the device form's (on the caller's input and a stand-in image); the output
-// side is host memory the kernels never see -- any address, any out_step >= 4*W -- whose rows may not meet the input's.
-mi_status check_packed422_bgra_host(mi_ctx* c, const P422BgrArgs& h, bool is_clahe, int tiles_x, int tiles_y, bool* work)
-{
-    *work = false;
-    P422BgrArgs shape = h;
-    shape.out = h.out ? (uint8_t*)16 : nullptr;
-    shape.out_pitch = 4 * (size_t)std::max(h.in.width, 0); shape.out_frame = 0;
-    bool any = false;
-    const mi_status st = check_packed422_bgra(c, shape, is_clahe, tiles_x, tiles_y, &any);
-    if (st || !any) return st;
-    const size_t w = (size_t)h.in.width, rows = (size_t)h.in.height;
-    if (h.out_pitch < 4 * w) return fail(c, MI_ERR_BAD_ARG, "out_step < 4 * width");
-    if ((long long)h.in.width * h.in.height > 0x7fffffffLL / 4) return fail(c, MI_ERR_UNSUPPORTED, "image too large");
-    if (Span(h.out, h.out_pitch, 4 * w, rows).meets(Span(h.in.in, h.in.in_pitch, 2 * w, rows)))
-        return fail(c, MI_ERR_BAD_ARG, "packed in, BGRA out has no in-place form: the image overlaps the input frame");
-    *work = true;
-    return MI_OK;
-}
-
-// Host frame: the packed frame goes up tight (2 B/px), the image comes back tight (4 B/px); pinned tight buffers are DMA'd as they are,
-// anything else goes through the context's pinned staging (stage_in / stage_out, which drain the stream on every error exit).  Only the
-// 2 * W bytes of each input row are read and the 4 * W bytes of each output row written.  The device image is tight at an aligned
-// allocation: always the wide store path, whatever the caller's address and out_step are.
-mi_status packed422_bgra_host(mi_ctx* c, const P422BgrArgs& h, int op, double clip_limit, int tiles_x, int tiles_y)
-{
-    const size_t w = (size_t)h.in.width, rows = (size_t)h.in.height;
-    const size_t in_row = 2 * w, in_bytes = in_row * rows, out_row = 4 * w, out_bytes = out_row * rows;
-    hipStream_t s = c->stream;
-    StreamDrain drain(HipStreamSync{}, drain_counter(c));
-    mi_status st;
-    if ((st = stage_in(c, s, h.in.in, h.in.in_pitch, in_row, rows, drain))) return st;
-    if ((st = grow_dev(c, &c->d_stage_out, &c->stage_out_bytes, out_bytes))) return st;
-    const P422BgrArgs d = p422_bgr_args(c->d_stage_in, in_row, in_bytes, c->d_stage_out, out_row, out_bytes,
-                                        h.in.width, h.in.height, 1, h.in.format, h.order);
-    if ((st = packed422_bgra_call(c, s, d, op, clip_limit, tiles_x, tiles_y))) return st;
-    return stage_out(c, s, h.out, h.out_pitch, out_row, rows, drain);
-}
 
 }  // namespace
 
@@ -130,8 +46,8 @@ mi_status mi_equalize_hist_packed422_to_bgra_batch_dev(mi_ctx* c, const void* d_
     ENTER_COMPUTE(c);
     const P422BgrArgs a = p422_bgr_args(d_in, in_pitch, in_frame_stride, d_out, out_pitch, out_frame_stride, width, height, n_frames, format, order);
     bool work = false;
-    const mi_status st = check_packed422_bgra(c, a, false, 0, 0, &work);
-    return (st || !work) ? st : packed422_bgra_call(c, pick_stream(c, stream), a, 0, 0.0, 0, 0);
+    const mi_status st = check_packed422_bgr<Bgra422Image>(c, a, false, 0, 0, &work);
+    return (st || !work) ? st : packed422_bgr_call<Bgra422Image>(c, pick_stream(c, stream), a, 0, 0.0, 0, 0);
 }
 
 mi_status mi_clahe_packed422_to_bgra_batch_dev(mi_ctx* c, const void* d_in, size_t in_pitch, size_t in_frame_stride,
@@ -142,8 +58,8 @@ mi_status mi_clahe_packed422_to_bgra_batch_dev(mi_ctx* c, const void* d_in, size
     ENTER_COMPUTE(c);
     const P422BgrArgs a = p422_bgr_args(d_in, in_pitch, in_frame_stride, d_out, out_pitch, out_frame_stride, width, height, n_frames, format, order);
     bool work = false;
-    const mi_status st = check_packed422_bgra(c, a, true, tiles_x, tiles_y, &work);
-    return (st || !work) ? st : packed422_bgra_call(c, pick_stream(c, stream), a, 1, clip_limit, tiles_x, tiles_y);
+    const mi_status st = check_packed422_bgr<Bgra422Image>(c, a, true, tiles_x, tiles_y, &work);
+    return (st || !work) ? st : packed422_bgr_call<Bgra422Image>(c, pick_stream(c, stream), a, 1, clip_limit, tiles_x, tiles_y);
 }
 
 mi_status mi_equalize_hist_packed422_to_bgra(mi_ctx* c, const uint8_t* in, size_t in_pitch, uint8_t* out, size_t out_step,
@@ -152,8 +68,8 @@ mi_status mi_equalize_hist_packed422_to_bgra(mi_ctx* c, const uint8_t* in, size_
     ENTER_COMPUTE(c);
     const P422BgrArgs h = p422_bgr_args(in, in_pitch, 0, out, out_step, 0, width, height, 1, format, order);
     bool work = false;
-    const mi_status st = check_packed422_bgra_host(c, h, false, 0, 0, &work);
-    return (st || !work) ? st : packed422_bgra_host(c, h, 0, 0.0, 0, 0);
+    const mi_status st = check_packed422_bgr_host<Bgra422Image>(c, h, false, 0, 0, &work);
+    return (st || !work) ? st : packed422_bgr_host<Bgra422Image>(c, h, 0, 0.0, 0, 0);
 }
 
 mi_status mi_clahe_packed422_to_bgra(mi_ctx* c, const uint8_t* in, size_t in_pitch, uint8_t* out, size_t out_step,
@@ -162,8 +78,8 @@ mi_status mi_clahe_packed422_to_bgra(mi_ctx* c, const uint8_t* in, size_t in_pit
     ENTER_COMPUTE(c);
     const P422BgrArgs h = p422_bgr_args(in, in_pitch, 0, out, out_step, 0, width, height, 1, format, order);
     bool work = false;
-    const mi_status st = check_packed422_bgra_host(c, h, true, tiles_x, tiles_y, &work);
-    return (st || !work) ? st : packed422_bgra_host(c, h, 1, clip_limit, tiles_x, tiles_y);
+    const mi_status st = check_packed422_bgr_host<Bgra422Image>(c, h, true, tiles_x, tiles_y, &work);
+    return (st || !work) ? st : packed422_bgr_host<Bgra422Image>(c, h, 1, clip_limit, tiles_x, tiles_y);
 }
 
 }  // extern "C"

@@ -1,72 +1,13 @@
 // packed422_bgra_frames.inc.hpp -- packed 4:2:2 in (YUY2 / UYVY), four-channel BGRA / RGBA (CV_8UC4, A = 255) out on a LIST of device
-// frames (mi_*_packed422_to_bgra_frames_dev): checks, chunking, extern "C"
+// frames (mi_*_packed422_to_bgra_frames_dev): extern "C"
 // Included by ../mi_lumaeq.hip after packed422_bgra.inc.hpp (one translation unit; not a stand-alone header).
 //
 // Neither end of a capture -> display pipeline is one allocation at a fixed frame stride: the capture card hands out a buffer pool
-// (packed422_frames.inc.hpp), the images are a swap chain's or a pool of surfaces, textures or cv::Mats.  This is
-// packed422_bgr_frames.inc.hpp with the BgraOut422 writer: the call is cut into chunks of at most kPacked422FramesPerLaunch frames; a
-// chunk's inputs travel to the histogram stages as a Packed422List whose out mirrors in (they only read), its {in, out} pairs to the
-// writers as a second Packed422List, both by value in the kernel arguments -- same grids, same tile splits, same bytes as the batch
-// form, every shape in one pass.  The entry type is the three-channel form's mi_packed422_bgr_frame_dev.  Each frame takes the wide or
-// the byte store path by its own address (packed422_bgra_frame_wide, as Table422Bgra::wide_of calls it).
-
-namespace {
-
-// The shape of a list call is the three-channel form's P422BgrFramesShape, with an out_pitch of at least 4 * W.
-
-// Everything is checked before anything is enqueued: a refused call writes nothing.  *work = false: MI_OK with nothing to do.
-mi_status check_packed422_bgra_frames(mi_ctx* c, const mi_packed422_bgr_frame_dev* frames, int n_frames, const P422BgrFramesShape& s,
-                                      bool is_clahe, int tiles_x, int tiles_y, bool* work)
-{
-    *work = false;
-    if (n_frames > 0 && !frames) return fail(c, MI_ERR_BAD_ARG, "null frame list");
-    // the shape: check_packed422_bgra's own answers (order, format, even width, sizes, tiles, the pitches, the tile grids and heights
-    // the stage sequences would refuse), on stand-in addresses that pass its pointer checks
-    const P422BgrArgs shape = p422_bgr_args((const void*)16, s.in_pitch, 0, (void*)32, s.out_pitch, 0, s.width, s.height, n_frames,
-                                            s.format, s.order);
-    bool any = false;
-    const mi_status st = check_packed422_bgra(c, shape, is_clahe, tiles_x, tiles_y, &any);
-    if (st || !any) return st;
-    const size_t w = (size_t)s.width, rows = (size_t)s.height;
-    for (int k = 0; k < n_frames; ++k) {
-        const mi_packed422_bgr_frame_dev& f = frames[k];
-        if (!f.in || !f.out) return fail(c, MI_ERR_BAD_ARG, "null frame pointer");
-        if ((uintptr_t)f.in & 3) return fail(c, MI_ERR_BAD_ARG, "packed 4:2:2 frame addresses are multiples of 4");
-        // there is no in-place form (2 bytes per pixel in, 4 out): the image's rows may not meet the rows of its own input
-        if (Span(f.out, s.out_pitch, 4 * w, rows).meets(Span(f.in, s.in_pitch, 2 * w, rows)))
-            return fail(c, MI_ERR_BAD_ARG, "packed in, BGRA out has no in-place form: an image overlaps its own input frame");
-    }
-    *work = true;
-    return MI_OK;
-}
-
-// op: 0 equalizeHist, 1 CLAHE
-mi_status packed422_bgra_frames_dev(mi_ctx* c, hipStream_t s, const mi_packed422_bgr_frame_dev* frames, int n_frames,
-                                    const P422BgrFramesShape& sh, int op, double clip_limit, int tiles_x, int tiles_y)
-{
-    unsigned long long n_wide = 0;
-    for (int f0 = 0; f0 < n_frames; f0 += kPacked422FramesPerLaunch) {
-        const int nf = std::min(kPacked422FramesPerLaunch, n_frames - f0);
-        Packed422List in{};                                          // this chunk's frames of the list, from index 0: the inputs for the
-        Packed422List io{};                                          // histogram stages (out mirrors in), the {in, out} pairs for the writers
-        for (int k = 0; k < nf; ++k) {
-            const mi_packed422_bgr_frame_dev& f = frames[f0 + k];
-            in.f[k] = Packed422Frame{(const uint8_t*)f.in, (uint8_t*)const_cast<void*>(f.in)};
-            io.f[k] = Packed422Frame{(const uint8_t*)f.in, (uint8_t*)f.out};
-            n_wide += packed422_bgra_frame_wide(f.out, (long long)sh.out_pitch, 0);
-        }
-        // a table launch ignores the block's base addresses, frame strides and `wide`: every frame brings its own address to the rule
-        const P422BgrArgs a = p422_bgr_args(io.f[0].in, sh.in_pitch, 0, nullptr, sh.out_pitch, 0, sh.width, sh.height, nf, sh.format, sh.order);
-        const mi_status st = packed422_bgra_dev(c, s, a, op, clip_limit, tiles_x, tiles_y, &in, &io);
-        if (st) return st;
-    }
-    // the FRAMES by the store path their pixel-writing kernel took, once the whole call is enqueued
-    c->packed422_bgra_list_frames_wide += n_wide;
-    c->packed422_bgra_list_frames_bytes += (unsigned long long)n_frames - n_wide;
-    return MI_OK;
-}
-
-}  // namespace
+// (packed422_frames.inc.hpp), the images are a swap chain's or a pool of surfaces, textures or cv::Mats.  The checks and the chunk
+// loop (f0 += kPacked422FramesPerLaunch) are packed422_bgr_frames.inc.hpp's templates on Bgra422Image; the entry type
+// (mi_packed422_bgr_frame_dev) and the shape (P422BgrFramesShape, with an out_pitch of at least 4 * W) are the three-channel form's.
+// Each frame takes the wide or the byte store path by its own address (packed422_bgra_frame_wide, as Table422Bgra::wide_of calls it),
+// and is counted by it in Bgra422Image::count_list.
 
 extern "C" {
 
@@ -77,8 +18,8 @@ mi_status mi_equalize_hist_packed422_to_bgra_frames_dev(mi_ctx* c, const mi_pack
     ENTER_COMPUTE(c);
     const P422BgrFramesShape sh{width, height, in_pitch, out_pitch, format, order};
     bool work = false;
-    const mi_status st = check_packed422_bgra_frames(c, frames, n_frames, sh, false, 0, 0, &work);
-    return (st || !work) ? st : packed422_bgra_frames_dev(c, pick_stream(c, stream), frames, n_frames, sh, 0, 0.0, 0, 0);
+    const mi_status st = check_packed422_bgr_frames<Bgra422Image>(c, frames, n_frames, sh, false, 0, 0, &work);
+    return (st || !work) ? st : packed422_bgr_frames_dev<Bgra422Image>(c, pick_stream(c, stream), frames, n_frames, sh, 0, 0.0, 0, 0);
 }
 
 mi_status mi_clahe_packed422_to_bgra_frames_dev(mi_ctx* c, const mi_packed422_bgr_frame_dev* frames, int n_frames,
@@ -88,8 +29,8 @@ mi_status mi_clahe_packed422_to_bgra_frames_dev(mi_ctx* c, const mi_packed422_bg
     ENTER_COMPUTE(c);
     const P422BgrFramesShape sh{width, height, in_pitch, out_pitch, format, order};
     bool work = false;
-    const mi_status st = check_packed422_bgra_frames(c, frames, n_frames, sh, true, tiles_x, tiles_y, &work);
-    return (st || !work) ? st : packed422_bgra_frames_dev(c, pick_stream(c, stream), frames, n_frames, sh, 1, clip_limit, tiles_x, tiles_y);
+    const mi_status st = check_packed422_bgr_frames<Bgra422Image>(c, frames, n_frames, sh, true, tiles_x, tiles_y, &work);
+    return (st || !work) ? st : packed422_bgr_frames_dev<Bgra422Image>(c, pick_stream(c, stream), frames, n_frames, sh, 1, clip_limit, tiles_x, tiles_y);
 }
 
 }  // extern "C"

@@ -123,7 +123,9 @@ static_assert(kThreads == 256, "bgr_to_packed422_hist_kernel writes one bin per 
 // not the cause: the parent's text moved unchanged into a __device__ __forceinline__ function that the kernel calls with its own
 // argument, by value or by reference, gives the same sixteen differences -- a body that is a function is optimised once on its own
 // and once more inside the kernel -- so no function-shaped body keeps the batch form's ISA, which it must not pay for the list form
-// (DESIGN.md).
+// (DESIGN.md).  Tried once more when the host side of the image forms became one implementation, with the two policies of
+// bgra_packed422.hip.h (StridedBgraPacked422 / TableBgraPacked422) word for word: all 32 instantiations of the two kernels changed
+// (docs/experiments.md, R39).  The copy stays.
 // =============================================================================================
 static_assert(sizeof(Packed422Frame) == 16, "two addresses an entry");
 

@@ -29,6 +29,13 @@ struct Packed422Bgr {
                                       // (a table launch: out_step alone, each frame adds its own address -- Table422Bgr::wide_of)
 };
 
+// THE rule "does an image at these addresses take the wide stores", for every pixel form of packed input: its address is a multiple of
+// 4, and so are the pitch and (a batch; a list passes 0) the frame stride.  The host fills `wide` and counts by it.
+__host__ __device__ __forceinline__ bool packed422_image_wide(const void* out, long long out_step, long long out_frame)
+{
+    return (((uintptr_t)out | (uintptr_t)out_step | (uintptr_t)out_frame) & 3) == 0;
+}
+
 // Where frame f lives, and which store path it takes.  The bodies below are templates on such a policy, as packed422_nv12.hip.h's
 // are: the batch kernels wrap them with the strided policy, the *_frames_kernel entries with the table.
 struct Strided422Bgr {
@@ -101,22 +108,30 @@ __device__ __forceinline__ void store422_px(uint8_t* p, const uint32_t* w, int n
         if (i < 3 * n) p[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
 }
 
-template <int ORDER>
-__device__ __forceinline__ void decode422_store(uint8_t* p, const u32x4& y, const u32x4& uv, int n, bool wide)
-{
-    uint32_t w[12];
-    decode422_16<ORDER>(y, uv, w);
-    store422_px(p, w, n, wide);
-}
+// What the LUT-apply and the interpolation body below do with a lane's 16 decoded pixels is a store policy S; they are written once
+// for every pixel form (this file's Store422Bgr; a form with another pixel size brings its own block type and policy and wraps the
+// same bodies):
+//   kPxBytes, kGroupBytes       bytes per pixel and per 16-pixel group of the image
+//   group(p, y, uv, n, wide)    16 mapped luma bytes and the 8 U,V pairs of the same macropixels -> the first n pixels at p
+// The three-channel policy: 48 bytes a group (decode422_16, store422_px).
+template <int ORDER> struct Store422Bgr {
+    static constexpr int kPxBytes = 3, kGroupBytes = 48;
+    static __device__ __forceinline__ void group(uint8_t* p, const u32x4& y, const u32x4& uv, int n, bool wide)
+    {
+        uint32_t w[12];
+        decode422_16<ORDER>(y, uv, w);
+        store422_px(p, w, n, wide);
+    }
+};
 
 // ---------------------------------------------------------------------------------------------
 // K3b  LUT apply + decode, packed -> BGR / RGB.  grid = (B, n_frames).  A workgroup takes a band of rows and walks it as (row,
 // 16-column group) items kThreads apart; an item is two 16-byte loads, 16 LUT reads, 8 chroma terms, 16 pixels decoded and 48 bytes
-// stored.  The input is read once: luma and chroma come out of the same two registers quads.  Groups are cut at multiples of 16 columns
-// from the row start; the last group of a row may be ragged (nd < 8 dwords).
+// stored (S::kGroupBytes).  The input is read once: luma and chroma come out of the same two registers quads.  Groups are cut at
+// multiples of 16 columns from the row start; the last group of a row may be ragged (nd < 8 dwords).
 // ---------------------------------------------------------------------------------------------
-template <int OFF, int ORDER, class Frames>
-__device__ __forceinline__ void lut_apply422_bgr_body(const Packed422Bgr& p, const Frames& fr, const uint8_t* __restrict__ luts)
+template <int OFF, class S, class Block, class Frames>
+__device__ __forceinline__ void lut_apply422_bgr_body(const Block& p, const Frames& fr, const uint8_t* __restrict__ luts)
 {
     __shared__ uint32_t lut[256 * kCopies];
     // frames last-to-first: the histogram pass streamed the batch first-to-last, its tail is still in the Infinity Cache
@@ -138,7 +153,7 @@ __device__ __forceinline__ void lut_apply422_bgr_body(const Packed422Bgr& p, con
     const int drow = kThreads / G, dgrp = kThreads - drow * G;
     for (long long it = t; it < items; it += kThreads) {
         const uint8_t* s = src0 + (long long)row * p.src_step + 32LL * grp;
-        uint8_t* d = out0 + (long long)row * p.out_step + 48LL * grp;
+        uint8_t* d = out0 + (long long)row * p.out_step + (long long)S::kGroupBytes * grp;
         const int nd = min(8, p.dwords - 8 * grp);
         u32x4 a, b;
         if (nd == 8) {
@@ -148,7 +163,7 @@ __device__ __forceinline__ void lut_apply422_bgr_body(const Packed422Bgr& p, con
             load422_tail(s, nd, a, b);
         }
         const u32x4 o = lut_vec(lut, gather422<OFF>(a, b), copy);
-        decode422_store<ORDER>(d, o, chroma422<OFF>(a, b), 2 * nd, wide);
+        S::group(d, o, chroma422<OFF>(a, b), 2 * nd, wide);
         row += drow; grp += dgrp;
         if (grp >= G) { grp -= G; ++row; }
     }
@@ -156,12 +171,12 @@ __device__ __forceinline__ void lut_apply422_bgr_body(const Packed422Bgr& p, con
 template <int OFF, int ORDER>
 __global__ __launch_bounds__(kThreads) void lut_apply422_bgr_kernel(Packed422Bgr p, const uint8_t* __restrict__ luts)
 {
-    lut_apply422_bgr_body<OFF, ORDER>(p, Strided422Bgr{p}, luts);
+    lut_apply422_bgr_body<OFF, Store422Bgr<ORDER>>(p, Strided422Bgr{p}, luts);
 }
 template <int OFF, int ORDER>
 __global__ __launch_bounds__(kThreads) void lut_apply422_bgr_frames_kernel(Packed422List l, Packed422Bgr p, const uint8_t* __restrict__ luts)
 {
-    lut_apply422_bgr_body<OFF, ORDER>(p, Table422Bgr{l, p}, luts);
+    lut_apply422_bgr_body<OFF, Store422Bgr<ORDER>>(p, Table422Bgr{l, p}, luts);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -169,8 +184,8 @@ __global__ __launch_bounds__(kThreads) void lut_apply422_bgr_frames_kernel(Packe
 // blend (interp_stage in clahe.hip.h; all four <FT, FMA> rungs), the 16 blended luma bytes decoded with the chroma of the same two
 // loads.  Every row belongs to exactly one band and carries its own chroma, so no lane reads a second row.
 // ---------------------------------------------------------------------------------------------
-template <bool FT, bool FMA, int OFF, int ORDER, class Frames>
-__device__ __forceinline__ void clahe_interp422_bgr_body(const Packed422Bgr& p, const Frames& fr, const ClaheGeom g,
+template <bool FT, bool FMA, int OFF, class S, class Block, class Frames>
+__device__ __forceinline__ void clahe_interp422_bgr_body(const Block& p, const Frames& fr, const ClaheGeom g,
                                                          const uint8_t* __restrict__ luts, int subs, int groups, int pair_cap)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t quad[];   // [(tiles_x + 1)][256] u32 quads, or f32x4 when FT
@@ -200,7 +215,7 @@ __device__ __forceinline__ void clahe_interp422_bgr_body(const Packed422Bgr& p, 
         poff[j] = pr << 8;
     }
     const uint8_t* src = fr.src_of(f) + 2LL * x0;
-    uint8_t* dst = fr.out_of(f) + 3LL * x0;
+    uint8_t* dst = fr.out_of(f) + (long long)S::kPxBytes * x0;
     const bool full = x0 + kInterpPx <= g.width;
     const bool wide = fr.wide_of(f);
     auto ty1_of = [&](int y) { return floor_f32_to_int(tile_coord<FMA>(y, g.inv_th)); };
@@ -214,7 +229,7 @@ __device__ __forceinline__ void clahe_interp422_bgr_body(const Packed422Bgr& p, 
             const float ya = __fsub_rn(tyf, (float)ty1u), ya1 = __fsub_rn(1.0f, ya);
             const u32x4 q = gather422<OFF>(a, b);
             const u32x4 o = FT ? clahe_vec16_f32<FMA>(quadf, q, poff, xw, ya, ya1) : clahe_vec16<FMA>(quad, q, poff, xa, xa1, ya, ya1);
-            decode422_store<ORDER>(dst + (long long)yy * p.out_step, o, chroma422<OFF>(a, b), kInterpPx, wide);
+            S::group(dst + (long long)yy * p.out_step, o, chroma422<OFF>(a, b), kInterpPx, wide);
         };
         // two rows in flight per lane, as clahe_interp422_kernel: 64 bytes of loads
         constexpr int kRowsInFlight = 2;
@@ -256,7 +271,7 @@ __device__ __forceinline__ void clahe_interp422_bgr_body(const Packed422Bgr& p, 
                     o[j >> 2] |= clahe_px<FMA>(e, xa[j], xa1[j], ya, ya1) << (8 * (j & 3));
                 }
             const u32x4 ov = {o[0], o[1], o[2], o[3]};
-            decode422_store<ORDER>(dst + (long long)y * p.out_step, ov, chroma422<OFF>(a, b), 2 * nd, wide);
+            S::group(dst + (long long)y * p.out_step, ov, chroma422<OFF>(a, b), 2 * nd, wide);
         }
     }
 }
@@ -264,18 +279,22 @@ template <bool FT, bool FMA, int OFF, int ORDER>
 __global__ __launch_bounds__(kThreads) void clahe_interp422_bgr_kernel(Packed422Bgr p, ClaheGeom g, const uint8_t* __restrict__ luts,
                                                                       int subs, int groups, int pair_cap)
 {
-    clahe_interp422_bgr_body<FT, FMA, OFF, ORDER>(p, Strided422Bgr{p}, g, luts, subs, groups, pair_cap);
+    clahe_interp422_bgr_body<FT, FMA, OFF, Store422Bgr<ORDER>>(p, Strided422Bgr{p}, g, luts, subs, groups, pair_cap);
 }
 template <bool FT, bool FMA, int OFF, int ORDER>
 __global__ __launch_bounds__(kThreads) void clahe_interp422_bgr_frames_kernel(Packed422List l, Packed422Bgr p, ClaheGeom g,
                                                                              const uint8_t* __restrict__ luts, int subs, int groups, int pair_cap)
 {
-    clahe_interp422_bgr_body<FT, FMA, OFF, ORDER>(p, Table422Bgr{l, p}, g, luts, subs, groups, pair_cap);
+    clahe_interp422_bgr_body<FT, FMA, OFF, Store422Bgr<ORDER>>(p, Table422Bgr{l, p}, g, luts, subs, groups, pair_cap);
 }
 
 // Fallback for tile grids too wide for the LDS pair table (clahe_interp422_global_kernel's arithmetic): one macropixel per thread, the
 // LUTs gathered from global memory (L2), two pixels decoded with the macropixel's own U and V: 6 bytes, as three 2-byte stores when the
 // row starts at an even address (`wide`), else as bytes.  grid = (ceil(W / 2 / 256), H, n_frames).
+// This body is written out for each pixel form (here and in the four-channel file), not shared through the store policy as the two
+// bodies above are: every policy shape tried for its 6- or 8-byte store -- one pair(o, ...) function, decode and store apart with the
+// pixels in a struct or in a word array, the wide / byte branch inside the policy or kept here -- left the instructions the same and
+// turned one of the kernel's two uniform branches round in 12 or 16 of the 16 instantiations (docs/experiments.md).
 template <int OFF, int ORDER, class Frames>
 __device__ __forceinline__ void clahe_interp422_bgr_global_body(const Packed422Bgr& p, const Frames& fr, const ClaheGeom& g,
                                                                 const uint8_t* __restrict__ luts)

@@ -44,14 +44,16 @@
 //                                  with the chroma loaded from two planes and zipped in registers; their *_frames_kernel entries on a
 //                                  list of {y, u, v, out} addresses
 //   kernels/packed422_bgr.hip.h    the pixel-writing stages of packed 4:2:2 in, interleaved BGR / RGB out: LUT apply / CLAHE blend + decode,
-//                                  every row with its own chroma
+//                                  every row with its own chroma; the LUT-apply and the interpolation body are templates on the block
+//                                  type and a store policy (Store422Bgr: 3 B/px), written once for every image form
 //   kernels/bgra_yuv420.hip.h      stage 1 of four-channel BGRA / RGBA (CV_8UC4) in, 4:2:0 out: one body for NV12 and planar chroma, for a
 //                                  strided batch and a list of {in, y, c0, c1} addresses; the fourth byte takes part in nothing
 //   kernels/yuv420_bgra.hip.h      the pixel-writing stages of 4:2:0 in, four-channel BGRA / RGBA (CV_8UC4, A = 255) out: LUT apply / CLAHE
 //                                  blend + decode, one body each for NV12 and planar chroma, for a strided batch and a list of
 //                                  {y, c0, c1, out} addresses; every pixel one dword, a 16-pixel group four 16-byte stores
-//   kernels/packed422_bgra.hip.h   the pixel-writing stages of packed 4:2:2 in, four-channel BGRA / RGBA (CV_8UC4, A = 255) out: the bodies of
-//                                  packed422_bgr.hip.h with that dword-per-pixel store, every row with its own chroma
+//   kernels/packed422_bgra.hip.h   the pixel-writing stages of packed 4:2:2 in, four-channel BGRA / RGBA (CV_8UC4, A = 255) out: its block, its
+//                                  store policy (Store422Bgra: that dword-per-pixel store) and the entries that wrap the bodies of
+//                                  packed422_bgr.hip.h with them; the wide-grid fallback body is written out
 //   kernels/bgra_packed422.hip.h   stage 1 of four-channel BGRA / RGBA (CV_8UC4) in, packed 4:2:2 (YUY2 / UYVY) out: one body for a strided
 //                                  batch and a list of {in, out} addresses; 16 pixel dwords in, eight macropixel dwords out per lane
 #pragma once

@@ -167,6 +167,13 @@ def test_new_sources_are_registered():
                "stage_out", "StreamDrain", "bgr_packed422_vec", "bgr_packed422_bytes"):
         assert re.search(r"\b" + fn + r"\b", host), fn
     assert "MI_K_HIST" not in re.sub(r"//[^\n]*", "", host), "stage 1 counts: the form has no MI_K_HIST launch"
+    # the three-channel pixel form of the templates in that file: 3 bytes a pixel, the byte basis (3 + 2) / 2 a pixel, its own kernels
+    for piece in ("struct BgrTo422", "static constexpr int kPx = 3;", "static long long grid_bytes(long long px) { return px * 5 / 2; }",
+                  "bgr_to_packed422_hist_kernel<ORDER, OFF, UVMODE, HIST>", "bgr_to_packed422_hist_frames_kernel<ORDER, OFF, UVMODE, HIST>",
+                  "bgr_packed422_entry<BgrTo422>"):
+        assert piece in host, piece
+    for other in ("packed422_bgra", "bgra422", "bgra_packed422", "bgra_to_packed422"):
+        assert other not in host.lower(), "the three-channel file does not know the four-channel form"
     assert (ROOT / "tools" / "bgr_to_packed422_ab.py").exists()
 
 

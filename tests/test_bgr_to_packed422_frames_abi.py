@@ -164,8 +164,16 @@ def test_new_sources_are_registered():
     assert "asm" not in re.sub(r"//[^\n]*", "", kern), "no inline assembly"
     host = (CSRC / "host" / "bgr_packed422_frames.inc.hpp").read_text()
     for fn in ("check_bgr_packed422", "launch_bgr_to_packed422", "kPacked422FramesPerLaunch", "Packed422List", "PackedOut", "clahe422_dev",
-               "launch_pair", "equalize_lut_kernel", "MI_K_COLOR", "Span", "bgr_packed422_frame_vec", "bgr_packed422_list_frames_vec", "bgr_packed422_list_frames_bytes"):
+               "launch_pair", "equalize_lut_kernel", "MI_K_COLOR", "Span"):
         assert re.search(r"\b" + fn + r"\b", host), fn
+    # the walk rule and the counters are the pixel form's (bgr_packed422.inc.hpp); the one chunk loop asks the form
+    form = re.sub(r"//[^\n]*", "", (CSRC / "host" / "bgr_packed422.inc.hpp").read_text())
+    for fn in ("bgr_packed422_frame_vec", "bgr_packed422_list_frames_vec", "bgr_packed422_list_frames_bytes"):
+        assert re.search(r"\b" + fn + r"\b", form), fn
+    assert "n_vec += F::frame_vec(shape_vec, io.f[k].in, io.f[k].out);" in host and host.count("F::count_list(c, n_frames, n_vec);") == 1
+    assert host.count("bgr_packed422_frames_entry<BgrTo422>(") == 2
+    for other in ("packed422_bgra", "bgra422", "bgra_packed422", "bgra_to_packed422"):
+        assert other not in host.lower(), "the three-channel file does not know the four-channel form"
     code = re.sub(r"//[^\n]*", "", host)
     assert "MI_K_HIST" not in code and "hist_lut_kernel" not in code, "stage 1 counts: the form has no MI_K_HIST launch"
     assert "The frame-list form (mi_*_bgr_to_packed422_frames_dev) is not built" not in (CSRC / "host" / "bgr_packed422.inc.hpp").read_text()

@@ -186,17 +186,33 @@ def test_new_sources_are_registered():
     assert "asm" not in code and "__builtin_nontemporal" not in code, "plain loads and stores, no inline assembly"
     assert re.search(r"static_assert\(sizeof\(BgraPacked422Job\)\s*\+\s*sizeof\(Packed422List\)\s*\+\s*sizeof\(uint32_t\*\)\s*\+\s*256\s*<=\s*4096", kern)
     assert re.search(r"__host__\s+__device__[^;{]*\bbgra_packed422_frame_vec\s*\(", kern), "one rule for the kernel and the host's counters"
+    # the four-channel file holds the pixel form and the extern "C" functions; the one implementation, a template on the form, is
+    # bgr_packed422.inc.hpp's
     host = (CSRC / "host" / "bgra_packed422.inc.hpp").read_text()
-    for fn in ("check_bgra_packed422", "launch_bgra_to_packed422", "bgr_packed422_in_place", "PackedOut", "clahe422_dev", "launch_pair",
-               "equalize_lut_kernel", "kBgrNv12FramesPerLaunch", "MI_K_COLOR", "check_yuv420_limits", "stage_in", "stage_out", "StreamDrain",
-               "bgra_packed422_vec", "bgra_packed422_bytes"):
-        assert re.search(r"\b" + fn + r"\b", host), fn
     hcode = re.sub(r"//[^\n]*", "", host)
+    for fn in ("struct BgraTo422", "using Job = BgraPacked422Job;", "bgra_to_packed422_hist_kernel<ORDER, OFF, UVMODE, HIST>",
+               "bgra_to_packed422_hist_frames_kernel<ORDER, OFF, UVMODE, HIST>", "bgra_packed422_frame_vec(shape_vec, in, out)",
+               "bgra_packed422_vec", "bgra_packed422_bytes", "bgr_packed422_entry<BgraTo422>"):
+        assert fn in hcode, fn
+    assert not re.search(r"\bmi_status\s+(?!mi_)\w+\s*\(", hcode), "nothing but the form and the extern \"C\" functions"
+    generic = re.sub(r"//[^\n]*", "", (CSRC / "host" / "bgr_packed422.inc.hpp").read_text())
+    for fn in ("check_bgr_packed422", "launch_bgr_to_packed422", "bgr_packed422_in_place", "PackedOut", "clahe422_dev", "launch_pair",
+               "equalize_lut_kernel", "kBgrNv12FramesPerLaunch", "MI_K_COLOR", "check_yuv420_limits", "stage_in", "stage_out", "StreamDrain"):
+        assert re.search(r"\b" + fn + r"\b", generic), fn
+    assert len(re.findall(r"template <class F(?:, int OFF)?>\s*mi_status (check_bgr_packed422|launch_bgr_to_packed422|equalize_bgr_packed422_dev|"
+                          r"clahe_bgr_packed422_dev|bgr_packed422_dev|bgr_packed422_host|bgr_packed422_entry)\(", generic)) == 7, \
+        "each written once, for every form"
+    assert "MI_K_HIST" not in generic and "hist_lut_kernel" not in generic
+    assert "F::template kernel<O, FMT, U, true>" in generic and "F::template frames_kernel<O, FMT, U, true>" in generic
     assert "MI_K_HIST" not in hcode and "hist_lut_kernel" not in hcode, "stage 1 counts: the form has no MI_K_HIST launch"
     assert not re.search(r"\bbgr_packed422_(vec|bytes|list_frames_vec|list_frames_bytes)\b", hcode), "no three-channel counter is moved"
     assert not re.search(r"\bbgr_to_packed422_hist(_frames)?_kernel\b", hcode), "stage 1 is this form's own kernel"
-    assert re.search(r"blocks_per_frame\(c, px \* 3, a\.height, nf, 2048\)", hcode), "the grid's byte basis: half of 4 + 2 bytes per pixel"
-    assert re.search(r"in_pitch < 4 \* \(size_t\)a\.width", hcode) and re.search(r"0x7fffffffLL / 4", hcode)
+    # the form's constants (bytes per pixel 4, byte basis px * 3: half of 4 + 2 bytes per pixel) and the one expression using each
+    assert "static constexpr int kPx = 4;" in hcode
+    assert re.search(r"static long long grid_bytes\(long long px\) \{ return px \* 3; \}", hcode), "the grid's byte basis"
+    assert re.search(r"blocks_per_frame\(c, F::grid_bytes\(px\), a\.height, nf, 2048\)", generic)
+    assert re.search(r"in_pitch < F::kPx \* \(size_t\)a\.width", generic) and re.search(r"0x7fffffffLL / F::kPx", generic)
+    assert 'kInPitch = "in_pitch < 4 * width"' in hcode and "fail(c, MI_ERR_BAD_ARG, F::kInPitch)" in generic
     assert (ROOT / "tools" / "bgra_to_packed422_ab.py").exists()
 
 

@@ -127,16 +127,31 @@ def test_new_sources_are_registered():
                      r"BgraPacked422Job j, Packed422List l, uint32_t\* __restrict__ partial\)", kern), "the table travels by value"
     assert re.search(r"__host__ __device__[^;{]*\bbgra_packed422_frame_vec\s*\(", kern)
     assert re.search(r"static_assert\(sizeof\(BgraPacked422Job\) \+ sizeof\(Packed422List\) \+ sizeof\(uint32_t\*\) \+ 256 <= 4096", kern)
+    # this file: the extern "C" functions on the four-channel form; the form: bgra_packed422.inc.hpp; the one check, chunk loop and
+    # entry, templates on the form: bgr_packed422_frames.inc.hpp
     host = (CSRC / "host" / "bgra_packed422_frames.inc.hpp").read_text()
-    for fn in ("check_bgra_packed422", "launch_bgra_to_packed422", "kPacked422FramesPerLaunch", "Packed422List", "PackedOut", "clahe422_dev",
-               "launch_pair", "equalize_lut_kernel", "MI_K_COLOR", "Span", "meets", "bgra_packed422_frame_vec", "mi_bgr_packed422_frame_dev",
-               "bgra_packed422_list_frames_vec", "bgra_packed422_list_frames_bytes"):
-        assert re.search(r"\b" + fn + r"\b", host), fn
     code = re.sub(r"//[^\n]*", "", host)
-    assert "MI_K_HIST" not in code and "hist_lut_kernel" not in code, "stage 1 counts: the form has no MI_K_HIST launch"
-    assert not re.search(r"\bbgr_packed422_(vec|bytes|list_frames_vec|list_frames_bytes)\b", code), "no three-channel counter is moved"
-    assert not re.search(r"\bbgra_packed422_(vec|bytes)\b", code), "list calls do not touch the per-call counters"
-    assert re.search(r"Span\(f\.in, s\.in_pitch, 4 \* w, rows\)\.meets\(Span\(f\.out, s\.out_pitch, 2 \* w, rows\)\)", code)
+    assert code.count("bgr_packed422_frames_entry<BgraTo422>(") == 2 and "mi_bgr_packed422_frame_dev" in code
+    assert not re.search(r"\bmi_status\s+(?!mi_)\w+\s*\(", code), "nothing but the extern \"C\" functions"
+    form = re.sub(r"//[^\n]*", "", (CSRC / "host" / "bgra_packed422.inc.hpp").read_text())
+    for fn in ("bgra_packed422_frame_vec", "bgra_packed422_list_frames_vec", "bgra_packed422_list_frames_bytes"):
+        assert re.search(r"\b" + fn + r"\b", form), fn
+    assert re.search(r"count_list\(mi_ctx\* c, int n_frames, unsigned long long n_vec\)\s*\{\s*c->bgra_packed422_list_frames_vec \+= n_vec;\s*"
+                     r"c->bgra_packed422_list_frames_bytes \+= \(unsigned long long\)n_frames - n_vec;\s*\}", form)
+    generic_text = (CSRC / "host" / "bgr_packed422_frames.inc.hpp").read_text()
+    for fn in ("check_bgr_packed422", "launch_bgr_to_packed422", "kPacked422FramesPerLaunch", "Packed422List", "PackedOut", "clahe422_dev",
+               "launch_pair", "equalize_lut_kernel", "MI_K_COLOR", "Span", "meets", "mi_bgr_packed422_frame_dev"):
+        assert re.search(r"\b" + fn + r"\b", generic_text), fn
+    generic = re.sub(r"//[^\n]*", "", generic_text)
+    assert "n_vec += F::frame_vec(shape_vec, io.f[k].in, io.f[k].out);" in generic and generic.count("F::count_list(c, n_frames, n_vec);") == 1
+    for txt in (code, generic):
+        assert "MI_K_HIST" not in txt and "hist_lut_kernel" not in txt, "stage 1 counts: the form has no MI_K_HIST launch"
+        assert not re.search(r"\bbgra_packed422_(vec|bytes)\b", txt), "list calls do not touch the per-call counters"
+        assert "count_call" not in txt, "list calls do not touch the per-call counters"
+    for txt in (code, form):
+        assert not re.search(r"\bbgr_packed422_(vec|bytes|list_frames_vec|list_frames_bytes)\b", txt), "no three-channel counter is moved"
+    assert 'kPx = 4;' in form
+    assert re.search(r"Span\(f\.in, s\.in_pitch, F::kPx \* w, rows\)\.meets\(Span\(f\.out, s\.out_pitch, 2 \* w, rows\)\)", generic)
 
 
 def test_the_restated_rule():

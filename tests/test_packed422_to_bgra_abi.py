@@ -139,14 +139,24 @@ def test_new_sources_are_registered_and_assert_their_sizes():
     assert tu.index('"host/packed422_bgr_frames.inc.hpp"') < tu.index('"host/packed422_bgra.inc.hpp"') \
         < tu.index('"host/packed422_bgra_frames.inc.hpp"') < tu.index('"host/pipe.inc.hpp"')
     kern = (CSRC / "kernels" / "packed422_bgra.hip.h").read_text()
-    for name in ("lut_apply422_bgra_body", "clahe_interp422_bgra_body", "clahe_interp422_bgra_global_body", "Packed422Bgra",
-                 "Strided422Bgra", "Table422Bgra", "Packed422List", "gather422", "chroma422", "load422_tail", "lut_vec",
-                 "bt601_uv_terms", "bt601_px_bgr", "bgra_dword", "interp_stage", "clahe_vec16_f32", "clahe_vec16", "clahe_px"):
+    # the LUT-apply and the interpolation body are the three-channel file's, templates on the block and a store policy; this file
+    # brings the policy, wraps them, and keeps the wide-grid fallback written out
+    for name in ("lut_apply422_bgr_body<OFF, Store422Bgra<ORDER>>", "clahe_interp422_bgr_body<FT, FMA, OFF, Store422Bgra<ORDER>>",
+                 "clahe_interp422_bgra_global_body", "Packed422Bgra", "Strided422Bgra", "Table422Bgra", "Packed422List", "Store422Bgra",
+                 "chroma422", "bt601_uv_terms", "bt601_px_bgr", "bgra_dword", "clahe_px"):
         assert name in kern, name
+    shared = (CSRC / "kernels" / "packed422_bgr.hip.h").read_text()
+    for name in ("lut_apply422_bgr_body(const Block& p, const Frames& fr,", "clahe_interp422_bgr_body(const Block& p, const Frames& fr,",
+                 "S::group(", "S::kGroupBytes", "S::kPxBytes", "gather422", "chroma422", "load422_tail", "lut_vec", "interp_stage",
+                 "clahe_vec16_f32", "clahe_vec16", "clahe_px"):
+        assert name in shared, name
     assert not re.search(r"\b(1673527|852492|409993|2116026|1220542)\b", kern), "the BT.601 arithmetic is reused, not restated"
     code = re.sub(r"//[^\n]*", "", kern)
     assert "decode422_16" not in code and "store422_px" not in code, "every pixel is one dword: none of the 48-byte packing"
     assert re.search(r"__host__\s+__device__[^;{]*\bpacked422_bgra_frame_wide\s*\(", kern), "one rule for the kernel and the host's counters"
+    assert re.search(r"\bpacked422_bgra_frame_wide\s*\([^)]*\)\s*\{\s*return packed422_image_wide\(out, out_step, out_frame\);", kern), \
+        "... which is the one rule of both image forms"
+    assert re.search(r"__host__\s+__device__[^;{]*\bpacked422_image_wide\s*\(", shared)
     assert re.search(r"static_assert\(sizeof\(Packed422Bgra\)\s*==\s*sizeof\(Packed422Bgr\)", kern)
     assert re.search(r"static_assert\(sizeof\(Packed422List\)\s*\+\s*sizeof\(Packed422Bgra\)[^;]*<=\s*4096", kern)
     # the sizes those asserts add up, restated: 128 entries of two pointers, the block of six 8-byte and three 4-byte fields
@@ -155,12 +165,30 @@ def test_new_sources_are_registered_and_assert_their_sizes():
     assert per_launch == 128 and per_launch * 16 == 2048
     block = 6 * 8 + 3 * 4 + 4                                       # padded to a multiple of 8
     assert block == 64 and 2048 + block + 256 + 256 < 4096           # ClaheGeom and the scalars are far below 256 bytes
+    # the host side: the four-channel file holds the pixel form, the three-channel file the one implementation it instantiates
     host = (CSRC / "host" / "packed422_bgra.inc.hpp").read_text()
-    for fn in ("check_packed422_bgra", "packed422_bgra_batch", "BgraOut422", "packed422_dev<BgraOut422<1>>", "packed422_dev<BgraOut422<0>>",
-               "check_packed422_bgra_host", "stage_in", "stage_out", "packed422_bgra_frame_wide", "0x7fffffffLL / 4"):
-        assert fn in host, fn
-    frames = (CSRC / "host" / "packed422_bgra_frames.inc.hpp").read_text()
-    assert "f0 += kPacked422FramesPerLaunch" in frames and "packed422_bgra_frame_wide" in frames
+    hcode = re.sub(r"//[^\n]*", "", host)
+    for fn in ("struct Bgra422Image", "static constexpr int kPx = 4;", "using Block = Packed422Bgra;", "check_packed422_bgr<Bgra422Image>",
+               "packed422_bgr_call<Bgra422Image>", "check_packed422_bgr_host<Bgra422Image>", "packed422_bgr_host<Bgra422Image>",
+               "lut_apply422_bgra_frames_kernel<OFF, ORDER>, lut_apply422_bgra_kernel<OFF, ORDER>",
+               "clahe_interp422_bgra_global_frames_kernel<OFF, ORDER>, clahe_interp422_bgra_global_kernel<OFF, ORDER>",
+               "clahe_interp422_bgra_frames_kernel<FT, FMA, OFF, ORDER>, clahe_interp422_bgra_kernel<FT, FMA, OFF, ORDER>"):
+        assert fn in hcode, fn
+    assert not re.search(r"\bmi_status\s+(?!mi_)\w+\s*\(", hcode), "nothing but the form and the extern \"C\" functions"
+    generic = re.sub(r"//[^\n]*", "", (CSRC / "host" / "packed422_bgr.inc.hpp").read_text())
+    for fn in ("check_packed422_bgr", "packed422_bgr_batch", "BgrOut", "packed422_dev<BgrOut<F, 1>>", "packed422_dev<BgrOut<F, 0>>",
+               "check_packed422_bgr_host", "stage_in", "stage_out", "packed422_image_wide", "0x7fffffffLL / F::kPx",
+               "a.out_pitch < F::kPx * (size_t)a.in.width", "Span(h.out, h.out_pitch, F::kPx * w, rows)", "out_row = F::kPx * w",
+               "F::count_call(c, packed422_image_wide(a.out, (long long)a.out_pitch, (long long)a.out_frame));"):
+        assert fn in generic, fn
+    assert len(re.findall(r"template <class F>\s*mi_status (check_packed422_bgr|packed422_bgr_dev|packed422_bgr_call|check_packed422_bgr_host|"
+                          r"packed422_bgr_host)\(", generic)) == 5, "each written once, for every form"
+    frames = re.sub(r"//[^\n]*", "", (CSRC / "host" / "packed422_bgra_frames.inc.hpp").read_text())
+    assert "check_packed422_bgr_frames<Bgra422Image>" in frames and "packed422_bgr_frames_dev<Bgra422Image>" in frames
+    assert not re.search(r"\bmi_status\s+(?!mi_)\w+\s*\(", frames), "nothing but the extern \"C\" functions"
+    gframes = re.sub(r"//[^\n]*", "", (CSRC / "host" / "packed422_bgr_frames.inc.hpp").read_text())
+    assert "f0 += kPacked422FramesPerLaunch" in gframes and "n_wide += packed422_image_wide(f.out, (long long)sh.out_pitch, 0);" in gframes
+    assert "F::count_list(c, n_frames, n_wide);" in gframes and "Span(f.out, s.out_pitch, F::kPx * w, rows)" in gframes
 
 
 def test_the_shared_stage_sequence_is_untouched():

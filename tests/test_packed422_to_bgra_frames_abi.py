@@ -90,10 +90,16 @@ def test_statistics_are_named_where_they_are_served():
     for s in STATS:
         assert '!strcmp(name, "%s")' % s in capi, s
     assert re.search(r"packed422_bgra_list_frames_wide\s*=\s*0\s*,\s*packed422_bgra_list_frames_bytes\s*=\s*0\s*;", ctx)
+    # the four-channel pixel form (packed422_bgra.inc.hpp) counts; the one chunk loop (packed422_bgr_frames.inc.hpp) calls it once
+    form = (CSRC / "host" / "packed422_bgra.inc.hpp").read_text()
+    assert "c->packed422_bgra_list_frames_wide += n_wide;" in form
+    assert "c->packed422_bgra_list_frames_bytes += (unsigned long long)n_frames - n_wide;" in form
+    loop = (CSRC / "host" / "packed422_bgr_frames.inc.hpp").read_text()
+    assert loop.count("F::count_list(c, n_frames, n_wide);") == 1
     frames = (CSRC / "host" / "packed422_bgra_frames.inc.hpp").read_text()
-    assert "c->packed422_bgra_list_frames_wide += n_wide;" in frames
-    assert "c->packed422_bgra_list_frames_bytes += (unsigned long long)n_frames - n_wide;" in frames
-    assert "packed422_bgr_list_frames" not in re.sub(r"//[^\n]*", "", frames), "the three-channel form's counters are not this form's"
+    assert "packed422_bgr_frames_dev<Bgra422Image>" in frames
+    for txt in (frames, form):
+        assert "packed422_bgr_list_frames" not in re.sub(r"//[^\n]*", "", txt), "the three-channel form's counters are not this form's"
 
 
 def test_binding_lists_the_symbols():

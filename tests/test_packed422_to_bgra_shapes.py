@@ -21,17 +21,28 @@ def _code(name):
 
 
 def test_the_apply_kernel_keeps_the_three_channel_walk():
-    """The carried (row, group) walk of lut_apply422_bgra_body is lut_apply422_bgr_body's, character for character (spaces aside), with
-    64 bytes a group out where that one writes 48."""
+    """The carried (row, group) walk of the four-channel LUT-apply kernels is lut_apply422_bgr_body's because it IS that body: one
+    text in packed422_bgr.hip.h, a template on the block type and a store policy, which both forms' kernels wrap -- with 64 bytes a
+    group and 4 a pixel out as Store422Bgra's constants where Store422Bgr has 48 and 3."""
     bgr, bgra = _code("packed422_bgr.hip.h"), _code("packed422_bgra.hip.h")
     for piece in ("constintG=(p.dwords+7)>>3;", "constlonglongitems=(longlong)(r1-r0)*G;", "introw=t/G,grp=t-row*G;",
                   "constintdrow=kThreads/G,dgrp=kThreads-drow*G;", "for(longlongit=t;it<items;it+=kThreads){",
                   "row+=drow;grp+=dgrp;if(grp>=G){grp-=G;++row;}", "constintnd=min(8,p.dwords-8*grp);",
-                  "constuint8_t*s=src0+(longlong)row*p.src_step+32LL*grp;"):
-        assert piece in bgr and piece in bgra, piece
-    assert "uint8_t*d=out0+(longlong)row*p.out_step+48LL*grp;" in bgr
-    assert "uint8_t*d=out0+(longlong)row*p.out_step+64LL*grp;" in bgra
-    assert "uint8_t*dst=fr.out_of(f)+4LL*x0;" in bgra and "uint8_t*dst=fr.out_of(f)+3LL*x0;" in bgr
+                  "constuint8_t*s=src0+(longlong)row*p.src_step+32LL*grp;",
+                  "uint8_t*d=out0+(longlong)row*p.out_step+(longlong)S::kGroupBytes*grp;",
+                  "uint8_t*dst=fr.out_of(f)+(longlong)S::kPxBytes*x0;"):
+        assert bgr.count(piece) == 1 and piece not in bgra, piece
+    for body in ("lut_apply422_bgr_body", "clahe_interp422_bgr_body"):
+        assert len(re.findall(r"void" + body + r"\(constBlock&p,constFrames&fr,", bgr)) == 1, body
+        assert "void" + body not in bgra and "void" + body.replace("bgr", "bgra") not in bgra, body
+    assert "template<intORDER>structStore422Bgr{staticconstexprintkPxBytes=3,kGroupBytes=48;" in bgr
+    assert "template<intORDER>structStore422Bgra{staticconstexprintkPxBytes=4,kGroupBytes=64;" in bgra
+    # every entry of the four-channel form wraps the shared body with its own policy and its own two address policies
+    for body in ("lut_apply422_bgr_body<OFF,", "clahe_interp422_bgr_body<FT,FMA,OFF,"):
+        assert bgra.count(body + "Store422Bgra<ORDER>>(p,Strided422Bgra{p},") == 1, body
+        assert bgra.count(body + "Store422Bgra<ORDER>>(p,Table422Bgra{l,p},") == 1, body
+        assert bgr.count(body + "Store422Bgr<ORDER>>(p,Strided422Bgr{p},") == 1, body
+        assert bgr.count(body + "Store422Bgr<ORDER>>(p,Table422Bgr{l,p},") == 1, body
     assert g.groups422(33) == 5 and g.groups422(8193) == 1025
 
 
