@@ -1135,6 +1135,76 @@ mi_status mi_equalize_hist_bgr_to_yuv420_frames_dev(mi_ctx* ctx, const mi_bgr_yu
 mi_status mi_clahe_bgr_to_yuv420_frames_dev(mi_ctx* ctx, const mi_bgr_yuv420_frame_dev* frames, int n_frames,
         int width, int height, size_t in_pitch, size_t y_pitch, size_t c_pitch, int chroma, int order, mi_uv_mode uv_mode,
         double clip_limit, int tiles_x, int tiles_y, void* stream);
+/* mi_*_packed422_to_yuv420*: packed 4:2:2 frames in (YUY2 / UYVY: what a capture card hands over), 4:2:0 frames described by
+ * mi_yuv420_planes out with the luma equalized -- planar chroma (I420 / YV12: the three pitched planes data[0..2] / linesize[0..2] a
+ * software encoder takes) or interleaved chroma (NV12) -- in the pass that equalizes, without an NV12 intermediate and without a
+ * de-interleave of the UV plane outside the library.  The packed frame is read twice (histograms, then map) exactly as by
+ * mi_*_packed422_to_nv12_batch_dev; the second pass writes 1.5*W*H bytes.
+ *   input  : exactly what mi_*_packed422_batch_dev takes.  `format` is MI_FMT_YUY2 or MI_FMT_UYVY; frame f lies at
+ *            d_in + f * in_frame_stride, H rows of 2*W bytes at in_pitch; the pointer, the pitch and the frame stride are multiples
+ *            of 4.  The input is never written.
+ *   output : frame f has its planes at out->y / out->c0 / out->c1 + f * out->frame_stride: Y, H rows of W bytes at y_pitch >= W;
+ *            MI_CHROMA_PLANAR: c0 is always U and c1 always V, each H/2 rows of W/2 bytes at c_pitch >= W/2 (both planes share the
+ *            pitch; a YV12 caller exchanges the two addresses).  U and V rows side by side in one pitched plane (c1 = c0 + W/2,
+ *            c_pitch = W) are legal.
+ *   luma   : byte for byte the Y plane of mi_*_packed422_to_nv12_batch_dev on the same input (same clahe_fp_contract option,
+ *            REFLECT_101 padding when the tile grid does not divide the frame, the same fallback for tile grids too wide for the LDS
+ *            pair table).
+ *   chroma : that call's UV plane de-interleaved.  MI_UV_FILL128 sets every byte of both planes to 128.  MI_UV_COPY keeps the chroma
+ *            and halves it vertically: for chroma row r, the U (and the V) sample of macropixel m is the rounding mean of input rows 2r
+ *            and 2r+1, (a + b + 1) >> 1 on the two input bytes.  No horizontal filtering and no change of siting.  OpenCV has no call
+ *            for this conversion and the reference has none: the rule is this header's own, it has no outside pin.
+ * out->chroma == MI_CHROMA_INTERLEAVED: the call IS the NV12 form's (d_y_out = out->y, d_uv_out = out->c0, uv_pitch = out->c_pitch,
+ * out_frame_stride = out->frame_stride; c1 is ignored and may be NULL): its checks, its launches, its bytes.
+ * Alignment (MI_CHROMA_PLANAR, device forms): out->y, y_pitch, c0, c1, c_pitch and frame_stride are multiples of 4.  Consequence: a
+ * TIGHT planar frame with W % 8 != 0 has a chroma pitch W/2 that is not a multiple of 4 and is refused (as the NV12 form refuses a tight
+ * W % 4 == 2 frame) -- such a caller pads the pitch, or uses the host form.
+ * Nothing outside the W bytes of each Y row and the W/2 bytes of each chroma row is written: not the pitch padding, not the space
+ * between the planes, not the gap between frames.  `width` and `height` are even.
+ * Stream rules, MI_STREAM_CTX, MI_ERR_BUSY while the context's pipe has frames pending and hipGraph capture after one eager call of
+ * the same shape as mi_*_packed422_to_nv12_batch_dev.  Never the fused equalizeHist kernel nor the single-launch histogram + LUT
+ * kernel; exactly the launches the NV12 form makes per chunk (equalizeHist: one MI_K_HIST, one MI_K_EQ_LUT and one MI_K_LUT_APPLY
+ * launch, for either uv_mode): the chroma is written by the launch that writes the luma, there is no chroma launch.
+ * Errors, MI_ERR_BAD_ARG: a null ctx, a null `out`, a chroma other than the two values, any null frame or plane pointer (a null c1 on
+ * a planar output included), an odd width or an odd height (refused even when another size is 0), a negative size, in_pitch < 2*W,
+ * y_pitch < W, a c_pitch below its row (W interleaved, W/2 planar), any pointer / pitch / stride that is not a multiple of 4, a format
+ * other than the two, a bad uv_mode, tiles <= 0, two output planes at one address, an output plane whose rows meet the rows of its
+ * own frame's input or a Y plane whose rows meet a chroma plane of its own frame (there is no in-place form; U and V are compared by
+ * address only, so that the side-by-side layout stays legal).  width, height or n_frames of 0: MI_OK, nothing written.  Sizes and tile
+ * grids the planar forms refuse: the status they give (MI_ERR_UNSUPPORTED), nothing written.  Outputs of DIFFERENT frames that overlap
+ * each other: undefined, not checked.  Nothing is enqueued unless all checks pass.
+ *
+ * mi_*_packed422_to_yuv420_frames_dev: the same conversion on a LIST of device frames, each at its own four addresses {in, y, c0, c1}
+ * (a capture device's buffer pool in, a software encoder's frame pool out).  `frames` is a host array of n_frames entries, read only
+ * during the call.  Every frame of one call has the same width, height, format, out_chroma and the same three pitches.  Every address
+ * and every pitch is a multiple of 4; each frame may have its own alignment modulo 16 (different bytes never).  The same input may
+ * appear in several entries.  Per frame the bytes are the batch form's.  out_chroma == MI_CHROMA_INTERLEAVED: the call IS
+ * mi_*_packed422_to_nv12_frames_dev on {in, y, c0} with uv_pitch = c_pitch.  Errors as above per entry, and a null `frames` with
+ * n_frames > 0; nothing is enqueued unless every frame passes the checks: a bad last entry leaves the first frames' outputs untouched.
+ *
+ * mi_equalize_hist_packed422_to_yuv420 / mi_clahe_packed422_to_yuv420: ONE host frame, synchronous.  The input side follows the rules of
+ * mi_*_packed422 (`in` and in_pitch multiples of 4, in_pitch >= 2*W).  `out` holds host pointers the kernels never see: any address,
+ * y_pitch any value >= W and c_pitch any value >= W/2 -- a tight frame with W % 8 != 0 is accepted; frame_stride is ignored.  Staged
+ * like mi_*_packed422_to_nv12 with three output planes: the device planes lie at pitches align4(W) and align4(W/2); pinned tight planes
+ * whose device rows are tight too are DMA'd as they are, everything else goes through the context's pinned staging (statistics
+ * "host_planes_direct" / "host_planes_staged", four planes a planar call).  MI_ERR_BAD_ARG when the rows of an output plane meet the
+ * rows of the input or the Y rows those of a chroma plane; shape, mode, size and zero-size rules as the device form above. */
+mi_status mi_equalize_hist_packed422_to_yuv420_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        const mi_yuv420_planes* out, int width, int height, int n_frames, int format, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_packed422_to_yuv420_batch_dev(mi_ctx* ctx, const void* d_in, size_t in_pitch, size_t in_frame_stride,
+        const mi_yuv420_planes* out, int width, int height, int n_frames, int format, mi_uv_mode uv_mode,
+        double clip_limit, int tiles_x, int tiles_y, void* stream);
+mi_status mi_equalize_hist_packed422_to_yuv420(mi_ctx* ctx, const uint8_t* in, size_t in_pitch, const mi_yuv420_planes* out,
+        int width, int height, int format, mi_uv_mode uv_mode);
+mi_status mi_clahe_packed422_to_yuv420(mi_ctx* ctx, const uint8_t* in, size_t in_pitch, const mi_yuv420_planes* out,
+        int width, int height, int format, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y);
+typedef mi_bgr_yuv420_frame_dev mi_packed422_yuv420_frame_dev;       /* { in, y, c0, c1 } */
+mi_status mi_equalize_hist_packed422_to_yuv420_frames_dev(mi_ctx* ctx, const mi_packed422_yuv420_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t y_pitch, size_t c_pitch, int out_chroma,
+        int format, mi_uv_mode uv_mode, void* stream);
+mi_status mi_clahe_packed422_to_yuv420_frames_dev(mi_ctx* ctx, const mi_packed422_yuv420_frame_dev* frames, int n_frames,
+        int width, int height, size_t in_pitch, size_t y_pitch, size_t c_pitch, int out_chroma,
+        int format, mi_uv_mode uv_mode, double clip_limit, int tiles_x, int tiles_y, void* stream);
 /* mi_*_bgr_to_packed422*: interleaved 8-bit BGR (or RGB) images in, packed 4:2:2 frames (YUY2 / UYVY) out with the luma equalized --
  * renderer, model output or image reader -> SDI / HDMI playout card, v4l2 output or loopback device, virtual camera, without an NV12
  * intermediate (which has already dropped every second chroma row) and without an interleave outside the library.

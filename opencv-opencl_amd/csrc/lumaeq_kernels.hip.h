@@ -32,6 +32,8 @@
 //   kernels/p010.hip.h            chroma half of 16-bit 4:2:0 frames (P010 / P012 / P016): copy or fill 0x8000
 //   kernels/packed422.hip.h       the pixel-touching stages on packed 4:2:2 frames (YUY2 / UYVY): luma at a 2-byte sample stride
 //   kernels/packed422_nv12.hip.h  the pixel-writing stages of packed 4:2:2 in, NV12 out: Y plane + vertically halved chroma in one pass
+//   kernels/packed422_yuv420.hip.h the pixel-writing stages of packed 4:2:2 in, planar 4:2:0 (I420 / YV12) out: that walk, the halved chroma
+//                                  de-interleaved in registers and stored into a U and a V plane
 //   kernels/nv12_bgr.hip.h         the pixel-writing stages of NV12 in, interleaved BGR / RGB out: LUT apply + decode, CLAHE blend + decode
 //   kernels/bgr_nv12.hip.h         stage 1 of interleaved BGR / RGB in, NV12 out: convert into pitched planes and count the luma written
 //   kernels/bgr_yuv420.hip.h       that stage with planar 4:2:0 (I420 / YV12) out: the chroma stored into a U and a V plane
@@ -68,6 +70,7 @@
 #include "kernels/p010.hip.h"
 #include "kernels/packed422.hip.h"
 #include "kernels/packed422_nv12.hip.h"
+#include "kernels/packed422_yuv420.hip.h"
 #include "kernels/nv12_bgr.hip.h"
 #include "kernels/bgr_nv12.hip.h"
 #include "kernels/bgr_yuv420.hip.h"

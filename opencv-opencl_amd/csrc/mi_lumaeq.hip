@@ -47,6 +47,8 @@ using namespace mi;
 #include "host/packed422_frames.inc.hpp"   // packed 4:2:2 frames as a list of pitched buffers (a capture device's buffer pool)
 #include "host/packed422_nv12.inc.hpp"     // packed 4:2:2 frames in, NV12 frames out (capture card -> encoder in one pass)
 #include "host/packed422_nv12_frames.inc.hpp"   // ... as lists of pitched device frames (buffer pool in, surface pool out) and as one host frame
+#include "host/packed422_yuv420.inc.hpp"   // packed 4:2:2 frames in, planar 4:2:0 (I420 / YV12) or NV12 out (capture card -> software encoder in one pass)
+#include "host/packed422_yuv420_frames.inc.hpp"   // ... as lists of pitched device frames (buffer pool in, frame pool out) and as one host frame
 #include "host/packed422_bgr.inc.hpp"      // packed 4:2:2 frames in, interleaved BGR / RGB out, every row with its own chroma (capture card -> display / writer / model)
 #include "host/packed422_bgr_frames.inc.hpp"   // ... as a list of pitched device frames (a capture device's buffer pool in, an image pool out)
 #include "host/nv12_bgr.inc.hpp"       // NV12 frames in, interleaved BGR / RGB out in the pass that maps the luma (decoder -> display / writer / model)

@@ -627,6 +627,26 @@ inline void claheBGRToYUV420(const unsigned char* in, size_t inStep, const YUV42
     detail::check(c, mi_clahe_bgr_to_yuv420(c, in, inStep, &b, width, height, (int)order, (mi_uv_mode)uv, clipLimit, tiles.width,
                                             tiles.height), "mi_clahe_bgr_to_yuv420");
 }
+// equalizeHistPacked422ToNV12 / clahePacked422ToNV12 with the planes of the view out (they stand here because the view does): one
+// packed 4:2:2 host frame at inPitch (a multiple of 4) in; the Y plane, U into out.c0 and V into out.c1 -- the chroma halved vertically
+// with rounding (UV_COPY) or 128 (UV_FILL128) -- in host memory at any address and any pitch: a capture card's frame -> the three
+// pitched planes a software encoder takes, without an NV12 frame in between.  An interleaved view gives what the NV12 wrappers give.
+inline void equalizeHistPacked422ToYUV420(const unsigned char* in, size_t inPitch, const YUV420View& out, int width, int height,
+                                          PackedFormat format = FMT_YUY2, UVMode uv = UV_COPY)
+{
+    mi_ctx* c = detail::thread_ctx();
+    const mi_yuv420_planes b = out.planes();
+    detail::check(c, mi_equalize_hist_packed422_to_yuv420(c, in, inPitch, &b, width, height, (int)format, (mi_uv_mode)uv),
+                  "mi_equalize_hist_packed422_to_yuv420");
+}
+inline void clahePacked422ToYUV420(const unsigned char* in, size_t inPitch, const YUV420View& out, int width, int height, double clipLimit,
+                                   Size tiles, PackedFormat format = FMT_YUY2, UVMode uv = UV_COPY)
+{
+    mi_ctx* c = detail::thread_ctx();
+    const mi_yuv420_planes b = out.planes();
+    detail::check(c, mi_clahe_packed422_to_yuv420(c, in, inPitch, &b, width, height, (int)format, (mi_uv_mode)uv, clipLimit, tiles.width,
+                                                  tiles.height), "mi_clahe_packed422_to_yuv420");
+}
 // The same edge for four-byte pixels: one interleaved CV_8UC4 host image (BGRA / BGRX, or RGBA / RGBX) at inStep >= 4*W in, the planes
 // of the view out: cv::cvtColor(COLOR_BGRA2YUV_I420) + cv::equalizeHist / CLAHE::apply on the Y plane; the fourth byte takes no part.
 // A render target's or a screen capture's surface -> an encoder's planes, without a three-channel copy in between.  Planar and

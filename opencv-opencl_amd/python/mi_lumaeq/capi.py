@@ -54,6 +54,9 @@ DECLARED_SYMBOLS = [
     "mi_equalize_hist_packed422_to_nv12_batch_dev", "mi_clahe_packed422_to_nv12_batch_dev",
     "mi_equalize_hist_packed422_to_nv12_frames_dev", "mi_clahe_packed422_to_nv12_frames_dev",
     "mi_equalize_hist_packed422_to_nv12", "mi_clahe_packed422_to_nv12",
+    "mi_equalize_hist_packed422_to_yuv420_batch_dev", "mi_clahe_packed422_to_yuv420_batch_dev",
+    "mi_equalize_hist_packed422_to_yuv420", "mi_clahe_packed422_to_yuv420",
+    "mi_equalize_hist_packed422_to_yuv420_frames_dev", "mi_clahe_packed422_to_yuv420_frames_dev",
     "mi_equalize_hist_packed422_to_bgr_batch_dev", "mi_clahe_packed422_to_bgr_batch_dev",
     "mi_equalize_hist_packed422_to_bgr", "mi_clahe_packed422_to_bgr",
     "mi_equalize_hist_packed422_to_bgr_frames_dev", "mi_clahe_packed422_to_bgr_frames_dev",
@@ -338,6 +341,12 @@ def _load(p: Path) -> C.CDLL:
     L.mi_clahe_yuv420_batch_dev.argtypes = [vp, yp, yp, i, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_yuv420.argtypes = [vp, yp, yp, i, i, i]
     L.mi_clahe_yuv420.argtypes = [vp, yp, yp, i, i, i, d, i, i]
+    L.mi_equalize_hist_packed422_to_yuv420_batch_dev.argtypes = [vp, vp, sz, sz, yp, i, i, i, i, i, vp]
+    L.mi_clahe_packed422_to_yuv420_batch_dev.argtypes = [vp, vp, sz, sz, yp, i, i, i, i, i, d, i, i, vp]
+    L.mi_equalize_hist_packed422_to_yuv420.argtypes = [vp, vp, sz, yp, i, i, i, i]
+    L.mi_clahe_packed422_to_yuv420.argtypes = [vp, vp, sz, yp, i, i, i, i, d, i, i]
+    L.mi_equalize_hist_packed422_to_yuv420_frames_dev.argtypes = [vp, C.POINTER(BgrYuv420FrameDev), i, i, i, sz, sz, sz, i, i, i, vp]
+    L.mi_clahe_packed422_to_yuv420_frames_dev.argtypes = [vp, C.POINTER(BgrYuv420FrameDev), i, i, i, sz, sz, sz, i, i, i, d, i, i, vp]
     L.mi_equalize_hist_yuv420_frames_dev.argtypes = [vp, C.POINTER(Yuv420FrameDev), i, i, i, sz, sz, i, sz, sz, i, i, vp]
     L.mi_clahe_yuv420_frames_dev.argtypes = [vp, C.POINTER(Yuv420FrameDev), i, i, i, sz, sz, i, sz, sz, i, i, d, i, i, vp]
     L.mi_equalize_hist_yuv420_to_bgr_batch_dev.argtypes = [vp, yp, vp, sz, sz, i, i, i, i, vp]
@@ -1021,6 +1030,79 @@ class Context:
                                                    uv_out.ctypes.data, _step(uv_out), int(width), int(h), int(fmt), int(uv_mode),
                                                    float(clip_limit), int(tiles_x), int(tiles_y)), "mi_clahe_packed422_to_nv12")
         return y_out, uv_out
+
+    # ---- packed 4:2:2 in, 4:2:0 frames (I420 / YV12 planes, or NV12) out: the halved chroma de-interleaved by the launch that writes the luma ----
+    def equalize_hist_packed422_to_yuv420_batch_dev(self, d_in, dst, width, height, n_frames, fmt=FMT_YUY2, uv_mode=UV_COPY,
+                                                    in_pitch=None, in_frame=None, stream=0):
+        """mi_equalize_hist_packed422_to_yuv420_batch_dev.  d_in: the packed frames (a torch tensor or a raw address); dst: a
+        Yuv420Planes holding device addresses (Yuv420Planes.i420 / .yv12 / .nv12 for tight batches, the fields themselves for pitched
+        or separately allocated planes).  The tight input is the default: in_pitch 2*W, in_frame = in_pitch * H."""
+        ip = 2 * int(width) if in_pitch is None else int(in_pitch)
+        fi = ip * int(height) if in_frame is None else int(in_frame)
+        self._chk(self._L.mi_equalize_hist_packed422_to_yuv420_batch_dev(self._h, _dptr(d_in), ip, fi, C.byref(dst), int(width),
+                                                                       int(height), int(n_frames), int(fmt), int(uv_mode), stream),
+                  "mi_equalize_hist_packed422_to_yuv420_batch_dev")
+
+    def clahe_packed422_to_yuv420_batch_dev(self, d_in, dst, width, height, n_frames, fmt=FMT_YUY2, uv_mode=UV_COPY, clip_limit=2.0,
+                                            tiles_x=8, tiles_y=8, in_pitch=None, in_frame=None, stream=0):
+        """mi_clahe_packed422_to_yuv420_batch_dev; arguments as equalize_hist_packed422_to_yuv420_batch_dev, plus the CLAHE parameters."""
+        ip = 2 * int(width) if in_pitch is None else int(in_pitch)
+        fi = ip * int(height) if in_frame is None else int(in_frame)
+        self._chk(self._L.mi_clahe_packed422_to_yuv420_batch_dev(self._h, _dptr(d_in), ip, fi, C.byref(dst), int(width), int(height),
+                                                               int(n_frames), int(fmt), int(uv_mode), float(clip_limit), int(tiles_x),
+                                                               int(tiles_y), stream), "mi_clahe_packed422_to_yuv420_batch_dev")
+
+    def equalize_hist_packed422_to_yuv420_frames_dev(self, frames, width, height, in_pitch, y_pitch, c_pitch, chroma, fmt=FMT_YUY2,
+                                                     uv_mode=UV_COPY, stream=0):
+        """mi_equalize_hist_packed422_to_yuv420_frames_dev.  frames: BgrYuv420FrameDev entries {in, y, c0, c1}, one per frame, every
+        packed frame and every plane at its own device address (a capture pool in, a software encoder's frame pool out); one shape, one
+        set of pitches and one chroma layout for the call."""
+        arr, n = self._bgr_yuv420_list(frames)
+        self._chk(self._L.mi_equalize_hist_packed422_to_yuv420_frames_dev(self._h, arr, n, int(width), int(height), int(in_pitch),
+                                                                        int(y_pitch), int(c_pitch), int(chroma), int(fmt), int(uv_mode),
+                                                                        stream), "mi_equalize_hist_packed422_to_yuv420_frames_dev")
+
+    def clahe_packed422_to_yuv420_frames_dev(self, frames, width, height, in_pitch, y_pitch, c_pitch, chroma, fmt=FMT_YUY2,
+                                             uv_mode=UV_COPY, clip_limit=2.0, tiles_x=8, tiles_y=8, stream=0):
+        """mi_clahe_packed422_to_yuv420_frames_dev; arguments as equalize_hist_packed422_to_yuv420_frames_dev, plus the CLAHE parameters."""
+        arr, n = self._bgr_yuv420_list(frames)
+        self._chk(self._L.mi_clahe_packed422_to_yuv420_frames_dev(self._h, arr, n, int(width), int(height), int(in_pitch), int(y_pitch),
+                                                                int(c_pitch), int(chroma), int(fmt), int(uv_mode), float(clip_limit),
+                                                                int(tiles_x), int(tiles_y), stream),
+                  "mi_clahe_packed422_to_yuv420_frames_dev")
+
+    def _packed422_yuv420_host(self, frame, width, dst_fmt, out, planes, name):
+        frame = self._packed_host(frame, width, name)
+        h, w = frame.shape[0], int(width)
+        if planes is not None:
+            return frame, h, None, planes
+        if dst_fmt not in _YUV420_FMTS:
+            raise MiError(1, name, 'dst_fmt must be "nv12", "i420" or "yv12"')
+        if out is None:
+            out = np.empty(w * h * 3 // 2, np.uint8)
+        if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.size == w * h * 3 // 2):
+            raise MiError(1, name, "out is a contiguous uint8 array of W*H*3/2 bytes")
+        return frame, h, out, _YUV420_FMTS[dst_fmt](out.ctypes.data, w, h)
+
+    def equalize_hist_packed422_to_yuv420(self, frame: np.ndarray, width: int, dst_fmt: str = "i420", fmt: int = FMT_YUY2,
+                                          uv_mode: int = UV_COPY, out: np.ndarray | None = None, planes: Yuv420Planes | None = None):
+        """mi_equalize_hist_packed422_to_yuv420 on a host frame: an H x pitch-bytes uint8 array (pitch >= 2*W) in, the tight frame of
+        W*H*3/2 bytes out, its chroma laid out as dst_fmt in {"nv12", "i420", "yv12"} says -- `out` when given, else a new array.
+        `planes`: a Yuv420Planes of host addresses (any address, any pitch) to write instead; nothing is returned then."""
+        frame, h, out, b = self._packed422_yuv420_host(frame, width, dst_fmt, out, planes, "equalize_hist_packed422_to_yuv420")
+        self._chk(self._L.mi_equalize_hist_packed422_to_yuv420(self._h, frame.ctypes.data, _step(frame), C.byref(b), int(width), int(h),
+                                                             int(fmt), int(uv_mode)), "mi_equalize_hist_packed422_to_yuv420")
+        return out
+
+    def clahe_packed422_to_yuv420(self, frame: np.ndarray, width: int, dst_fmt: str = "i420", fmt: int = FMT_YUY2,
+                                  uv_mode: int = UV_COPY, clip_limit: float = 2.0, tiles_x: int = 8, tiles_y: int = 8,
+                                  out: np.ndarray | None = None, planes: Yuv420Planes | None = None):
+        """mi_clahe_packed422_to_yuv420; arguments as equalize_hist_packed422_to_yuv420, plus the CLAHE parameters."""
+        frame, h, out, b = self._packed422_yuv420_host(frame, width, dst_fmt, out, planes, "clahe_packed422_to_yuv420")
+        self._chk(self._L.mi_clahe_packed422_to_yuv420(self._h, frame.ctypes.data, _step(frame), C.byref(b), int(width), int(h),
+                                                     int(fmt), int(uv_mode), float(clip_limit), int(tiles_x), int(tiles_y)),
+                  "mi_clahe_packed422_to_yuv420")
+        return out
 
     # ---- packed 4:2:2 in, interleaved BGR / RGB out in the pass that maps the luma: every row keeps its own chroma ----
     def equalize_hist_packed422_to_bgr_batch_dev(self, d_in, d_out, width, height, n_frames, fmt=FMT_YUY2, order=ORDER_BGR,
