@@ -7,13 +7,14 @@ The walks of kernels/packed422*.hip.h restated (W even, dwords = W / 2 macropixe
   lut_apply422            the same walk cut at the destination row, a step is 4 * 256 items
   lut_apply422_nv12       band of row PAIRS, (pair, group) items with G = (dwords + 7) >> 3 groups of 16 columns, a step is 256 items
   lut_apply422_bgr        band of rows, (row, group) items with the same G, a step is 256 items
+  lut_apply422_yuv420     (kernels/packed422_yuv420.hip.h) lut_apply422_nv12's arithmetic: row pairs, the same G, a step is 256 items
   tile_hist422            one tile per workgroup (512 lanes), (row, slot) items over the tile's dwords, a step is 4 * 512 items
 A band is rows [units * b / B, units * (b + 1) / B); B <= max(1, floor(2*W*H / 16384)) and, when units > 1, B <= units."""
 import numpy as np
 
 FMT_YUY2, FMT_UYVY = 2, 3
 UV_FILL128, UV_COPY = 0, 1
-FORMS = ("packed", "nv12", "bgr")
+FORMS = ("packed", "nv12", "bgr", "yuv420")
 EQ = ("eq", None)
 
 
@@ -63,7 +64,7 @@ def walk(kernel, w, h, grid=None):
     dwords = w // 2
     if kernel in ("hist422_partial", "lut_apply422"):
         units, per, step = h, slots422(dwords), 4 * 256
-    elif kernel == "lut_apply422_nv12":
+    elif kernel in ("lut_apply422_nv12", "lut_apply422_yuv420"):
         units, per, step = h // 2, groups422(dwords), 256
     elif kernel == "lut_apply422_bgr":
         units, per, step = h, groups422(dwords), 256
@@ -84,10 +85,25 @@ PHASE_SRC = dict(extra=4, gap=4)                # pitch 2W + 4: the source phase
 PHASE_DST = dict(extra=8, gap=12)               # pitch 2W + 8: the destination phase advances by 8 a row
 PHASE_OPS = (EQ, ("clahe", (2.0, 2, 2)), ("clahe", (2.0, 64, 2)))      # LUT apply; LDS interpolation; the wide-grid kernel
 BGR_BASES = (0, 1, 4, 16)
+# planar 4:2:0 out: y_pitch W + 4 = 44 (the Y phase advances by 12 a row), c_pitch W / 2 + 4 = 24 (the chroma phases advance by 8)
+PHASE_YUV420 = dict(ye=4, ce=4)
+
+# every length of the ragged chroma tail: 33 .. 40 macropixels a row, so the last group of a row holds 1, 2, ..., 8
+TAIL_WIDTHS = (66, 68, 70, 72, 74, 76, 78, 80)
+TAIL_H, TAIL_N = 4, 2
+TAIL_OPS = (EQ, ("clahe", (2.0, 2, 2)), ("clahe", (2.0, 64, 2)))
+TAIL_DST = ("one", 4, 4, 4, (8, 12))            # a planar layout (below): Y / U / V at phases 4 / 8 / 12, padded pitches
+
+
+def tail_dwords(dwords):
+    """Macropixels in the last group of a row: the nd of the writers' last (pair, group) item."""
+    return min(8, dwords - 8 * (groups422(dwords) - 1))
 
 
 # ---- group 2: walks past their first step ----------------------------------------------------------------------------------------
-# (extra, gap, off) as the Batch class of the packed-in test modules takes them
+# (extra, gap, off) as the Batch class of the packed-in test modules takes them; a planar 4:2:0 destination is
+# (kind, y_off, y_pitch - align4(W), c_pitch - align4(W / 2), (phase of the first chroma plane, of the second)) as
+# test_gpu_packed422_to_yuv420.PlanarOut takes them
 TIGHT, P4 = (0, 0, 0), (4, 0, 4)
 CL22 = ("clahe", (2.0, 2, 2))
 LOOP_SHAPES = [
@@ -121,6 +137,14 @@ LOOP_SHAPES = [
     # lut_apply422_bgr steps by 256 (row, group) items.  2WH / 16384 = 3.1: up to three bands of 128 / 129 / 129 rows; G = 5, drow 51,
     # dgrp 1: 640 / 645 / 645 items, three steps each, and the group wraps into the next row; two frames
     dict(id="66x386-bgr", form="bgr", w=66, h=386, n=2, sl=(4, 4, 4), dl=TIGHT, ops=(EQ, CL22), walks=("hist422_partial", "lut_apply422_bgr")),
+    # lut_apply422_yuv420 steps by 256 (row pair, group) items.  193 row pairs in up to three bands of 64 / 64 / 65; G = 5, dpr 51,
+    # dgrp 1: 320 / 320 / 325 items, two steps each, and the group wraps into the next pair; two frames 4 bytes apart
+    dict(id="66x386-yuv420", form="yuv420", w=66, h=386, n=2, sl=(4, 4, 4), dl=("one", 4, 4, 4, (8, 12)), ops=(EQ, CL22),
+         walks=("hist422_partial", "lut_apply422_yuv420")),
+    # as 16386x2-nv12 -- one row pair, up to four apply bands, three of them without a pair; G = 1025, five steps -- with the source
+    # and the three planes each at a phase of its own
+    dict(id="16386x2-yuv420", form="yuv420", w=16386, h=2, n=1, sl=P4, dl=("one", 8, 4, 4, (12, 0)), ops=(EQ, ("clahe", (2.0, 2, 1))),
+         walks=("hist422_partial", "lut_apply422_yuv420")),
 ]
 
 # tile_hist422_body: CLAHE with a 1 x 1 grid, the largest tile a size allows.  The row split of launch_tile_luts422 is not observable; it
@@ -149,6 +173,12 @@ HEAD_DST = (12, 8, 12)         # pitch 2W + 12 at offset 12
 HEAD_OPS = (EQ, ("clahe", (2.0, 1, 1)))
 
 
+def head_yuv420(w):
+    """Planar 4:2:0 out on the short rows: chroma rows of 1, 2 and 3 bytes (a byte; a 2-byte store; a 2-byte store and a byte) at a
+    chroma pitch of 8, 4 and 8; Y / U / V at offsets 12 / 8 / 4."""
+    return ("one", 12, 12, 4 * ((w // 2) & 1), (8, 4))
+
+
 def row_addresses(w, h, n, layout):
     """Byte addresses (relative to a 16-byte aligned allocation) of every row of a batch in a (extra, gap, off) layout."""
     extra, gap, off = layout
@@ -166,7 +196,8 @@ def draw_case(rng, form):
     """One case.  W even in [2, 160]: half of the cases force a multiple of 16, a quarter W % 4 == 2.  H in [1, 48] (rounded up to
     even for NV12 out), 1..3 frames, the op, a grid in [1, 16] x [1, 5] with tiles_x = 64 one time in eight (and, one time in sixteen,
     a grid the planar form refuses), a clip limit, the format, the UV mode (BGR out: the channel order), and two independent layouts:
-    pitch paddings in 4 * [0, 10], offsets and gaps in 4 * [0, 7].  Every form draws the same numbers from the same seed."""
+    pitch paddings in 4 * [0, 10], offsets and gaps in 4 * [0, 7].  Every form draws the same numbers from the same seed.  Planar
+    4:2:0 out rounds H up to even too, and takes its chroma planes from extra2, phase2, own and byte alone (yuv420_layout)."""
     w = 2 * int(rng.integers(1, 81))
     u = rng.random()
     if u < 0.5:
@@ -174,7 +205,7 @@ def draw_case(rng, form):
     elif u < 0.75:
         w = 4 * int(rng.integers(0, 40)) + 2
     h = int(rng.integers(1, 49))
-    if form == "nv12":
+    if form in ("nv12", "yuv420"):
         h += h & 1
     n = int(rng.integers(1, 4))
     kind = "clahe" if rng.random() < 0.8 else "eq"
@@ -196,7 +227,19 @@ def draw_case(rng, form):
         case.update(uv_extra=extra2, uv_phase=phase2, uv_own=own)
     if form == "bgr":           # one case in four moves the image to an odd base and an odd pitch: byte stores
         case.update(byte=bool(byte))
+    if form == "yuv420":        # the chroma planes: their pitch padding, the U phase, one allocation or three, YV12 order
+        case.update(c_extra=extra2, u_phase=phase2, c_own=own, yv12=bool(byte))
     return case
+
+
+def yuv420_layout(case):
+    """The planar destination of a yuv420 sweep case, as LOOP_SHAPES writes one: Y from dl (pitch padding and offset), the chroma
+    pitch padded by c_extra, U at u_phase, V four bytes on (modulo 16) or, when c_extra is an odd multiple of 4, four bytes back; the
+    planes in three allocations (c_own), or in one, where yv12 puts V's address below U's."""
+    u = case["u_phase"]
+    v = (u + (4 if (case["c_extra"] >> 2) & 1 == 0 else 12)) % 16
+    kind = "own" if case["c_own"] else ("yv12" if case["yv12"] else "one")
+    return (kind, case["dl"][2], case["dl"][0], case["c_extra"], (v, u) if kind == "yv12" else (u, v))
 
 
 def sweep_cases(form, seed=SWEEP_SEED):

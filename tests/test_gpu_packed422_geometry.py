@@ -1,10 +1,11 @@
-"""Packed 4:2:2 in (YUY2 / UYVY) -- packed, NV12 and BGR / RGB out -- at the shapes where the kernels of kernels/packed422.hip.h,
-packed422_nv12.hip.h and packed422_bgr.hip.h repeat themselves: source and destination rows at different 16-byte phases, carried
+"""Packed 4:2:2 in (YUY2 / UYVY) -- packed, NV12, BGR / RGB and planar 4:2:0 (I420 / YV12) out -- at the shapes where the kernels of
+kernels/packed422.hip.h, packed422_nv12.hip.h, packed422_bgr.hip.h and packed422_yuv420.hip.h repeat themselves: source and destination rows at different 16-byte phases, carried
 (row, slot) walks past their first step, bands without rows, rows shorter than their head, frame lists whose frames each have their
 own phase, and a seeded sweep with a class census.  test_gpu_packed422.py, test_gpu_packed422_to_nv12.py and test_gpu_packed422_to_bgr.py
 cover layouts, errors, graphs and the big sizes with one layout for both sides of a call; their Batch / Nv12Out / BgrOut classes, their
 expected_frame / expected_planes builders, run and planar_status are used here unchanged (as P, N and B), and packed422_bgr_ref.expected
-builds the images.  Every comparison is exact: the whole sentinel-filled output allocation(s), 64 guard bytes included, against the
+builds the images; the planar 4:2:0 form takes PlanarOut, expected_planes and run of test_gpu_packed422_to_yuv420.py (as Y) the same
+way.  Every comparison is exact: the whole sentinel-filled output allocation(s), 64 guard bytes included, against the
 image built from oracle.equalize_hist / oracle.clahe, and the whole input allocation against what was uploaded.  Luma and chroma are
 full-range bytes of np.random.default_rng, drawn independently; every batch (every pair of calls on a one-frame batch) holds one such
 frame and one compressed to (x // 3) + 40, on which a dword that was not mapped, or mapped twice, cannot equal its expected value.
@@ -23,6 +24,8 @@ is walked as items, a step at a time, the position carried from step to step (ro
     lut_apply422_nv12               items (row pair, group), G = (W/2 + 7) >> 3 groups of 16 columns, step 256
     lut_apply422_bgr                items (row, group), the same G, step 256 (kThreads lanes, one item a lane and step; a group is
                                      two 16-byte loads, 16 pixels decoded, 48 bytes stored; the last group of a row may be ragged)
+    lut_apply422_yuv420             lut_apply422_nv12's walk; a group leaves as two 16-byte Y stores and an 8-byte store into the U and
+                                     into the V row, the ragged last group of a row as a dword, a 2-byte store and a byte
 tests/packed422_geometry_cases.py holds the shapes with these numbers worked out next to each, and
 tests/test_packed422_geometry_shapes.py asserts them on the CPU."""
 import numpy as np
@@ -35,6 +38,8 @@ import packed422_geometry_cases as g
 import test_gpu_packed422 as P
 import test_gpu_packed422_to_nv12 as N
 import test_gpu_packed422_to_bgr as B
+import test_gpu_packed422_to_yuv420 as Y                # helpers only: PlanarOut, expected_planes, run
+from mi_lumaeq.capi import BgrYuv420FrameDev, CHROMA_PLANAR
 from mi_lumaeq import UV_COPY, UV_FILL128, FMT_YUY2, FMT_UYVY, ORDER_BGR, ORDER_RGB
 
 pytestmark = pytest.mark.gpu
@@ -43,7 +48,7 @@ FMTS = [FMT_YUY2, FMT_UYVY]
 UVS = [UV_COPY, UV_FILL128]
 ORDERS = [ORDER_BGR, ORDER_RGB]
 KEY = "packed422-geometry"
-assert (g.FMT_YUY2, g.FMT_UYVY, g.UV_FILL128, g.UV_COPY) == (FMT_YUY2, FMT_UYVY, UV_FILL128, UV_COPY) and N.SENT == B.SENT == SENT
+assert (g.FMT_YUY2, g.FMT_UYVY, g.UV_FILL128, g.UV_COPY) == (FMT_YUY2, FMT_UYVY, UV_FILL128, UV_COPY) and N.SENT == B.SENT == Y.SENT == SENT
 
 
 @pytest.fixture(scope="module")
@@ -107,7 +112,7 @@ def align4(x):
     return (x + 3) & ~3
 
 
-# ---- the three forms, each with a source layout and a destination layout of its own -----------------------------------------------
+# ---- the four forms, each with a source layout and a destination layout of its own -----------------------------------------------
 def check_packed(c, w, h, n, seed, fmt, uv, op, sl, dl, in_place=False):
     """sl, dl: (pitch - 2W, gap between frames, base offset) of the source and of the destination batch."""
     for flip in variants(n):
@@ -185,6 +190,28 @@ def check_bgr(c, w, h, n, seed, fmt, order, op, sl, dl):
         assert np.array_equal(got, src.image(frames)), (why, "the input allocation was written", first_bad(got, src.image(frames)))
 
 
+def planar_out(w, h, n, dl):
+    """dl: (kind, y_off, y_pitch - align4(W), c_pitch - align4(W / 2), (phase of the first chroma plane, of the second)) of a PlanarOut."""
+    kind, y_off, ye, ce, phases = dl
+    return Y.PlanarOut(w, h, n, kind, y_off=y_off, ye=ye, ce=ce, phases=phases)
+
+
+def check_yuv420(c, w, h, n, seed, fmt, uv, op, sl, dl):
+    """sl as check_packed; dl as planar_out takes it.  Every allocation of the three planes, and the input's, compared whole."""
+    for flip in variants(n):
+        frames, key = content(w, h, n, fmt, seed, flip)
+        src = N.Batch(w, h, n, sl).upload(frames)
+        dst = planar_out(w, h, n, dl)
+        Y.run(c, op[0], op[1], src, dst.planes(), fmt, uv)
+        torch.cuda.synchronize()
+        want = dst.image([Y.expected_planes(f, w, fmt, op[0], op[1], uv, (key, k)) for k, f in enumerate(frames)])
+        why = dict(form="yuv420", w=w, h=h, n=n, fmt=fmt, uv=uv, op=op, src=sl, dst=dl, flip=flip)
+        for bi, (got, wnt) in enumerate(zip(dst.host(), want)):
+            assert np.array_equal(got, wnt), (why, "allocation", bi, first_bad(got, wnt))
+        got = src.host()
+        assert np.array_equal(got, src.image(frames)), (why, "the input allocation was written", first_bad(got, src.image(frames)))
+
+
 # ---- 1. phase matrix -------------------------------------------------------------------------------------------------------------
 def phase_src(off):
     return (g.PHASE_SRC["extra"], g.PHASE_SRC["gap"], off)
@@ -237,6 +264,34 @@ def test_phase_matrix_bgr(c, src_off):
                 check_bgr(c, w, h, n, 14, fmt, ORDERS[(src_off // 4 + di + fmt + oi) % 2], op, phase_src(src_off), dl)
 
 
+@pytest.mark.parametrize("src_off", g.PHASES)
+def test_phase_matrix_yuv420(c, src_off):
+    """The source offset crossed with the Y plane's; U and V at the first two of 0, 4, 8, 12 that neither has, V's address below U's
+    (YV12 order) for UYVY.  Y pitch W + 4 and chroma pitch W / 2 + 4: the Y phase advances by 12 a row, the chroma phases by 8."""
+    w, h, n = g.PHASE_W, g.PHASE_H, g.PHASE_N
+    ye, ce = g.PHASE_YUV420["ye"], g.PHASE_YUV420["ce"]
+    for di, y_off in enumerate(g.PHASES):
+        rest = tuple(p for p in g.PHASES if p not in (src_off, y_off))[:2]
+        for fmt in FMTS:
+            kind = "one" if fmt == FMT_YUY2 else "yv12"
+            for oi, op in enumerate(g.PHASE_OPS):
+                uv = UVS[(src_off // 4 + di + fmt + oi) % 2]
+                check_yuv420(c, w, h, n, 15, fmt, uv, op, phase_src(src_off), (kind, y_off, ye, ce, rest))
+
+
+@pytest.mark.parametrize("w", g.TAIL_WIDTHS)
+def test_every_chroma_tail_length_yuv420(c, w):
+    """33 .. 40 macropixels a row: the last group of a row holds 1, 2, ..., 8 macropixels, so store_c_tail, load422_tail and the
+    ragged branch of the interpolation run at every length (a dword, a 2-byte store and a byte in every combination), through the LUT
+    apply, the LDS interpolation and the wide-grid kernel, with both UV modes and both formats."""
+    h, n = g.TAIL_H, g.TAIL_N
+    assert g.tail_dwords(w // 2) == (w - 64) // 2
+    for op in g.TAIL_OPS:
+        for fmt in FMTS:
+            for uv in UVS:
+                check_yuv420(c, w, h, n, 16, fmt, uv, op, g.P4, g.TAIL_DST)
+
+
 # ---- 2. walks past their first step ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", g.LOOP_SHAPES, ids=[s["id"] for s in g.LOOP_SHAPES])
 def test_walks_past_their_first_step(c, shape):
@@ -254,6 +309,8 @@ def test_walks_past_their_first_step(c, shape):
                 check_packed(c, w, h, n, 21, fmt, UVS[k], op, shape["sl"], shape["dl"])
             elif form == "nv12":
                 check_nv12(c, w, h, n, 22, fmt, UVS[k], op, shape["sl"], nv12_layout(w, h, 4, 12, 4, 8, gap=8))
+            elif form == "yuv420":
+                check_yuv420(c, w, h, n, 25, fmt, UVS[k], op, shape["sl"], shape["dl"])
             else:
                 check_bgr(c, w, h, n, 23, fmt, ORDERS[k], op, shape["sl"], bgr_wide(w))
                 check_bgr(c, w, h, n, 23, fmt, ORDERS[1 - k], op, shape["sl"], bgr_bytes(w))
@@ -274,13 +331,15 @@ def test_tile_histogram_walk(c, shape):
 def test_rows_shorter_than_their_head(c, w):
     """One, two and three macropixels a row, eight rows, three frames; source pitch 2W + 4 at offset 4, destination pitch 2W + 12 at
     offset 12: rows that lie wholly before their first 16-byte boundary, next to rows that cross it.  NV12 out: UV rows of 2, 4 and 6
-    bytes, a single 2-byte store, a dword, a dword and a 2-byte store."""
+    bytes, a single 2-byte store, a dword, a dword and a 2-byte store.  Planar 4:2:0 out: chroma rows of 1, 2 and 3 bytes (a byte; a
+    2-byte store; a 2-byte store and a byte) at a chroma pitch of 4 or 8, the planes at offsets 12 / 8 / 4."""
     h, n = g.HEAD_H, g.HEAD_N
     for oi, op in enumerate(g.HEAD_OPS):
         for fmt in FMTS:
             uv = UVS[(oi + fmt + w // 2) % 2]
             check_packed(c, w, h, n, 31, fmt, uv, op, g.HEAD_SRC, g.HEAD_DST)
             check_nv12(c, w, h, n, 32, fmt, uv, op, g.HEAD_SRC, nv12_layout(w, h, 12, 4, 12, 8))
+            check_yuv420(c, w, h, n, 33, fmt, uv, op, g.HEAD_SRC, g.head_yuv420(w))
 
 
 # ---- 4. frame lists --------------------------------------------------------------------------------------------------------------
@@ -385,6 +444,51 @@ def test_frame_list_bgr(c):
                 assert np.array_equal(one_dst.host(), got), (why, "the list call and the batch call differ")
 
 
+def yuv420_list_call(c, w, h, kind, fmt, uv, op, seed):
+    """One list call on four frames -- `in` at offsets 0, 4, 8, 12; the planes of frame k one, two and three phases on, in three
+    allocations ("own") or with the U and V rows side by side in one pitched plane ("side": V = U + W / 2) -- compared per frame with
+    the oracle's image over the whole allocations, and with a single-frame batch call at the same phases."""
+    frames, keys = list_frames(w, h, fmt, seed)
+    srcs = [N.Batch(w, h, 1, (4, 0, off)).upload([f]) for off, f in zip(g.PHASES, frames)]
+    lays = [(kind, g.PHASES[(k + 1) % 4], 4, 4, (g.PHASES[(k + 2) % 4], g.PHASES[(k + 3) % 4])) for k in range(4)]
+    dsts = [planar_out(w, h, 1, lay) for lay in lays]
+    if kind == "side":
+        assert all(d.c_pitch == w and d.ptr("v") == d.ptr("u") + w // 2 for d in dsts)
+    entries = [BgrYuv420FrameDev(s.dev.data_ptr(), d.ptr("y"), d.ptr("u"), d.ptr("v")) for s, d in zip(srcs, dsts)]
+    a = (entries, w, h, srcs[0].pitch, dsts[0].y_pitch, dsts[0].c_pitch, CHROMA_PLANAR, fmt, uv)
+    if op[0] == "eq":
+        c.equalize_hist_packed422_to_yuv420_frames_dev(*a, stream=Y.stream())
+    else:
+        c.clahe_packed422_to_yuv420_frames_dev(*a, *op[1], stream=Y.stream())
+    torch.cuda.synchronize()
+    for k, (f, s, d) in enumerate(zip(frames, srcs, dsts)):
+        why = dict(form="yuv420 list", w=w, h=h, fmt=fmt, uv=uv, op=op, frame=k, src=(4, 0, s.off), dst=lays[k])
+        want = d.image([Y.expected_planes(f, w, fmt, op[0], op[1], uv, keys[k])])
+        got = d.host()
+        for bi, (gt, wnt) in enumerate(zip(got, want)):
+            assert np.array_equal(gt, wnt), (why, "allocation", bi, first_bad(gt, wnt))
+        assert np.array_equal(s.host(), s.image([f])), (why, "the input allocation was written")
+        one_dst = planar_out(w, h, 1, lays[k])
+        Y.run(c, op[0], op[1], s, one_dst.planes(), fmt, uv)
+        torch.cuda.synchronize()
+        for gt, one in zip(got, one_dst.host()):
+            assert np.array_equal(one, gt), (why, "the list call and the batch call differ", first_bad(one, gt))
+
+
+@pytest.mark.parametrize("kind", ["own", "side"], ids=["own-planes", "side-by-side"])
+def test_frame_list_yuv420(c, kind):
+    """40 x 6: two full groups and a ragged one of 4 macropixels; W / 2 = 20 is a multiple of 4, so the form accepts c_pitch = W with
+    c1 = c0 + W / 2.  Own planes also at 62 x 6, whose last group holds 7 macropixels: the table launches of the LUT apply, the LDS
+    interpolation and the wide-grid kernel run load422_tail and the dword, 2-byte and byte stores of store_c_tail."""
+    w, h = g.PHASE_W, g.PHASE_H
+    for fmt in FMTS:
+        for oi, op in enumerate(g.PHASE_OPS):
+            yuv420_list_call(c, w, h, kind, fmt, UVS[(oi + fmt) % 2], op, 44)
+            if kind == "own":
+                assert g.tail_dwords(62 // 2) == 7
+                yuv420_list_call(c, 62, h, kind, fmt, UVS[(oi + fmt + 1) % 2], op, 45)
+
+
 # ---- 5. seeded sweep -------------------------------------------------------------------------------------------------------------
 def sweep_layouts(case):
     """The two layouts of a case in the terms of its form's classes."""
@@ -395,6 +499,8 @@ def sweep_layouts(case):
         if case["uv_own"]:
             return case["sl"], (dl[0], case["uv_extra"], "own", dl[1], dl[2])
         return case["sl"], nv12_layout(w, h, dl[0], case["uv_extra"], dl[2], case["uv_phase"], gap=dl[1])
+    if case["form"] == "yuv420":
+        return case["sl"], g.yuv420_layout(case)
     if case["byte"]:
         return case["sl"], (dl[2] + 1, 3 * w + dl[0] + 1, dl[1] + 3)
     return case["sl"], (dl[2], align4(3 * w) + dl[0], dl[1])
@@ -406,13 +512,13 @@ def untouched(form, dst):
 
 @pytest.mark.parametrize("form", g.FORMS)
 def test_seeded_sweep(c, form):
-    """48 cases of one fixed seed for each output form (the same draws for all three), named by classify(): the census is a condition
+    """48 cases of one fixed seed for each output form (the same draws for all four), named by classify(): the census is a condition
     on the generator, asserted here and, without a GPU, in test_packed422_geometry_shapes.py.  A case the planar form refuses gives that
-    form's status and leaves the output allocation untouched."""
+    form's status and leaves the output allocation(s) -- all three planes' -- and the input untouched."""
     cases = g.sweep_cases(form)
     assert g.census_holds(cases), {k: v[0] for k, v in g.census(cases).items()}
-    check = {"packed": check_packed, "nv12": check_nv12, "bgr": check_bgr}[form]
-    M = {"packed": P, "nv12": N, "bgr": B}[form]
+    check = {"packed": check_packed, "nv12": check_nv12, "bgr": check_bgr, "yuv420": check_yuv420}[form]
+    M = {"packed": P, "nv12": N, "bgr": B, "yuv420": N}[form]
     for i, case in enumerate(cases):
         w, h, n, fmt, op = case["w"], case["h"], case["n"], case["fmt"], g.op_of(case)
         sl, dl = sweep_layouts(case)
@@ -424,9 +530,15 @@ def test_seeded_sweep(c, form):
         assert status != 0, (i, case)
         frames, _ = content(w, h, n, fmt, 500 + i)
         src = M.Batch(w, h, n, sl).upload(frames)
-        dst = BgrAt(w, h, n, *dl) if form == "bgr" else (P.Batch if form == "packed" else N.Nv12Out)(w, h, n, dl)
+        if form == "yuv420":
+            dst = planar_out(w, h, n, dl)
+        else:
+            dst = BgrAt(w, h, n, *dl) if form == "bgr" else (P.Batch if form == "packed" else N.Nv12Out)(w, h, n, dl)
         with pytest.raises(mi_lumaeq.MiError) as e:
-            M.run(c, op[0], op[1], src, dst, fmt, case["uv"])
+            if form == "yuv420":
+                Y.run(c, op[0], op[1], src, dst.planes(), fmt, case["uv"])
+            else:
+                M.run(c, op[0], op[1], src, dst, fmt, case["uv"])
         torch.cuda.synchronize()
         assert e.value.status == status, (i, case, e.value.status, status)
         assert untouched(form, dst), (i, case, "a refused call wrote")

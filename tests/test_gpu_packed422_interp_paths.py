@@ -1,7 +1,7 @@
-"""Every rung of the CLAHE interpolation ladder on packed 4:2:2 input (YUY2 / UYVY), through every device form: packed out and NV12
-out, each as a strided batch and as a list of frames.  The host picks the interpolation kernel from (writer, list or batch, float or
-quad tables, clahe_fp_contract, format, LDS or global tables); the four sizes below are the smallest that reach each branch of that
-choice, and the options clahe_float_tables and clahe_fp_contract are set both ways, so that every instantiation runs.  64 x 8 and
+"""Every rung of the CLAHE interpolation ladder on packed 4:2:2 input (YUY2 / UYVY), through every device form: packed out, NV12 out
+and planar 4:2:0 out (I420 / YV12), each as a strided batch and as a list of frames.  The host picks the interpolation kernel from
+(writer, list or batch, float or quad tables, clahe_fp_contract, format, LDS or global tables); the sizes below are the smallest that
+reach each branch of that choice, and the options clahe_float_tables and clahe_fp_contract are set both ways, so that every instantiation runs.  64 x 8 and
 128 x 8 have tiles of 4 x 4 and 2 x 4 pixels: 1 / tile is exact there, FMA and mul + add round alike and both arithmetic modes give the
 same bytes, so those two rungs cannot tell an FMA body from a plain one.  96 x 10 and 192 x 10 (tiles 6 x 5 and 3 x 5) reach the same
 two kernels on shapes where the modes differ; their luma is tests/clahe_u8_rungs.py content, on which the test first shows that they do.
@@ -10,14 +10,22 @@ two kernels on shapes where the modes differ; their luma is tests/clahe_u8_rungs
     64 x 48,   8 x 8:   9 pairs <= 15: one float table; uchar quads when clahe_float_tables = 0
     1792 x 8,  16 x 2:  17 pairs > 15, tile_w = 112: (9 - 3) * 112 / 16 = 42 >= 40 column groups per segment, so float tables on
                         column segments (112 groups in ceil(112 / 42) = 3 segments); quads in one segment when clahe_float_tables = 0
+    1790 x 8,  16 x 2:  17 pairs > 15, the width pads to 1792: tile_w = 112 and 42 groups a segment again, so float tables on column
+                        segments: 112 groups in 3 segments of 38, 38 and 36, and the LAST group (x0 = 1776, 7 macropixels) is ragged in
+                        the last segment: the dword-by-dword branch with p0 != 0 and blockIdx.z > 0.  With clahe_float_tables = 0
+                        the same shape is the ragged quad path in one segment
     64 x 8,    16 x 2:  17 pairs > 15, tile_w = 4: (9 - 3) * 4 / 16 = 1 < 40, quads whatever clahe_float_tables says
     128 x 8,   64 x 2:  65 pairs > 63: the global-LUT kernel
     96 x 10,   16 x 2:  17 pairs > 15, tile_w = 6: (9 - 3) * 6 / 16 = 2 < 40, quads again, on tiles that are no power of two
     192 x 10,  64 x 2:  65 pairs > 63: the global-LUT kernel again, tile_w = 3
 
+How many column segments plan_interp422 makes is not observable: the rungs are chosen from its arithmetic, restated above, and the
+segment count is not asserted against the library.  The float-table rungs (64 x 48, 1792 x 8, 1790 x 8) are the only ones that run the
+float-table bodies, so the test first shows that the two arithmetic modes differ on their D1 / D2 / D3 content too.
+
 The expected luma is oracle.clahe on the gathered luma in the arithmetic mode of the call (oracle.set_fp_contract); chroma is copied
-(packed out) or the rounding mean of each row pair (NV12 out).  Every plane lies in a sentinel-filled allocation at a padded pitch,
-the WHOLE allocations are compared, and every comparison is exact bytes."""
+(packed out), the rounding mean of each row pair (NV12 out), or the even (U) and odd (V) columns of that mean (planar out).  Every plane
+lies in a sentinel-filled allocation at a padded pitch, the WHOLE allocations are compared, and every comparison is exact bytes."""
 import numpy as np
 import pytest
 import torch
@@ -26,6 +34,7 @@ import mi_lumaeq
 import oracle
 import clahe_u8_rungs
 from mi_lumaeq import synth, UV_COPY, FMT_YUY2, FMT_UYVY
+from mi_lumaeq.capi import Yuv420Planes, BgrYuv420FrameDev, CHROMA_PLANAR
 
 pytestmark = pytest.mark.gpu
 SENT = 0x5A
@@ -33,14 +42,16 @@ N = 3
 DISTS = ["D1", "D2", "D3"]
 CLIP = 2.0
 # (width, height, tiles_x, tiles_y): plain float tables, column-segment float tables, quad fallback of a wide grid, global LUTs;
-# then the last two again on tiles where the arithmetic mode shows
-SHAPES = [(64, 48, 8, 8), (1792, 8, 16, 2), (64, 8, 16, 2), (128, 8, 64, 2), (96, 10, 16, 2), (192, 10, 64, 2)]
-MODE_SHAPES = SHAPES[4:]                                         # luma from clahe_u8_rungs.content, not from D1 / D2 / D3
-FORMS = ["packed_batch", "packed_list", "nv12_batch", "nv12_list"]
+# then the last two again on tiles where the arithmetic mode shows; then column segments whose last group is ragged
+SHAPES = [(64, 48, 8, 8), (1792, 8, 16, 2), (64, 8, 16, 2), (128, 8, 64, 2), (96, 10, 16, 2), (192, 10, 64, 2), (1790, 8, 16, 2)]
+MODE_SHAPES = SHAPES[4:6]                                        # luma from clahe_u8_rungs.content, not from D1 / D2 / D3
+FLOAT_SHAPES = [SHAPES[0], SHAPES[1], SHAPES[6]]                 # the rungs that run float tables: the modes differ on D1 / D2 / D3 there
+FORMS = ["packed_batch", "packed_list", "nv12_batch", "nv12_list", "yuv420_batch", "yuv420_list"]
 FMTS = [FMT_YUY2, FMT_UYVY]
 # (clahe_float_tables, clahe_fp_contract); the first is the default pair, whose bytes the other pair with fp_contract 0 must repeat
 OPTIONS = [(1, 0), (0, 0), (1, 1), (0, 1)]
 OFFS = (4, 8, 12)                                                # bytes past a 16-byte boundary
+OFFS4 = (0, 4, 8, 12)                                            # the planar list: in, Y, U and V of a frame each at its own
 
 
 def stream():
@@ -49,6 +60,10 @@ def stream():
 
 def align4(x):
     return (x + 3) & ~3
+
+
+def up16(x):
+    return (x + 15) & ~15
 
 
 def luma(frame, w, fmt):
@@ -113,10 +128,20 @@ class Layout:
         b = self.alloc(off + fstride * N + 64)
         return [(b, off + k * fstride, pitch) for k in range(N)]
 
-    def frames(self, rows, pitch, first):
+    def frames(self, rows, pitch, first, offs=OFFS):
         """N planes, each in an allocation of its own at its own offset."""
-        offs = [OFFS[(first + k) % 3] for k in range(N)]
+        offs = [offs[(first + k) % len(offs)] for k in range(N)]
         return [(self.alloc(o + pitch * rows + 64), o, pitch) for o in offs]
+
+    def planes3(self, h, y_pitch, c_pitch):
+        """N frames of three planes (H rows, H / 2, H / 2) in ONE allocation with one frame stride: Y, U and V start 4, 8 and 12 bytes
+        past a 16-byte boundary, and the stride is 4 past one, so every frame's planes have phases of their own."""
+        y_at = OFFS[0]
+        u_at = up16(y_at + y_pitch * h) + OFFS[1]
+        v_at = up16(u_at + c_pitch * (h // 2)) + OFFS[2]
+        fstride = up16(v_at + c_pitch * (h // 2) - y_at) + 4
+        b = self.alloc(y_at + fstride * N + 64)
+        return fstride, [[(b, at + k * fstride, pitch) for k in range(N)] for at, pitch in ((y_at, y_pitch), (u_at, c_pitch), (v_at, c_pitch))]
 
     def ptr(self, at):
         return self.bufs[at[0]].data_ptr() + at[1]
@@ -146,7 +171,7 @@ class Case:
     def __init__(self, form, shape):
         self.form, self.shape = form, shape
         w, h = shape[:2]
-        self.nv12, self.list = form.startswith("nv12"), form.endswith("list")
+        self.nv12, self.yuv420, self.list = form.startswith("nv12"), form.startswith("yuv420"), form.endswith("list")
         self.lay = lay = Layout()
         self.in_pitch = 2 * w + 4
         self.in_frame = self.in_pitch * h + 20
@@ -159,6 +184,13 @@ class Case:
             else:
                 self.ys = lay.batch(self.y_pitch, self.out_frame, 8)
                 self.uvs = lay.batch(self.uv_pitch, self.out_frame, 12)
+        elif self.yuv420:
+            self.y_pitch, self.c_pitch = align4(w) + 4, align4(w // 2) + 12
+            if self.list:                                                   # frame 0: in at 4, Y at 8, U at 12, V at 0
+                self.ys = lay.frames(h, self.y_pitch, 2, OFFS4)
+                self.us, self.vs = lay.frames(h // 2, self.c_pitch, 3, OFFS4), lay.frames(h // 2, self.c_pitch, 0, OFFS4)
+            else:
+                self.out_frame, (self.ys, self.us, self.vs) = lay.planes3(h, self.y_pitch, self.c_pitch)
         else:
             self.out_pitch = 2 * w + 36
             self.out_frame = self.out_pitch * h
@@ -177,6 +209,16 @@ class Case:
                 c.clahe_packed422_to_nv12_batch_dev(ins[0], ys[0], uvs[0], w, h, N, fmt, UV_COPY, CLIP, tx, ty, in_pitch=self.in_pitch,
                                                     in_frame=self.in_frame, y_pitch=self.y_pitch, uv_pitch=self.uv_pitch,
                                                     out_frame=self.out_frame, stream=stream())
+        elif self.yuv420:
+            ys, us, vs = [p(a) for a in self.ys], [p(a) for a in self.us], [p(a) for a in self.vs]
+            if self.list:
+                entries = [BgrYuv420FrameDev(*a) for a in zip(ins, ys, us, vs)]
+                c.clahe_packed422_to_yuv420_frames_dev(entries, w, h, self.in_pitch, self.y_pitch, self.c_pitch, CHROMA_PLANAR, fmt, UV_COPY,
+                                                       CLIP, tx, ty, stream=stream())
+            else:
+                planes = Yuv420Planes(ys[0], self.y_pitch, us[0], vs[0], self.c_pitch, self.out_frame, CHROMA_PLANAR)
+                c.clahe_packed422_to_yuv420_batch_dev(ins[0], planes, w, h, N, fmt, UV_COPY, CLIP, tx, ty, in_pitch=self.in_pitch,
+                                                      in_frame=self.in_frame, stream=stream())
         else:
             outs = [p(a) for a in self.outs]
             if self.list:
@@ -194,6 +236,9 @@ class Case:
             y = y_ref(self.shape, k, contract)
             if self.nv12:
                 painted += [(self.ys[k], y), (self.uvs[k], uv_mean(chroma(f, w, fmt)))]
+            elif self.yuv420:
+                uv = uv_mean(chroma(f, w, fmt))
+                painted += [(self.ys[k], y), (self.us[k], uv[:, 0::2]), (self.vs[k], uv[:, 1::2])]
             else:
                 out = f.copy()
                 out[:, fmt - 2::2] = y
@@ -214,7 +259,7 @@ def test_every_rung(c, shape, form):
     oracle's in the call's arithmetic mode, and with clahe_fp_contract = 0 also those of the default tables (the same bytes on
     every path)."""
     w, h = shape[:2]
-    if shape in MODE_SHAPES:                                     # the two arithmetic modes are told apart on this shape
+    if shape in MODE_SHAPES or shape in FLOAT_SHAPES:            # the two arithmetic modes are told apart on this shape
         assert any(not np.array_equal(y_ref(shape, k, 0), y_ref(shape, k, 1)) for k in range(N)), (shape, "both modes give the same bytes")
     case = Case(form, shape)
     try:

@@ -14,7 +14,7 @@ import torch
 import mi_lumaeq
 import clahe_u8_rungs
 import packed422_bgr_ref as ref
-import test_gpu_packed422_interp_paths as interp_paths          # the six rung shapes and the four option pairs are read from there
+import test_gpu_packed422_interp_paths as interp_paths          # the seven rung shapes and the four option pairs are read from there
 from mi_lumaeq import synth, UV_COPY, FMT_YUY2, FMT_UYVY, ORDER_BGR, ORDER_RGB
 
 pytestmark = pytest.mark.gpu
@@ -261,7 +261,7 @@ def test_every_rung(c, shape):
     and the batch form's."""
     w, h, tx, ty = shape
     cfg = (interp_paths.CLIP, tx, ty)
-    assert len(interp_paths.SHAPES) == 6 and len(interp_paths.OPTIONS) == 4
+    assert len(interp_paths.SHAPES) == 7 and len(interp_paths.OPTIONS) == 4
     try:
         for fmt in FMTS:
             frames = [rung_frame(shape, fmt, k) for k in range(2)]

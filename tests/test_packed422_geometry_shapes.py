@@ -22,6 +22,32 @@ def test_restated_slot_arithmetic_is_the_headers():
     assert "s.d0=a;s.n=max(b-a,0);" in src
 
 
+def test_restated_planar_apply_walk_is_the_headers():
+    """walk("lut_apply422_yuv420") takes lut_apply422_nv12's numbers: the planar writer's header still cuts row pairs into groups of
+    eight macropixels and steps by kThreads items."""
+    src = re.sub(r"\s+", "", (KERNELS / "packed422_yuv420.hip.h").read_text())
+    body = src[src.index("voidlut_apply422_yuv420_body("): src.index("voidlut_apply422_yuv420_kernel(")]
+    assert "constintG=(p.dwords+7)>>3;" in body
+    assert "it+=kThreads" in body
+    assert "pairs=p.rows>>1" in body
+    assert "constintnd=min(8,p.dwords-8*grp);" in body
+    for w, h in ((66, 386), (16386, 2), (62, 200)):
+        assert g.walk("lut_apply422_yuv420", w, h) == g.walk("lut_apply422_nv12", w, h)
+
+
+def test_tail_widths_give_every_tail_length():
+    """33 .. 40 macropixels a row: the last group of a row holds 1, 2, ..., 8 of them, in that order."""
+    assert [g.tail_dwords(w // 2) for w in g.TAIL_WIDTHS] == [1, 2, 3, 4, 5, 6, 7, 8]
+    assert {min(8, w // 2 - 8 * (g.groups422(w // 2) - 1)) for w in g.TAIL_WIDTHS} == set(range(1, 9))
+    kind, y_off, ye, ce, phases = g.TAIL_DST
+    assert (y_off,) + phases == (4, 8, 12) and ye > 0 and ce > 0
+    # the short rows: chroma rows of 1, 2 and 3 bytes at a pitch of 4 or 8, planes at 12 / 8 / 4
+    for w in g.HEAD_WIDTHS:
+        kind, y_off, ye, ce, phases = g.head_yuv420(w)
+        assert (y_off,) + phases == (12, 8, 4) and ((w // 2 + 3) & ~3) + ce in (4, 8)
+    assert {((w // 2 + 3) & ~3) + g.head_yuv420(w)[3] for w in g.HEAD_WIDTHS} == {4, 8}
+
+
 @pytest.mark.parametrize("phase", g.PHASES)
 def test_slots_partition_a_row(phase):
     """For every row phase and 1..40 dwords: the slots tile [0, dwords) once and in order, only the first and the last non-empty slot
@@ -77,6 +103,13 @@ def test_loop_table_says_what_its_comments_say():
     assert w("62x200-nv12", "lut_apply422_nv12") == (400, 4, 256, 1) and 31 - 8 * 3 == 7
     assert w("66x200-nv12", "lut_apply422_nv12") == (500, 5, 256, 1) and 33 - 8 * 4 == 1
     assert w("66x386-bgr", "lut_apply422_bgr") == (640, 5, 256, 3)
+    assert w("66x386-yuv420", "lut_apply422_yuv420") == (320, 5, 256, 3) and 193 * 1 // 3 == 64 and 256 // 5 == 51 and 256 % 5 == 1
+    assert w("66x386-yuv420", "hist422_partial") == (1280, 10, 1024, 3)
+    assert by["66x386-yuv420"]["n"] == 2 and by["66x386-yuv420"]["sl"][1] == 4               # frames 4 bytes apart
+    assert w("16386x2-yuv420", "lut_apply422_yuv420") == (1025, 1025, 256, 4)
+    assert w("16386x2-yuv420", "hist422_partial") == (2050, 2050, 1024, 2)
+    sl, dl = by["16386x2-yuv420"]["sl"], by["16386x2-yuv420"]["dl"]
+    assert len({sl[2], dl[1]} | set(dl[4])) == 4                                             # source, Y, U and V at four phases
     # both forms and the packed walks with drow == 0 and drow > 0 are there
     assert {s["form"] for s in g.LOOP_SHAPES} == set(g.FORMS)
 
@@ -134,10 +167,33 @@ def test_sweep_census_holds_for_the_committed_seed():
         assert all(cen[k][0] >= 6 for k in g.CLASSES[:4]) and 1 <= cen[g.CLASSES[4]][0] <= 4
         for c in cases:
             assert c["w"] % 2 == 0 and 2 <= c["w"] <= 160 and 1 <= c["h"] <= 48 and 1 <= c["n"] <= 3
-            assert form != "nv12" or c["h"] % 2 == 0
+            assert form not in ("nv12", "yuv420") or c["h"] % 2 == 0
             assert all(v % 4 == 0 for v in c["sl"] + c["dl"])
         assert sum(c["w"] % 16 == 0 for c in cases) >= 16 and sum(c["w"] % 4 == 2 for c in cases) >= 8
     # every form draws the same numbers
     a, b = g.sweep_cases("packed"), g.sweep_cases("bgr")
     assert [(c["w"], c["h"], c["sl"], c["dl"]) for c in a] == [(c["w"], c["h"], c["sl"], c["dl"]) for c in b]
     assert g.sweep_cases("packed") == g.sweep_cases("packed")
+
+
+def test_sweep_yuv420_draws_what_the_other_forms_draw():
+    """The planar 4:2:0 form adds no draw: its cases have the widths and layouts of `packed`, the heights of `nv12`, hence the census
+    of both; its chroma planes come from the four numbers every form draws last, and all of them are multiples of 4."""
+    y, p, n = g.sweep_cases("yuv420"), g.sweep_cases("packed"), g.sweep_cases("nv12")
+    assert [(c["w"], c["sl"], c["dl"]) for c in y] == [(c["w"], c["sl"], c["dl"]) for c in p]
+    assert [c["h"] for c in y] == [c["h"] for c in n]
+    keys = ("n", "kind", "tx", "ty", "clip", "fmt", "uv")
+    assert [[c[k] for k in keys] for c in y] == [[c[k] for k in keys] for c in p]
+    assert [(c["c_extra"], c["u_phase"], c["c_own"]) for c in y] == [(c["uv_extra"], c["uv_phase"], c["uv_own"]) for c in n]
+    assert [c["yv12"] for c in y] == [c["byte"] for c in g.sweep_cases("bgr")]
+    assert [g.census(y)[k][0] for k in g.CLASSES] == [7, 17, 14, 7, 3] == [g.census(p)[k][0] for k in g.CLASSES]
+    kinds = set()
+    for c in y:
+        kind, y_off, ye, ce, (pa, pb) = g.yuv420_layout(c)
+        kinds.add(kind)
+        c_pitch = ((c["w"] // 2 + 3) & ~3) + ce
+        assert c_pitch % 4 == 0 and c_pitch >= c["w"] // 2 and all(v % 4 == 0 and 0 <= v < 16 for v in (pa, pb)) and y_off % 4 == 0 and ye % 4 == 0
+        assert (pa - pb) % 16 in (4, 12)                         # V = U + 4 or U - 4 modulo 16: never the same phase
+        u = pb if kind == "yv12" else pa
+        assert u == c["u_phase"]
+    assert kinds == {"one", "yv12", "own"}
